@@ -21,13 +21,19 @@ The reads are generated on the device before the timed region: `value` is throug
            127.0.0.1); under an external launcher (torch.distributed.run) it is one of the ranks.  Per GPU the work is 12.5 Gbp
            (BASELINE configs[3]: 100 Gbp over 8 GPUs), the same at every N > 1: weak scaling.
 
-Prints ONE JSON line (rank 0).  `value` comes from the contract's timed region (K steps, once); `repeats` re-runs the
-same job a few more times (median/min/max), `flush_sweep` forces 1/2/4/8 flushes per job, `end_to_end` is the Counting
-phase of `jellyfish-amd count` from a FASTA file of the same reads (host read + H2D + device parse included), `roofline`
-and `cpu_baseline` are the contract's extra objects (algorithmic bytes per k-mer from SURVEY 8(d); the reference's own
-CPU path, oracle/_ref, timed on this box's host cores on a bounded sample, its table's content digest compared with the
-engine's on the same sample), `secondary` carries BASELINE configs[2] and configs[4] (C3, C5: one job each, run after the
-metric's own work in child processes of this script).  The oracle is only baseline / checker here.
+Prints ONE JSON line (rank 0).  `value` comes from the contract's timed region (K steps, once).  A plain run sets up,
+warms up, times the K steps and prints the line (per-stage times of the timed steps in `kernels` and `roofline`).
+  --dump-outputs DIR : after the timed steps, what the counting path handed back -- table statistics, content digest,
+           count histogram and the counts of every k-mer of a fixed, seeded sample of the reads -- as float64 .npy files.
+  --full : everything else as well.  `repeats` re-runs the same job a few more times (median/min/max), `flush_sweep`
+           forces 1/2/4/8 flushes per job, `end_to_end` is the Counting phase of `jellyfish-amd count` from a FASTA file of
+           the same reads (host read + H2D + device parse included), `roofline` gains the GUPS denominators and
+           `cpu_baseline` is the contract's extra object (algorithmic bytes per k-mer from SURVEY 8(d); the reference's own
+           CPU path, oracle/_ref, timed on this box's host cores on a bounded sample, its table's content digest compared
+           with the engine's on the same sample), `secondary` carries BASELINE configs[2] and configs[4] (C3, C5: one job
+           each, run after the metric's own work in child processes of this script).  --no-extras, --no-secondary and
+           --no-cpu-baseline narrow a --full run.  The oracle is only baseline / checker here (and, for --dump-outputs,
+           the host-side extraction of the sampled reads' k-mers).
 """
 import argparse
 import json
@@ -213,6 +219,40 @@ def cpu_baseline(cfg, sample, k, tmpdir, job_load=0.5):
     return res, stats
 
 
+DUMP_READS = 4096                                # reads whose k-mers --dump-outputs looks up in the finished table
+DUMP_SEED = 20240601
+
+
+def _u32_halves(words):
+    """uint64 array (..., w) -> float64 (..., 2w): low and high 32 bits of every word, exact in float64."""
+    import numpy as np
+    w = np.asarray(words, dtype=np.uint64)
+    return np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=-1).reshape(w.shape[:-1] + (2 * w.shape[-1],)).astype(np.float64)
+
+
+def dump_outputs(out_dir, t, reads_to_host, n_reads, k, digest):
+    """--dump-outputs: what a caller of the counting path gets back from the finished table, as float64 .npy files (key and
+    digest words split into 32-bit halves, so that every value is exact).  stats: unique, distinct, total, max_count,
+    mers_fed; digest: the content digest (records, sum of counts, sum of h, xor of h); histo: the count histogram 1..10000
+    (`jellyfish histo`); sample_keys / sample_counts: every k-mer of DUMP_READS reads drawn with a fixed seed (k-mers
+    extracted on the host by the oracle, canonical) and its count in the table (0 where absent).  About 13 MB at k = 21."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    os.makedirs(out_dir, exist_ok=True)
+    st = t.stats()
+    np.save(os.path.join(out_dir, "stats.npy"), np.array([st.unique, st.distinct, st.total, st.max_count, st.mers_fed], dtype=np.float64))
+    np.save(os.path.join(out_dir, "digest.npy"), _u32_halves(np.array(digest, dtype=np.uint64)))
+    _, _, h = t.histo(1, 10000, 1)
+    np.save(os.path.join(out_dir, "histo.npy"), h.astype(np.float64))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_reads, size=min(DUMP_READS, n_reads), replace=False))
+    seq = b"".join(reads_to_host(int(r), int(r) + 1).tobytes() for r in rows)      # every read ends in 'N': no k-mer spans two
+    keys = np.ascontiguousarray(O.extract(seq, k, True))
+    vals, found = t.lookup(keys)
+    np.save(os.path.join(out_dir, "sample_keys.npy"), _u32_halves(keys))
+    np.save(os.path.join(out_dir, "sample_counts.npy"), np.where(found, vals, 0).astype(np.float64))
+
+
 def spawn_ranks(n):
     """python bench.py --gpus N from a bare shell: N copies of this command, one rank per GPU, rendezvous on 127.0.0.1 (what
     torch.distributed.run would set up).  Rank 0's stdout (the JSON line) is this process's; a failing rank ends the others,
@@ -336,8 +376,14 @@ def main():
     ap.add_argument("--matrix", choices=["xs", "reference"], default="xs",
                     help="hash matrix family of the table (include/jfgpu.h: JFGPU_MATRIX_*): xs = the xor-shift matrix the partition kernel evaluates in "
                          "registers; reference = the matrix `jellyfish count` itself draws (file bodies byte-identical to the reference's)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: repeats, GUPS roofline denominators, CPU baseline, flush sweep, end-to-end run and the "
+                         "secondary configurations (a plain run does only what its headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the counting path computed as DIR/<name>.npy (float64; --gpus 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the whole job is run in all (first = the contract's timed region)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how many times the whole job is run in all (first = the contract's timed region; default 5 with --full, else 1)")
     ap.add_argument("--no-extras", action="store_true", help="skip flush sweep, end-to-end and the secondary configurations (quick runs, profiling)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the C5 / C3 jobs attached to the default C2 line")
     ap.add_argument("--as-secondary", action="store_true", help=argparse.SUPPRESS)      # child of the default run: one job, compact line
@@ -349,8 +395,14 @@ def main():
     if args.plan:
         print(json.dumps(plan(args)))
         return
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs writes one table's outputs: use it with --gpus 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
+    if not args.full:
+        args.no_extras = True; args.no_cpu_baseline = True
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.as_secondary:
         args.no_extras = True; args.no_cpu_baseline = True
         if "--repeats" not in sys.argv:
@@ -445,7 +497,7 @@ def main():
 
     # random-access roofline denominator on this very table (dirty afterwards -> cleared)
     gups = {}
-    if rank == 0 and cfg != "C5":
+    if rank == 0 and cfg != "C5" and args.full:
         for mode, name in ((0, "atomic_add"), (2, "atomic_cas")):
             gups[name] = t.gups(1 << 28, mode)
     t.clear()
@@ -578,6 +630,8 @@ def main():
         assert int(tot[0]) == total_kmers, "counted %d k-mers, expected %d" % (int(tot[0]), total_kmers)
     digest = t.digest() if world == 1 else None
     ctrs = t.counters()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, t, reads_to_host, n_reads, K, digest)
 
     out = None
     if rank == 0:
@@ -817,7 +871,7 @@ def main():
             try:
                 if "--matrix" not in extra:
                     extra = extra + ["--matrix", args.matrix]
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", c, "--as-secondary", "--steps", str(steps), "--warmup", str(warmup)] + extra,
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", c, "--as-secondary", "--full", "--steps", str(steps), "--warmup", str(warmup)] + extra,
                                    capture_output=True, text=True, timeout=900, preexec_fn=_all_cpus)
                 line = [l for l in r.stdout.splitlines() if l.startswith("{")]
                 if r.returncode == 0 and line:

@@ -1,6 +1,6 @@
 """ctypes binding of the parity oracle (oracle/jf_oracle.c) -- TEST INFRASTRUCTURE.
 
-Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
+Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg and --dump-outputs sample import this.
 """
 import ctypes as C
 import os

@@ -3,11 +3,11 @@
 cd "$(dirname "$0")/.."
 O=gpurun_out
 last_json() { grep '^{' | tail -1; }
-python bench.py 2> $O/r06_final_default.err | last_json > $O/r06_final_bench_default.json
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-extras 2> /dev/null | last_json > $O/r06_final_bench_steps20_warmup5.json
-JFGPU_BENCH_FORCE_DIST=1 python bench.py --no-extras --no-cpu-baseline 2> /dev/null | last_json > $O/r06_final_bench_C2_sharded_path_one_gpu.json
-timeout 600 python bench.py --gpus 2 --no-extras --no-cpu-baseline 2> $O/r06_final_gpus2.err | last_json > $O/r06_final_bench_gpus2_on_one_device.json
-timeout 600 python bench.py --gpus 4 --no-extras --no-cpu-baseline 2> $O/r06_final_gpus4.err | last_json > $O/r06_final_bench_gpus4_on_one_device.json
+python bench.py --full 2> $O/r06_final_default.err | last_json > $O/r06_final_bench_default.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-extras 2> /dev/null | last_json > $O/r06_final_bench_steps20_warmup5.json
+JFGPU_BENCH_FORCE_DIST=1 python bench.py --full --no-extras --no-cpu-baseline 2> /dev/null | last_json > $O/r06_final_bench_C2_sharded_path_one_gpu.json
+timeout 600 python bench.py --full --gpus 2 --no-extras --no-cpu-baseline 2> $O/r06_final_gpus2.err | last_json > $O/r06_final_bench_gpus2_on_one_device.json
+timeout 600 python bench.py --full --gpus 4 --no-extras --no-cpu-baseline 2> $O/r06_final_gpus4.err | last_json > $O/r06_final_bench_gpus4_on_one_device.json
 for f in default steps20_warmup5 C2_sharded_path_one_gpu gpus2_on_one_device gpus4_on_one_device; do
   python - $O/r06_final_bench_$f.json <<'PY'
 import json, sys

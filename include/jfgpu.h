@@ -42,7 +42,9 @@ enum {
   JFGPU_E_FULL = 4,       /* std::runtime_error("Hash full"), hash_counter.hpp:194-195 */
   JFGPU_E_HIP = 5,        /* HIP runtime error */
   JFGPU_E_UNSUPPORTED = 6,/* combination not built (e.g. k > 128, a sharded table for k > 64, --bc / --if over shards of two-word keys) */
-  JFGPU_E_FORMAT = 7      /* device parser: chunk is not in the strict layout it handles; give it to the host parser */
+  JFGPU_E_FORMAT = 7,     /* device parser: chunk is not in the strict layout it handles; give it to the host parser */
+  JFGPU_E_CORRUPT = 8     /* compressed input (BGZF / BAM) is malformed or fails its CRC32 / ISIZE check: there is no
+                             host path for it, the input is bad (htslib's "bgzf_read" / "truncated file" errors) */
 };
 
 typedef struct jfgpu_table jfgpu_table; /* opaque: one hash shard resident in one GPU's HBM */
@@ -371,6 +373,46 @@ int  jfgpu_parser_parse_uploaded(jfgpu_parser* p, int which, unsigned flags,
  * jfgpu_parser_parse_dev is edited in place when this is on.  FASTA input has no qualities: unaffected, as in the reference. */
 int  jfgpu_parser_set_min_quality(jfgpu_parser* p, int min_qual_char);
 int  jfgpu_parser_last_ms(jfgpu_parser* p, double* ms);
+
+/* ---- BAM / SAM input: BGZF inflated and BAM records decoded on the device ----
+ * Replaces htslib's sam_open / sam_hdr_read / sam_read1 behind jellyfish::sam_wrapper
+ * (include/jellyfish/sam_format.hpp) as read by mer_overlap_sequence_parser::read_sam (:220-250) and
+ * whole_sequence_parser (:192-210): BGZF members in, the contract buffer (the bases of every record,
+ * one 'N' after each) out, in device memory.  Every record counts, whatever its flags; bases as
+ * stored (4-bit codes 1 A, 2 C, 4 G, 8 T, anything else N); with jfgpu_parser_set_min_quality a
+ * base whose quality character (char)(q + '!') is below the minimum (signed compare,
+ * mer_qual_iterator.hpp:76-77) becomes N -- a missing quality (0xFF) always does.
+ *
+ * One BGZF member: compressed deflate data at c_off (relative to the uploaded chunk), c_len bytes,
+ * inflating to isize <= 65536 bytes with the given CRC32; u_off = sum of the isize of the blocks before
+ * it in the same table. */
+typedef struct jfgpu_bgzf_block {
+  uint64_t c_off, u_off;
+  uint32_t c_len, isize, crc32, reserved;
+} jfgpu_bgzf_block;
+/* Host only, no device: the block table of the whole BGZF members at the start of bytes[0, n) (at most cap),
+ * read from each member's XLEN and 'BC' subfield and its trailer -- nothing is inflated.  *n_used = bytes of
+ * those members; a member cut by the end of the window is left out.  JFGPU_E_CORRUPT: not gzip, or gzip
+ * without the BGZF field (plain gzip), or a member that inflates to more than 64 KiB. */
+int  jfgpu_bgzf_scan(const void* bytes, size_t n, jfgpu_bgzf_block* out, size_t cap, size_t* n_blocks, size_t* n_used);
+/* Inflate the members of the chunk uploaded into buffer `which` (jfgpu_parser_upload) on the device, one
+ * wavefront per member, ISIZE and CRC32 checked per member as bgzf_read does; the output is appended to
+ * the parser's inflated stream, *stream_len is its new length.  A bad member: JFGPU_E_CORRUPT naming it,
+ * nothing appended. */
+int  jfgpu_parser_inflate_uploaded(jfgpu_parser* p, int which, const jfgpu_bgzf_block* blocks, size_t n_blocks,
+                                   size_t* stream_len);
+/* Copy inflated stream bytes [offset, offset + n) to host memory (the BAM header, SAM text). */
+int  jfgpu_parser_stream_read(jfgpu_parser* p, size_t offset, size_t n, void* dst);
+/* Drop the first n bytes of the inflated stream. */
+int  jfgpu_parser_stream_consume(jfgpu_parser* p, size_t n);
+/* BAM records (sam_read1 over bam1_t, sam_format.hpp:55-95): skip the first `skip` bytes of the inflated
+ * stream (the rest of the header), then decode every complete record into the contract buffer (*d_out,
+ * *n_out; same lifetime rule as jfgpu_parser_parse).  n_ref (the header's reference count) only sharpens
+ * the search for record starts.  The incomplete last record stays in the stream (*n_left bytes) and is
+ * completed by the next jfgpu_parser_inflate_uploaded: chunks may end anywhere in a record.
+ * JFGPU_E_CORRUPT: a record whose lengths do not add up. */
+int  jfgpu_parser_bam_decode(jfgpu_parser* p, size_t skip, int32_t n_ref, const char** d_out, size_t* n_out,
+                             uint64_t* n_records, size_t* n_left);
 
 /* ---- measurement helpers (bench.py; not part of the reference surface) -- */
 /* Per-kernel HIP-event timing on the table's stream.  which: 0 count (direct), 1 add_keys,

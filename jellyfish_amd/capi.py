@@ -13,7 +13,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JFGPU_LIB") or os.path.join(_HERE, "lib", "libjfgpu.so")   # JFGPU_LIB: experimental builds (tools/)
 
-OK, E_INVALID, E_NO_DEVICE, E_ALLOC, E_FULL, E_HIP, E_UNSUPPORTED, E_FORMAT = range(8)
+OK, E_INVALID, E_NO_DEVICE, E_ALLOC, E_FULL, E_HIP, E_UNSUPPORTED, E_FORMAT, E_CORRUPT = range(9)
 PARSE_FASTA, PARSE_FASTQ, PARSE_CONTINUE = 1, 2, 4
 
 
@@ -123,6 +123,12 @@ SIGNATURES = {
     "jfgpu_parser_host_buffer": (C.c_int, [_P, C.c_int, C.c_size_t, C.POINTER(_P)]),
     "jfgpu_parser_set_min_quality": (C.c_int, [_P, C.c_int]),
     "jfgpu_parser_last_ms": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "jfgpu_bgzf_scan": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "jfgpu_parser_inflate_uploaded": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "jfgpu_parser_stream_read": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P]),
+    "jfgpu_parser_stream_consume": (C.c_int, [_P, C.c_size_t]),
+    "jfgpu_parser_bam_decode": (C.c_int, [_P, C.c_size_t, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_size_t)]),
     "jfgpu_set_growth": (C.c_int, [_P, C.c_int]),
     "jfgpu_reference_matrix": (C.c_int, [C.c_uint32, C.c_uint32, _P]),
     "jfgpu_table_bytes": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -699,3 +705,50 @@ class Parser:
         ms = C.c_double()
         _check(self._lib.jfgpu_parser_last_ms(self._h, C.byref(ms)))
         return ms.value
+
+    def inflate(self, data: bytes, which=0):
+        """Whole BGZF members (host bytes) -> appended to the inflated stream on the device; returns its length."""
+        blocks, used = bgzf_scan(data)
+        _check(self._lib.jfgpu_parser_upload(self._h, which, data, used))
+        _check(self._lib.jfgpu_parser_upload_wait(self._h, which))
+        n = C.c_size_t()
+        _check(self._lib.jfgpu_parser_inflate_uploaded(self._h, which, blocks, len(blocks), C.byref(n)))
+        return n.value
+
+    def inflate_table(self, data: bytes, blocks, which=0):
+        """The same with a block table given by the caller (a BgzfBlock array)."""
+        _check(self._lib.jfgpu_parser_upload(self._h, which, data, len(data)))
+        _check(self._lib.jfgpu_parser_upload_wait(self._h, which))
+        n = C.c_size_t()
+        _check(self._lib.jfgpu_parser_inflate_uploaded(self._h, which, blocks, len(blocks), C.byref(n)))
+        return n.value
+
+    def stream_read(self, offset, n):
+        buf = C.create_string_buffer(max(1, n))
+        _check(self._lib.jfgpu_parser_stream_read(self._h, offset, n, buf))
+        return buf.raw[:n]
+
+    def stream_consume(self, n):
+        _check(self._lib.jfgpu_parser_stream_consume(self._h, n))
+
+    def bam_decode(self, skip, n_ref):
+        """-> (device pointer, length) of the contract buffer, records, bytes left in the stream."""
+        out, n_out, recs, left = _P(), C.c_size_t(), C.c_uint64(), C.c_size_t()
+        _check(self._lib.jfgpu_parser_bam_decode(self._h, skip, n_ref, C.byref(out), C.byref(n_out), C.byref(recs), C.byref(left)))
+        self.records = recs.value
+        return (out.value or 0), n_out.value, recs.value, left.value
+
+
+class BgzfBlock(C.Structure):
+    _fields_ = [("c_off", C.c_uint64), ("u_off", C.c_uint64), ("c_len", C.c_uint32), ("isize", C.c_uint32),
+                ("crc32", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def bgzf_scan(data: bytes):
+    """Block table of the whole BGZF members at the start of data (host only) -> (BgzfBlock array, bytes used)."""
+    lib = load()
+    cap = len(data) // 26 + 1
+    arr = (BgzfBlock * cap)()
+    nb, used = C.c_size_t(), C.c_size_t()
+    _check(lib.jfgpu_bgzf_scan(data, len(data), arr, cap, C.byref(nb), C.byref(used)))
+    return (BgzfBlock * nb.value).from_buffer_copy(arr, 0) if nb.value else (BgzfBlock * 0)(), used.value

@@ -31,6 +31,7 @@
 #include <sys/wait.h>
 #include <jellyfish_amd/sequence_parser.hpp>
 #include <jellyfish_amd/device_parser.hpp>
+#include <jellyfish_amd/sam_parser.hpp>
 
 using namespace jellyfish_amd;
 
@@ -365,7 +366,7 @@ int count_main(int argc, char* argv[]) {
   bool min_qual_char_given = false, min_quality_given = false;
   uint32_t matrix_kind = JFGPU_MATRIX_DEFAULT;
   std::string output = "mer_counts.jf", timing, bc_path, generator, shell, digest_path;
-  std::vector<std::string> files, if_files;
+  std::vector<std::string> files, if_files, sam_files;
   ArgCursor a{argc, argv};
   for(; a.more(); ++a.i) {
     if(a.is("-m", "--mer-len")) mer_len = (unsigned)strtoul(a.value("-m", "--mer-len").c_str(), 0, 10);
@@ -410,8 +411,7 @@ int count_main(int argc, char* argv[]) {
     else if(a.is("", "--min-quality")) { min_quality = atoi(a.value("", "--min-quality").c_str()); min_quality_given = true; }
     else if(a.is("", "--bf-size")) { bf_size = parse_suffix(a.value("", "--bf-size"), "--bf-size"); bf_size_given = true; }
     else if(a.is("", "--bf-fp")) bf_fp = atof(a.value("", "--bf-fp").c_str());
-    else if(a.is("", "--sam"))
-      die("SAM/BAM/CRAM not supported (missing htslib).");
+    else if(a.is("", "--sam")) sam_files.push_back(a.value("", "--sam"));   // BAM / SAM, read after the files and -g (stream_manager.hpp:132-180)
     else if(a.cur() == "-h" || a.cur() == "--help") {
       std::cout << "Usage: jellyfish-amd count [options] file:path+\n\n"
                    "Count k-mers in fasta or fastq files on an MI355X\n\n"
@@ -428,6 +428,8 @@ int count_main(int argc, char* argv[]) {
                    "     --if=path               Count only the k-mers of these fasta / fastq files (repeatable)\n"
                    " -g, --generator=path        File of commands generating fast[aq] (one per line, e.g. zcat reads.fa.gz)\n"
                    " -S, --shell=string          Shell used to run generator commands ($SHELL or /bin/sh)\n"
+                   "     --sam=PATH              SAM/BAM file to count (repeatable; BAM is inflated and decoded on the device;\n"
+                   "                             every record counts; CRAM and plain gzip are not read; --host-parse does not apply)\n"
                    "     --text                  Dump in text format (false)\n"
                    "     --timing=Timing file    Print timing information\n"
                    "     --device=int            HIP device ordinal (current)\n"
@@ -441,7 +443,7 @@ int count_main(int argc, char* argv[]) {
   }
   if(!mer_len) die("Error: mandatory switch missing: -m, --mer-len");
   if(!size_given) die("Error: mandatory switch missing: -s, --size");
-  if(files.empty() && generator.empty()) die("Error: at least 1 file argument is required");
+  if(files.empty() && generator.empty() && sam_files.empty()) die("Error: at least 1 file argument is required");
   if(bf_size_given && !bc_path.empty()) die("Switches --bf-size and --bc conflict");
   if(min_quality_given) {                                   // count_main.cc:245-256
     if(min_qual_char_given) die("Switches --min-quality and -Q, --min-qual-char conflict");
@@ -545,14 +547,29 @@ int count_main(int argc, char* argv[]) {
   // starts): the device workspace for the whole input (file sizes are an upper bound of the sequence) and the feed's
   // pinned staging buffers.  Tens of GB of fresh device memory cost seconds to hand out, whoever asks first.
   std::unique_ptr<device_sequence_parser> dev_parser;
+  std::unique_ptr<sam_parser> sam_feed;
   {
     uint64_t total = 0, largest = 0;
     for(const auto& f : files) { struct stat st; if(stat(f.c_str(), &st) == 0 && S_ISREG(st.st_mode)) { total += (uint64_t)st.st_size; largest = std::max<uint64_t>(largest, st.st_size); } }
     if(gpus_given) { total = total / gpus + ((uint64_t)1 << 20); largest = largest / gpus + ((uint64_t)1 << 20); }   // this rank's part
-    if(!host_parse && total > ((uint64_t)64 << 20)) ary->expect_input(std::min<uint64_t>(total, (uint64_t)12 << 30));
+    // SAM / BAM files: whole files per rank (file i to rank i mod N); their sequence is taken as up to twice the
+    // compressed size (a BAM record's bases are a third of it, BGZF compresses it 2 - 4 times)
+    uint64_t sam_total = 0, sam_largest = 0;
+    for(size_t i = 0; i < sam_files.size(); ++i) {
+      struct stat st;
+      if((!gpus_given || i % gpus == (size_t)renv.rank) && stat(sam_files[i].c_str(), &st) == 0 && S_ISREG(st.st_mode)) {
+        sam_total += (uint64_t)st.st_size; sam_largest = std::max<uint64_t>(sam_largest, st.st_size);
+      }
+    }
+    const uint64_t expected = std::max<uint64_t>(host_parse ? 0 : total, 2 * sam_total);
+    if(expected > ((uint64_t)64 << 20)) ary->expect_input(std::min<uint64_t>(expected, (uint64_t)12 << 30));
     init_mark("partition workspace reserved");
     if(!host_parse) {
       try { dev_parser.reset(new device_sequence_parser(mer_len, device)); dev_parser->min_quality(min_qual); dev_parser->prepare(largest); }
+      catch(std::exception& e) { die(e.what()); }
+    }
+    if(!sam_files.empty()) {
+      try { sam_feed.reset(new sam_parser(mer_len, device)); sam_feed->min_quality(min_qual); sam_feed->prepare(sam_largest); }
       catch(std::exception& e) { die(e.what()); }
     }
   }
@@ -593,6 +610,17 @@ int count_main(int argc, char* argv[]) {
     if(!generator.empty()) {
       feed_generators(generator, shell, mer_len, [&](const char* buf, size_t n) { ary->count_sequence(buf, n); },
                       gpus_given ? (unsigned)renv.rank : 0u, gpus_given ? gpus : 1u);
+      ary->done();
+    }
+    if(!sam_files.empty()) {
+      // SAM / BAM streams come after the files and the generators (stream_manager.hpp:132-180).  Always the device
+      // path (--host-parse is about FASTA / FASTQ); with --gpus N file i is read by rank i mod N -- a BAM is not cut.
+      sam_parser& sp = *sam_feed;
+      for(size_t i = 0; i < sam_files.size(); ++i)
+        if(!gpus_given || i % gpus == (size_t)renv.rank)
+          sp.parse_file(sam_files[i].c_str(), [&](const char* d_buf, size_t n) { ary->count_sequence_dev(d_buf, n); },
+                        [&](const char* buf, size_t n) { ary->count_sequence(buf, n); }, [&]() { ary->wait_consumed(); });
+      parse_ms += sp.device_ms();
       ary->done();
     }
   } catch(std::exception& e) { die(e.what()); }

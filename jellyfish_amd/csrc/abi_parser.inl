@@ -1,5 +1,7 @@
 // jellyfish_amd/csrc/abi_parser.inl -- C ABI of the device-side sequence parser (jfgpu_parser_*), included by jfgpu.hip.
 // ---- device-side FASTA / FASTQ parse (kernels_parse.hip.hpp) ----------------------------------------
+struct BgzfState;                                          // BGZF / BAM work buffers (abi_sam.inl)
+static void bgzf_state_free(BgzfState* b);
 struct jfgpu_parser {
   int device = 0;
   uint32_t k = 0;
@@ -18,6 +20,7 @@ struct jfgpu_parser {
   char* h_pin[2] = {nullptr, nullptr}; size_t pin_cap[2] = {0, 0};   // pinned host staging for callers that read files
   double last_ms = 0;
   uint32_t min_qual = 0;                                   // > 0: FASTQ bases with a lower quality character become 'N'
+  BgzfState* bgzf = nullptr;                               // created by the first jfgpu_parser_inflate_uploaded
 };
 
 namespace {
@@ -66,6 +69,7 @@ void jfgpu_parser_destroy(jfgpu_parser* p) {
   if(p->stream) hipStreamSynchronize(p->stream);
   hipFree(p->d_raw); hipFree(p->d_out[0]); hipFree(p->d_out[1]); hipFree(p->d_agg); hipFree(p->d_start);
   hipFree(p->d_nlpos); hipFree(p->d_res); hipFree(p->d_carry);
+  bgzf_state_free(p->bgzf);
   if(p->copy_stream) { hipStreamSynchronize(p->copy_stream); hipStreamDestroy(p->copy_stream); }
   for(int i = 0; i < 2; ++i) { if(p->d_up[i]) hipFree(p->d_up[i]); if(p->up_done[i]) hipEventDestroy(p->up_done[i]); }
   for(int i = 0; i < 2; ++i) if(p->h_pin[i]) hipHostFree(p->h_pin[i]);

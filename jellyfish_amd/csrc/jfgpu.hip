@@ -27,6 +27,7 @@
 #include "kernels_wide_part.hip.hpp"
 #include "kernels_nword.hip.hpp"
 #include "kernels_parse.hip.hpp"
+#include "kernels_bgzf.hip.hpp"
 
 using namespace jfgpu;
 
@@ -1453,4 +1454,5 @@ int jfgpu_memcpy_d2h(jfgpu_table* t, void* dst, const void* d_src, size_t bytes)
 
 #include "abi_bloom.inl"
 #include "abi_parser.inl"
+#include "abi_sam.inl"
 #include "abi_comm.inl"

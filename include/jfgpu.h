@@ -41,7 +41,7 @@ enum {
   JFGPU_E_ALLOC = 3,      /* large_hash::array::ErrorAllocation, large_hash_array.hpp:55,169-172 */
   JFGPU_E_FULL = 4,       /* std::runtime_error("Hash full"), hash_counter.hpp:194-195 */
   JFGPU_E_HIP = 5,        /* HIP runtime error */
-  JFGPU_E_UNSUPPORTED = 6,/* combination not built (e.g. k > 128, a sharded table for k > 64, --bc / --if over shards of two-word keys) */
+  JFGPU_E_UNSUPPORTED = 6,/* combination not built (e.g. k > 128, a Bloom counter for k > 64, a one-pass filter over shards) */
   JFGPU_E_FORMAT = 7,     /* device parser: chunk is not in the strict layout it handles; give it to the host parser */
   JFGPU_E_CORRUPT = 8     /* compressed input (BGZF / BAM) is malformed or fails its CRC32 / ISIZE check: there is no
                              host path for it, the input is bad (htslib's "bgzf_read" / "truncated file" errors) */
@@ -60,7 +60,8 @@ typedef struct jfgpu_params {
                             two, capped at 4^k, raised to the engine minimum for large k) */
   int32_t  device;       /* HIP device ordinal, -1 = current device */
   uint32_t shard_bits;   /* log2(number of shards).  Shard s owns global positions whose top
-                            shard_bits bits equal s; 0 = single GPU */
+                            shard_bits bits equal s; 0 = single GPU.  Any k (1..128);
+                            for k > 32 a shard holds at least one tile of slots */
   uint32_t shard_id;     /* which shard this table is */
   uint64_t matrix_seed;  /* seed of the random GF(2) hash matrix; 0 = engine default.
                             All shards of one job must use the same seed */

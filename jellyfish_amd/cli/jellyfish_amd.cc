@@ -433,7 +433,8 @@ int count_main(int argc, char* argv[]) {
                    "     --text                  Dump in text format (false)\n"
                    "     --timing=Timing file    Print timing information\n"
                    "     --device=int            HIP device ordinal (current)\n"
-                   "     --gpus=N                Spread the table over N GPUs (a power of two), one process each\n"
+                   "     --gpus=N                Spread the table over N GPUs (a power of two), one process each; any mer\n"
+                   "                             length (--bc / --bf-size: mer length <= 64; not with --disk)\n"
                    "     --host-parse            Parse the sequence files on the host (default: on the device)\n"
                    "     --matrix=xs|reference   Hash matrix family: xs = evaluated in registers by the GPU kernels (fastest);\n"
                    "                             reference = the matrix jellyfish itself draws (byte-identical files; default)\n";
@@ -469,11 +470,12 @@ int count_main(int argc, char* argv[]) {
   uint32_t shard_bits = 0;
   if(gpus_given) {
     if(gpus < 1 || (gpus & (gpus - 1)) || gpus > 256) die("--gpus must be a power of two");
-    if(mer_len > 64) die("--gpus: sharded tables for mer length > 64 are not built yet");
+    if(mer_len > 64 && (bf_size_given || !bc_path.empty()))
+      die("--gpus: --bc and --bf-size are not built for mer length " + std::to_string(mer_len) + " (Bloom counters hold keys of at most 64 bases)");
     if(bf_size_given || disk)
       die("--gpus cannot be combined with --bf-size (a one-pass filter cannot be sharded by input) or --disk yet");
-    // (--if and --bc over shards: keys of one and two words -- every rank loads the whole counter and asks it before routing;
-    //  mer length > 64 has no shards at all: refused above)
+    // (--if and --bc over shards: every rank loads the whole counter and asks it before routing -- --bc for keys of one and
+    //  two words only, refused above for longer ones)
     renv = read_rank_env();
     if(!renv.is_rank) return spawn_ranks(gpus, argv);
     if(renv.world != (int)gpus || renv.rank < 0 || renv.rank >= renv.world) die("--gpus does not match the ranks' environment (WORLD_SIZE / RANK)");

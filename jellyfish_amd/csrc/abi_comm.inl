@@ -213,7 +213,6 @@ __global__ __launch_bounds__(1024) void comm_claims_kernel(const unsigned long l
 // A Bloom counter attached to a shard (count --bc) is asked on the SENDING side, every rank holding the whole read-only
 // counter.  A one-pass filter (--bf-size) changes as it is asked and would see only its rank's reads; two-word keys: not built.
 int comm_filter_ok(const jfgpu_table* t) {
-  if(t->operation != 0 && t->nword) return fail(JFGPU_E_UNSUPPORTED, "count --if with --gpus: keys longer than two words are not built yet");
   if(t->wide && t->wt.bloom.data && t->wt.bloom.kind != 0) return fail(JFGPU_E_UNSUPPORTED, "--bf-size with --gpus: a one-pass filter cannot be sharded by input");
   if(!t->wide && t->dt.bloom.data && t->dt.bloom.kind != 0) return fail(JFGPU_E_UNSUPPORTED, "--bf-size with --gpus: a one-pass filter cannot be sharded by input");
   return JFGPU_OK;
@@ -454,9 +453,8 @@ int comm_route(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_bases, size_t n
   jfgpu_table* t = R.t;
   const int cur = R.turn, W = c->world;
   if((int)(1u << t->g.shard_bits) != W) return fail(JFGPU_E_INVALID, "table shard_bits does not match the communicator's world size");
-  if(t->nword) return fail(JFGPU_E_UNSUPPORTED, "sharded tables with mer length > 64 are not built yet");
   { const int rc_ = comm_filter_ok(t); if(rc_) return rc_; }
-  const uint64_t kw = t->wide ? 2 : 1;                                   // 64-bit words per routed k-mer (counts and offsets below are in words)
+  const uint64_t kw = t->key_words;                                      // 64-bit words per routed k-mer (counts and offsets below are in words)
   if(R.used[cur]) HIP_TRY(hipEventSynchronize(R.exchanged[cur]));       // send[cur] has left (step - 2)
   std::fill(R.scount[cur].begin(), R.scount[cur].end(), 0);
   std::fill(R.soff[cur].begin(), R.soff[cur].end(), 0);
@@ -470,7 +468,8 @@ int comm_route(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_bases, size_t n
   HIP_TRY(hipMemsetAsync(R.d_cnt, 0, sizeof(unsigned long long) * W, t->stream));
   {
     ProfScope ps(t, 2, n);
-    if(t->wide && t->wt.bloom.data) hipLaunchKernelGGL(partition_count_wide_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, R.d_cnt);
+    if(t->nword) hipLaunchKernelGGL(partition_count_nword_kernel, dim3(grid), dim3(kBlock), nword_route_lds(t->g.nbytes), t->stream, t->nt, base, lo, hi, R.d_cnt);
+    else if(t->wide && t->wt.bloom.data) hipLaunchKernelGGL(partition_count_wide_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, R.d_cnt);
     else if(t->wide) hipLaunchKernelGGL(partition_count_wide_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, R.d_cnt);
     else if(t->dt.bloom.data) hipLaunchKernelGGL(partition_count_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, R.d_cnt);
     else hipLaunchKernelGGL(partition_count_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, R.d_cnt);
@@ -484,7 +483,8 @@ int comm_route(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_bases, size_t n
   HIP_TRY(hipMemcpyAsync(R.d_cnt, h.data(), sizeof(unsigned long long) * W, hipMemcpyHostToDevice, t->stream));   // cursors = offsets
   {
     ProfScope ps(t, 2, 0);
-    if(t->wide && t->wt.bloom.data) hipLaunchKernelGGL(partition_scatter_wide_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, R.d_cnt, R.send[cur]);
+    if(t->nword) hipLaunchKernelGGL(partition_scatter_nword_kernel, dim3(grid), dim3(kBlock), nword_route_lds(t->g.nbytes), t->stream, t->nt, base, lo, hi, R.d_cnt, R.send[cur], t->key_words);
+    else if(t->wide && t->wt.bloom.data) hipLaunchKernelGGL(partition_scatter_wide_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, R.d_cnt, R.send[cur]);
     else if(t->wide) hipLaunchKernelGGL(partition_scatter_wide_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, R.d_cnt, R.send[cur]);
     else if(t->dt.bloom.data) hipLaunchKernelGGL(partition_scatter_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, R.d_cnt, R.send[cur]);
     else hipLaunchKernelGGL(partition_scatter_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, R.d_cnt, R.send[cur]);
@@ -503,14 +503,15 @@ int comm_insert_prev(jfgpu_comm* c, jfgpu_comm::Rank& R) {
   if(R.icap[prev]) return comm_insert_prev_items(c, R, c->local ? (int)(&R - c->ranks.data()) : c->rank);
   jfgpu_table* t = R.t;
   HIP_TRY(hipStreamWaitEvent(t->stream, R.exchanged[prev], 0));
-  const uint64_t n = R.roff[prev][c->world] / (t->wide ? 2 : 1);          // k-mers that arrived (the offsets are in words)
+  const uint64_t n = R.roff[prev][c->world] / t->key_words;               // k-mers that arrived (the offsets are in words)
   int rc = JFGPU_OK;
   // what the table does with a k-mer (jfgpu_set_operation: the passes of count --if) holds for what arrives, too
   if(n && t->operation == 2) {
     rc = part_flush(t); if(rc) return rc;
     ProfScope ps(t, 1, n);
     const int grid = grid_for(t, (n + kBlock - 1) / kBlock);
-    if(t->wide) {
+    if(t->nword) hipLaunchKernelGGL(update_keys_nword_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->nt, (const uint64_t*)R.recv[prev], (uint64_t)n, t->key_words);
+    else if(t->wide) {
       if(t->returning) hipLaunchKernelGGL(update_keys_wide_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, (const uint64_t*)R.recv[prev], (uint64_t)n);
       else             hipLaunchKernelGGL(update_keys_wide_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, (const uint64_t*)R.recv[prev], (uint64_t)n);
     }
@@ -1007,6 +1008,30 @@ __global__ __launch_bounds__(kBlock) void add_pairs_wide_kernel(WideTable T, con
     wide_add_val(T, T.fwd_tbl, ((u128)keys[2 * i + 1] << 64) | keys[2 * i], cnts[i]);
 }
 
+// The same for keys of three and four words: a pair is kw key words (low first) and a count.
+__global__ __launch_bounds__(kBlock) void reshard_nword_kernel(NTable old, NTable neu, int have_ovf, int pass, uint32_t kw, unsigned long long* __restrict__ cursors,
+                                                               uint64_t* __restrict__ keys_out, uint64_t* __restrict__ cnts_out) {
+  const TableGeom& g = old.N.g;
+  const DevTable od = ovf_view(old);
+  const uint64_t n = 1ull << g.lsize_l;
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t* sp = &old.slots[4 * i];
+    if(!nword_complete(sp)) continue;                    // (a claim that was never completed holds no key)
+    const K256 key = nword_slot_key(old, old.inv_tbl, sp, i & ~g.tile_mask);
+    const uint64_t cnt = nword_count_at(old, od, i, sp[3], have_ovf);
+    const uint32_t owner = slot_addr(neu.N.g, hash_tables_n256(neu.fwd_tbl, key, neu.N.g.nbytes)).shard;
+    if(owner == neu.N.g.shard_id) { if(pass) nword_add_val(neu, key, cnt); }
+    else {
+      const unsigned long long at = atomicAdd(&cursors[owner], 1ull);
+      if(pass) { for(uint32_t q = 0; q < kw; ++q) keys_out[(uint64_t)kw * at + q] = key.w[q]; cnts_out[at] = cnt; }
+    }
+  }
+}
+__global__ __launch_bounds__(kBlock) void add_pairs_nword_kernel(NTable T, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ cnts, uint64_t n, uint32_t kw) {
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    nword_add_val(T, load_key4(keys, i, kw, T.N.key_mask), cnts[i]);
+}
+
 int comm_exchange_rccl(jfgpu_comm* c); int comm_exchange_local(jfgpu_comm* c); int comm_exchange_ipc(jfgpu_comm* c);
 
 // Collective (every rank of the communicator; the local transport: all its ranks here).
@@ -1020,7 +1045,6 @@ int comm_grow(jfgpu_comm* c) {
   for(size_t q = 0; q < c->ranks.size() && !hard; ++q) {
     jfgpu_comm::Rank& R = c->ranks[q];
     jfgpu_table* t = R.t;
-    if(t->nword) return fail(JFGPU_E_UNSUPPORTED, "sharded tables of keys longer than two words are not built");      // (the same on every rank)
     int rc = comm_insert_prev(c, R);
     if(rc == 0) rc = grow_prepare(t, N[q]);
     if(rc > 0) { hard = rc; hard_msg = g_err; break; }
@@ -1054,13 +1078,14 @@ int comm_grow(jfgpu_comm* c) {
   for(size_t q = 0; q < c->ranks.size(); ++q) {
     jfgpu_comm::Rank& R = c->ranks[q];
     jfgpu_table* t = R.t;
-    const uint64_t kw = t->wide ? 2 : 1;                   // 64-bit words per key
+    const uint64_t kw = t->key_words;                      // 64-bit words per key
     int rc = 0;
     HIP_TRY(hipStreamSynchronize(c->xstream));
     const int have_ovf = (int)(N[q].ctr[CTR_OVF_USED] != 0);
     const dim3 grid(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), block(kBlock);
     HIP_TRY(hipMemsetAsync(R.d_cnt, 0, sizeof(unsigned long long) * W, t->stream));
-    if(t->wide) hipLaunchKernelGGL(reshard_wide_kernel, grid, block, 0, t->stream, t->wt, N[q].nw, have_ovf, 0, R.d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
+    if(t->nword) hipLaunchKernelGGL(reshard_nword_kernel, grid, block, 0, t->stream, t->nt, N[q].nn, have_ovf, 0, (uint32_t)kw, R.d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
+    else if(t->wide) hipLaunchKernelGGL(reshard_wide_kernel, grid, block, 0, t->stream, t->wt, N[q].nw, have_ovf, 0, R.d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
     else hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, t->dt, N[q].nd, have_ovf, 0, R.d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
     std::vector<unsigned long long> h(W);
     HIP_TRY(hipMemcpyAsync(h.data(), R.d_cnt, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost, t->stream));
@@ -1077,7 +1102,8 @@ int comm_grow(jfgpu_comm* c) {
     rc = comm_reserve_send(c, R, 0, std::max<uint64_t>(total * kw, 1), t->stream); if(rc) return rc;
     rc = comm_reserve_send(c, R, 1, std::max<uint64_t>(total, 1), t->stream); if(rc) return rc;
     HIP_TRY(hipMemcpyAsync(R.d_cnt, h.data(), sizeof(unsigned long long) * W, hipMemcpyHostToDevice, t->stream));   // cursors = offsets
-    if(t->wide) hipLaunchKernelGGL(reshard_wide_kernel, grid, block, 0, t->stream, t->wt, N[q].nw, have_ovf, 1, R.d_cnt, R.send[0], R.send[1]);
+    if(t->nword) hipLaunchKernelGGL(reshard_nword_kernel, grid, block, 0, t->stream, t->nt, N[q].nn, have_ovf, 1, (uint32_t)kw, R.d_cnt, R.send[0], R.send[1]);
+    else if(t->wide) hipLaunchKernelGGL(reshard_wide_kernel, grid, block, 0, t->stream, t->wt, N[q].nw, have_ovf, 1, R.d_cnt, R.send[0], R.send[1]);
     else hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, t->dt, N[q].nd, have_ovf, 1, R.d_cnt, R.send[0], R.send[1]);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(t->stream));
@@ -1096,7 +1122,7 @@ int comm_grow(jfgpu_comm* c) {
     HIP_TRY(hipStreamWaitEvent(t->stream, R.exchanged[0], 0));
     HIP_TRY(hipStreamWaitEvent(t->stream, R.exchanged[1], 0));
     const uint64_t n = R.roff[1][W];                        // pairs that arrived (turn 1's offsets count them; turn 0's count key words)
-    if(c->tun.comm_trace && !t->wide) {                     // where do the arrivals belong under the new matrix?  (host check, trace runs only)
+    if(c->tun.comm_trace && t->key_words == 1) {                     // where do the arrivals belong under the new matrix?  (host check, trace runs only)
       HIP_TRY(hipStreamSynchronize(c->xstream));
       std::vector<uint64_t> hk(n);
       if(n) HIP_TRY(hipMemcpy(hk.data(), R.recv[0], n * 8, hipMemcpyDeviceToHost));
@@ -1112,7 +1138,8 @@ int comm_grow(jfgpu_comm* c) {
       }
       IPC_TRACE(c, "grow: shard %u, arrived/not mine per sender:%s", t->g.shard_id, hs.c_str());
     }
-    if(n && t->wide) hipLaunchKernelGGL(add_pairs_wide_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, N[q].nw, (const uint64_t*)R.recv[0], (const uint64_t*)R.recv[1], n);
+    if(n && t->nword) hipLaunchKernelGGL(add_pairs_nword_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, N[q].nn, (const uint64_t*)R.recv[0], (const uint64_t*)R.recv[1], n, t->key_words);
+    else if(n && t->wide) hipLaunchKernelGGL(add_pairs_wide_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, N[q].nw, (const uint64_t*)R.recv[0], (const uint64_t*)R.recv[1], n);
     else if(n) hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, N[q].nd, (const uint64_t*)R.recv[0], (const uint64_t*)R.recv[1], n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(R.consumed[0], t->stream));
@@ -1270,7 +1297,7 @@ extern "C" int jfgpu_comm_allreduce_u64(jfgpu_comm* c, uint64_t* values, int n, 
 // since: k-mers <= bytes, and a hash prefix gets its even share of them), input is fed in pieces that fit the head-room the
 // ranks have between them (the smallest), and when a rank's head-room runs out every rank measures its shard; if one is
 // more than half full, all of them double together (comm_grow).
-bool comm_growing(const jfgpu_table* t) { return t->grow_on && !t->nword && t->g.lsize_g < t->g.key_bits; }
+bool comm_growing(const jfgpu_table* t) { return t->grow_on && t->g.lsize_g < t->g.key_bits; }
 uint64_t comm_headroom(const jfgpu_table* t) {
   const uint64_t limit = capacity_limit(t), used = t->occ_known + t->fed_since;
   return limit > used ? limit - used : 0;
@@ -1281,6 +1308,14 @@ uint64_t comm_headroom(const jfgpu_table* t) {
 uint64_t comm_charge(uint64_t piece) { return piece + piece / 16 + 4 * (uint64_t)std::sqrt((double)piece); }
 // head-room too small for a useful piece of `left` bytes: time to measure
 bool comm_bound_out(const jfgpu_table* t, uint64_t left) { return comm_headroom(t) < std::min<uint64_t>(left, std::max<uint64_t>(capacity_limit(t) / 8, 1)); }
+// Keys of three and four words: the largest piece of a step in input bytes, so that its send buffer (at most one k-mer per
+// byte, key_words words each) stays under the byte budget (tuning.hpp: kCommNWordPieceBytes, JFGPU_COMM_PIECE_BYTES);
+// at least 2k, so that a piece holds a window and moves forward.  0: not cut (keys of one and two words).
+uint64_t comm_piece_cap(const jfgpu_comm* c, const jfgpu_table* t) {
+  if(t->key_words < 3) return 0;
+  const uint64_t budget = c->tun.comm_piece_bytes ? c->tun.comm_piece_bytes : kCommNWordPieceBytes;
+  return std::max<uint64_t>(budget / (8ull * t->key_words), 2ull * t->g.k);
+}
 
 // One piece of this rank's step through routing, exchange and the insert of the previous piece (cap: the agreed region
 // capacity of the item path, 0: keys).
@@ -1307,7 +1342,7 @@ int comm_piece_rccl(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_bases, siz
     // (the one-box test transport: importing a peer's send buffer of 10 GB never returned -- bench.py --gpus 2 --steps 4 on one
     //  device, a 1.26 GB step as keys; 5 GB buffers are fine -- so such a step fails here, loudly and on every rank, instead
     //  of standing in a barrier for ten minutes)
-    if(c->ipc && (uint64_t)n * (t->wide ? 16 : 8) > ((uint64_t)6 << 30))
+    if(c->ipc && (uint64_t)n * t->key_words * 8 > ((uint64_t)6 << 30))
       return ipc_fail(c, "a step of this size travels as keys in send buffers of more than 6 GiB, which this runtime does not import: feed smaller steps");
 #endif
     rc = comm_route(c, R, d_bases, n); if(rc) return rc;
@@ -1410,6 +1445,7 @@ int jfgpu_comm_count_ascii_dev(jfgpu_comm* c, jfgpu_table* t, const char* d_base
   jfgpu_comm::Rank& R = c->ranks[0];
   R.t = t;
   const uint64_t k = t->g.k;
+  const uint64_t piece_cap = comm_piece_cap(c, t);          // (keys of three and four words: a step goes in pieces of at most this)
   size_t off = 0;
   for(bool first = true;; first = false) {
     const size_t left = n - off;
@@ -1435,7 +1471,7 @@ int jfgpu_comm_count_ascii_dev(jfgpu_comm* c, jfgpu_table* t, const char* d_base
       first = true;                                          // (the agreement is taken again: new head-room, maybe a new geometry)
       continue;
     }
-    const uint64_t agreed = ~0ull - v[4];                    // the smallest head-room
+    const uint64_t agreed = piece_cap ? std::min<uint64_t>(~0ull - v[4], piece_cap) : ~0ull - v[4];     // the smallest head-room (and the cap)
     size_t piece = (size_t)std::min<uint64_t>(left, agreed);
     if(piece < left && piece < 2 * k) piece = (size_t)std::min<uint64_t>(left, 2 * k);      // (a piece holds a window and moves forward)
     const uint32_t cap = v[0] ? 0u : (uint32_t)v[1];
@@ -1443,7 +1479,7 @@ int jfgpu_comm_count_ascii_dev(jfgpu_comm* c, jfgpu_table* t, const char* d_base
     rc = comm_piece_rccl(c, R, d_bases + off, piece, cap); if(rc) return rc;
     if(growing) t->fed_since += comm_charge(std::min<uint64_t>(v[2], std::max<uint64_t>(agreed, 2 * k)));
     if(off + piece >= n) off = n; else off += piece - (size_t)(k - 1);      // the next piece re-reads the last k-1 characters: every window exactly once
-    if(!growing) break;                                      // (no pieces without growth: the step is one exchange, as the caller counts them)
+    if(!growing && !piece_cap) break;                        // (no pieces without growth or a cap: the step is one exchange, as the caller counts them)
   }
   IPC_TRACE(c, "step: done");
   return JFGPU_OK;
@@ -1462,6 +1498,7 @@ int jfgpu_comm_local_step(jfgpu_comm* c, jfgpu_table** tables, const char* const
     growing = growing && comm_growing(tables[r]);
   }
   const uint64_t k = tables[0]->g.k;
+  const uint64_t piece_cap = comm_piece_cap(c, tables[0]);    // (the cut of jfgpu_comm_count_ascii_dev)
   std::vector<size_t> off(W, 0), piece(W, 0);
   std::vector<const char*> at(W);
   for(bool first = true;; first = false) {
@@ -1491,7 +1528,7 @@ int jfgpu_comm_local_step(jfgpu_comm* c, jfgpu_table** tables, const char* const
     uint32_t cap = 0xFFFFFFFFu, want_max = 0;
     for(int r = 0; r < W; ++r) {
       const uint64_t left = n[r] - off[r];
-      piece[r] = (size_t)std::min<uint64_t>(left, head);
+      piece[r] = (size_t)std::min<uint64_t>(left, piece_cap ? std::min<uint64_t>(head, piece_cap) : head);
       if(piece[r] < left && piece[r] < 2 * k) piece[r] = (size_t)std::min<uint64_t>(left, 2 * k);
       at[r] = d_bases[r] + off[r];
       const uint32_t w = items_cap_wanted(c, c->ranks[r], piece[r]);
@@ -1529,7 +1566,7 @@ int jfgpu_comm_local_step(jfgpu_comm* c, jfgpu_table** tables, const char* const
       if(off[r] + piece[r] >= n[r]) off[r] = n[r]; else off[r] += piece[r] - (size_t)(k - 1);
     }
     if(growing) for(int r = 0; r < W; ++r) tables[r]->fed_since += comm_charge(max_piece);
-    if(!growing) break;
+    if(!growing && !piece_cap) break;
   }
   return JFGPU_OK;
 }

@@ -476,7 +476,7 @@ int grow_prepare(jfgpu_table* t, GrowNew& N) {
     }
   }
   TableGeom& g2 = N.g2;
-  if(t->nword) { if(!nword_geom_init(N.ng2, t->g.k, r + 1, t->g.canonical)) return -1; g2 = N.ng2.g; }
+  if(t->nword) { if(!nword_geom_init(N.ng2, t->g.k, r + 1, t->g.canonical, t->g.shard_bits, t->g.shard_id)) return -1; g2 = N.ng2.g; }
   else if(t->wide) { if(!wide_geom_init(N.w2, t->g.k, r + 1, t->g.canonical, t->g.shard_bits, t->g.shard_id)) return -1; g2 = N.w2.g; }
   else if(!geom_init(g2, t->g.k, r + 1, t->g.shard_bits, t->g.shard_id, t->g.canonical, !t->tun.slot64)) return -1;
   if(!t->nword) { g2.hash_xs = gf2_is_xorshift(m2) ? 1 : 0; if(t->wide) N.w2.g.hash_xs = g2.hash_xs; }
@@ -590,7 +590,6 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
   *out = nullptr;
   if(p->k < 1) return fail(JFGPU_E_INVALID, "mer length must be >= 1");
   if(p->k > 128) return fail(JFGPU_E_UNSUPPORTED, "mer length > 128 (more than four key words) is not built");
-  if(p->k > 64 && p->shard_bits) return fail(JFGPU_E_UNSUPPORTED, "sharded tables with mer length > 64 are not built yet");
   if(p->shard_bits > 8) return fail(JFGPU_E_INVALID, "at most 256 shards");
   if(p->shard_id >= (1u << p->shard_bits)) return fail(JFGPU_E_INVALID, "shard_id out of range");
   int ndev = 0;
@@ -607,6 +606,7 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
   while(lsize < 63 && (1ull << lsize) < p->size) ++lsize;
   if(nword) {
     lsize = std::max(lsize, nword_min_lsize(p->k));
+    lsize = std::max<uint32_t>(lsize, kNTileBits + p->shard_bits);        // a shard holds at least one tile
     lsize = std::min<uint32_t>(lsize, 48);
   } else if(wide) {
     lsize = std::max(lsize, wide_min_lsize(p->k));
@@ -629,7 +629,7 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
   if(t->out_counter_len > 8) return fail(JFGPU_E_INVALID, "out_counter_len must be <= 8");
   t->wide = wide; t->nword = nword; t->key_words = (2 * p->k + 63) / 64; t->slot_words = nword ? kNWords : wide ? 2 : 1;
   if(nword) {
-    if(!nword_geom_init(t->nt.N, p->k, lsize, p->canonical ? 1 : 0)) return fail(JFGPU_E_INVALID, "table geometry does not fit a 256-bit slot");
+    if(!nword_geom_init(t->nt.N, p->k, lsize, p->canonical ? 1 : 0, p->shard_bits, p->shard_id)) return fail(JFGPU_E_INVALID, "table geometry does not fit a 256-bit slot");
     t->g = t->nt.N.g;
   } else if(wide) {
     if(!wide_geom_init(t->wt.W, p->k, lsize, p->canonical ? 1 : 0, p->shard_bits, p->shard_id)) return fail(JFGPU_E_INVALID, "table geometry does not fit a 128-bit slot");
@@ -698,6 +698,11 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
     t->part_ok = false; t->mode = MODE_DIRECT;
     const int nl = (int)(((size_t)32 << kNTileBits) + ((size_t)2 << kNTileBits));
     HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_nword_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, nl));
+    {                                                                          // the routing passes of a shard, world 1 included (abi_comm.inl)
+      const int rl = (int)nword_route_lds(t->g.nbytes);
+      HIP_TRY(hipFuncSetAttribute((const void*)partition_count_nword_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
+      HIP_TRY(hipFuncSetAttribute((const void*)partition_scatter_nword_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
+    }
   } else if(wide) {
     WideTable& w = t->wt;
     w.slots = d.slots; w.fwd_tbl = d.fwd_tbl; w.inv_tbl = d.inv_tbl; w.ovf_key = d.ovf_key; w.ovf_cnt = d.ovf_cnt;

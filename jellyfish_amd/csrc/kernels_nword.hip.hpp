@@ -88,11 +88,14 @@ inline uint32_t nword_min_lsize(uint32_t k) {
   if(need < (int)kNTileBits) need = kNTileBits;
   return (uint32_t)need;
 }
-inline bool nword_geom_init(NGeom& N, uint32_t k, uint32_t lsize_g, uint32_t canonical) {
+// shard_bits / shard_id: one shard of a table spread over GPUs, as wide_geom_init (kernels_wide.hip.hpp): the shard owns
+// the global positions whose top shard_bits bits are shard_id and holds at least one tile.  The tag is that of the whole
+// table (rem_bits = key_bits - lsize_g): the shard id is implied by the rank.
+inline bool nword_geom_init(NGeom& N, uint32_t k, uint32_t lsize_g, uint32_t canonical, uint32_t shard_bits = 0, uint32_t shard_id = 0) {
   TableGeom& g = N.g;
-  if(k < 65 || k > 128 || lsize_g > 63 || lsize_g < kNTileBits) return false;
+  if(k < 65 || k > 128 || lsize_g > 63 || shard_bits > lsize_g || lsize_g - shard_bits < kNTileBits) return false;
   memset(&g, 0, sizeof g);
-  g.k = k; g.key_bits = 2 * k; g.lsize_g = g.lsize_l = lsize_g;
+  g.k = k; g.key_bits = 2 * k; g.lsize_g = lsize_g; g.lsize_l = lsize_g - shard_bits; g.shard_bits = shard_bits; g.shard_id = shard_id;
   g.tile_bits = kNTileBits;
   g.rem_bits = g.key_bits - lsize_g;
   N.tag_full = g.tile_bits + g.rem_bits;
@@ -152,17 +155,24 @@ __device__ inline K256 nword_slot_key(const NTable& T, const uint64_t* inv_tbl, 
   const K256 rem = k256_and(tag, k256_low_mask(N.g.rem_bits));
   const uint64_t idx0 = k256_shr(tag, N.g.rem_bits).w[0];
   const K256 hi_part = k256_shl(rem, N.g.lsize_g);
-  K256 v = hi_part; v.w[0] |= tile_base | idx0;
+  K256 v = hi_part; v.w[0] |= ((uint64_t)N.g.shard_id << N.g.lsize_l) | tile_base | idx0;     // (the shard prefix goes back into the position)
   K256 key = hi_part; key.w[0] |= hash_tables_n256(inv_tbl, v, N.g.nbytes);
   return key;
 }
 
-// claim-or-increment.  Returns true when the key was new (this lane set the last word).
+// Where `key` lives, or false when its position names another shard (counted: a key is never silently inserted or
+// credited on a shard that does not own it -- jfgpu_sync reports it).
+__device__ inline bool nword_addr(const NTable& T, const K256& key, SlotAddr& a) {
+  a = slot_addr(T.N.g, hash_tables_n256(T.fwd_tbl, key, T.N.g.nbytes));
+  if(a.shard == T.N.g.shard_id) return true;
+  atomicAdd((unsigned long long*)&T.counters[CTR_MISROUTED], 1ull);
+  return false;
+}
+
+// claim-or-increment at the key's home.  Returns true when the key was new (this lane set the last word).
 template <bool RETURNING>
-__device__ inline bool nword_add(const NTable& T, const K256& key, uint64_t cnt) {
+__device__ inline bool nword_add_at(const NTable& T, const K256& key, const SlotAddr& a, uint64_t cnt) {
   const TableGeom& g = T.N.g;
-  const uint64_t pos = hash_tables_n256(T.fwd_tbl, key, g.nbytes);
-  const SlotAddr a = slot_addr(g, pos);
   const NSlot w = nword_words(T.N, key, a.idx0);
   const uint64_t add = cnt << (g.tag_bits + 1);
   for(uint32_t p = 0; p <= T.max_probe; ++p) {
@@ -191,11 +201,15 @@ __device__ inline bool nword_add(const NTable& T, const K256& key, uint64_t cnt)
   return false;
 }
 
-// Slot holding `key`, or ~0 when it is absent (a look-up: the first never-claimed slot ends the search).
-__device__ inline uint64_t nword_find(const NTable& T, const K256& key) {
+template <bool RETURNING>
+__device__ inline bool nword_add(const NTable& T, const K256& key, uint64_t cnt) {
+  SlotAddr a;
+  return nword_addr(T, key, a) && nword_add_at<RETURNING>(T, key, a, cnt);
+}
+
+// Slot holding `key` in the tile of `a`, or ~0 when it is absent (a look-up: the first never-claimed slot ends the search).
+__device__ inline uint64_t nword_find_at(const NTable& T, const K256& key, const SlotAddr& a) {
   const TableGeom& g = T.N.g;
-  const uint64_t pos = hash_tables_n256(T.fwd_tbl, key, g.nbytes);
-  const SlotAddr a = slot_addr(g, pos);
   const NSlot w = nword_words(T.N, key, a.idx0);
   for(uint32_t p = 0; p <= T.max_probe; ++p) {
     const uint64_t slot = a.tile_base + probe_slot(a.idx0, p, (uint32_t)g.tile_mask);
@@ -209,6 +223,10 @@ __device__ inline uint64_t nword_find(const NTable& T, const K256& key) {
   }
   return ~0ull;
 }
+__device__ inline uint64_t nword_find(const NTable& T, const K256& key) {     // (a key of another shard is not here)
+  const SlotAddr a = slot_addr(T.N.g, hash_tables_n256(T.fwd_tbl, key, T.N.g.nbytes));
+  return a.shard == T.N.g.shard_id ? nword_find_at(T, key, a) : ~0ull;
+}
 
 __device__ inline void nword_credit(const NTable& T, uint64_t slot, uint64_t cnt) {    // add to an existing slot
   const TableGeom& g = T.N.g;
@@ -220,8 +238,10 @@ __device__ inline void nword_credit(const NTable& T, uint64_t slot, uint64_t cnt
 __device__ inline bool nword_add_val(const NTable& T, const K256& key, uint64_t val) {
   const TableGeom& g = T.N.g;
   const uint64_t lowpart = val & g.cnt_max, units = val >> g.cnt_bits;
-  const bool is_new = nword_add<true>(T, key, lowpart);
-  if(units) { const uint64_t s = nword_find(T, key); if(s != ~0ull) { const DevTable d = ovf_view(T); ovf_add(d, s, units); } }
+  SlotAddr a;
+  if(!nword_addr(T, key, a)) return false;
+  const bool is_new = nword_add_at<true>(T, key, a, lowpart);
+  if(units) { const uint64_t s = nword_find_at(T, key, a); if(s != ~0ull) { const DevTable d = ovf_view(T); ovf_add(d, s, units); } }
   return is_new;
 }
 
@@ -435,6 +455,147 @@ __global__ __launch_bounds__(kBlock) void dump_tiles_nword_kernel(NTable T, uint
       for(uint32_t b = 0; b < key_bytes; ++b) dd[b] = (uint8_t)(key.w[b >> 3] >> (8 * (b & 7)));
       for(uint32_t b = 0; b < val_bytes; ++b) dd[key_bytes + b] = (uint8_t)(cnt >> (8 * b));
     }
+  }
+}
+
+// hash_counter::update_add on encoded keys of kw words, val == 1: the receive side of the exchange in the UPDATE pass of
+// count --if over shards (the two-word twin is update_keys_wide_kernel).  A key of another shard is counted as misrouted.
+__global__ __launch_bounds__(kBlock) void update_keys_nword_kernel(NTable T, const uint64_t* __restrict__ keys, uint64_t n, uint32_t kw) {
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const K256 key = load_key4(keys, i, kw, T.N.key_mask);
+    SlotAddr a;
+    if(!nword_addr(T, key, a)) continue;
+    const uint64_t s = nword_find_at(T, key, a);
+    if(s != ~0ull) nword_credit(T, s, 1);
+  }
+}
+
+// ---- multi-GPU: a contract buffer's k-mers grouped by owner (abi_comm.inl, key path) ---------------------------------
+// The two passes of partition_count / scatter_wide_kernel for 256-bit keys, reading the buffer like count_ascii_nword_kernel
+// (halo of 8 code words, `filled` validity, canonical form).  The owner is pos >> lsize_l under the shard's global matrix,
+// whose byte tables (up to 32 x 256 words, 64 KiB) sit in dynamic LDS: a k-mer's 32 gathers go to LDS, not to L2.
+// Per-owner counts never become a global atomic per k-mer: the lanes of a wave that route to the same owner are grouped
+// by ballot (one LDS atomic per wave and owner, and consecutive ranks in lane order), a workgroup's LDS counts go out with
+// one global atomic per owner.  Pass 1 writes kw (3 for k <= 96, 4 above) little-endian words per k-mer at its owner's
+// cursor, the layout of jfgpu_add_keys; a wave's k-mers for one owner land in neighbouring records.
+inline size_t nword_route_lds(uint32_t nbytes) { return (size_t)nbytes * 256 * 8 + 256 * 8 + 256 * 4 + 2 * (kBlock + 8) * 4; }
+
+struct NLane { uint32_t c, v, filled; K256 fw, rc; };     // a lane's 16 bases and the k-mer state just before them
+
+__device__ inline NLane nword_stage_tile(const NGeom& N, const uint8_t* __restrict__ base, int64_t tile_start, int64_t lo, int64_t hi,
+                                         uint32_t* s_codes, uint32_t* s_inv) {
+  const int tid = threadIdx.x;
+  NLane L;
+  load_pack16(base, tile_start + 16 * tid, lo, hi, L.c, L.v);
+  s_codes[tid + 8] = L.c; s_inv[tid + 8] = L.v;
+  if(tid < 8) { uint32_t hc, hv; load_pack16(base, tile_start - 128 + 16 * tid, lo, hi, hc, hv); s_codes[tid] = hc; s_inv[tid] = hv; }
+  __syncthreads();
+  for(int i = 0; i < 4; ++i) L.fw.w[i] = ((uint64_t)s_codes[tid + 7 - 2 * i - 1] << 32) | s_codes[tid + 7 - 2 * i];
+  L.fw = k256_and(L.fw, N.key_mask);
+  L.rc = revcomp256(L.fw, N.g.k);
+  L.filled = 0;
+  for(int q = 7; q >= 0; --q) {                            // nearest halo word first
+    const uint32_t iv = s_inv[tid + q] & 0xFFFFu;
+    if(iv == 0) { L.filled += 16; continue; }
+    L.filled += (uint32_t)__ffs((int)iv) - 1;
+    break;
+  }
+  if(L.filled > N.g.k) L.filled = N.g.k;
+  return L;
+}
+
+// f(j, key, valid) for the lane's 16 positions, called by every lane at every position (wave-uniform: f may ballot)
+template <typename F>
+__device__ inline void for_each_kmer_nword(const NGeom& N, NLane L, F&& f) {
+  const uint32_t k = N.g.k, rc_pos = 2 * (k - 1);
+#pragma unroll                                             // (unrolled: the callers' per-position arrays stay in registers)
+  for(int j = 0; j < kPerLane; ++j) {
+    const uint64_t code = (L.c >> (2 * (15 - j))) & 3u;
+    k256_roll_fw(L.fw, code, N.key_mask);
+    k256_roll_rc(L.rc, 3ull - code, rc_pos);
+    if((L.v >> (15 - j)) & 1u) L.filled = 0;
+    else if(L.filled < k) ++L.filled;
+    f(j, (N.g.canonical && k256_less(L.rc, L.fw)) ? L.rc : L.fw, L.filled >= k && !((L.v >> (15 - j)) & 1u));
+  }
+}
+
+// The rank of this lane's k-mer among the workgroup's k-mers of owner s (s_hist[s] grows by one LDS atomic per wave and
+// owner).  Called by every lane of the wave; valid: this lane has a k-mer here.
+__device__ inline uint32_t nword_wave_rank(bool valid, uint32_t s, uint32_t* s_hist) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint64_t pending = __ballot(valid);
+  uint32_t rank = 0;
+  while(pending) {                                         // (wave-uniform: one round per distinct owner in the wave)
+    const int leader = __ffsll((long long)pending) - 1;
+    const uint32_t so = __shfl(s, leader, 64);
+    const bool mine = valid && s == so;
+    const uint64_t m = __ballot(mine);
+    uint32_t b = 0;
+    if((int)lane == leader) b = atomicAdd(&s_hist[so], (uint32_t)__popcll(m));
+    b = __shfl(b, leader, 64);
+    if(mine) rank = b + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+    pending &= ~m;
+  }
+  return rank;
+}
+
+__global__ __launch_bounds__(kBlock) void partition_count_nword_kernel(NTable T, const uint8_t* __restrict__ base, int64_t lo, int64_t hi,
+                                                                       unsigned long long* __restrict__ shard_counts) {
+  JF_DYN_LDS(s_raw);
+  const NGeom& N = T.N;
+  uint64_t* s_fwd = reinterpret_cast<uint64_t*>(s_raw);
+  uint32_t* s_hist = reinterpret_cast<uint32_t*>(s_fwd + (size_t)N.g.nbytes * 256 + 256);
+  uint32_t* s_codes = s_hist + 256;
+  uint32_t* s_inv = s_codes + kBlock + 8;
+  load_tables_lds(s_fwd, T.fwd_tbl, N.g.nbytes);
+  const uint32_t n_shards = 1u << N.g.shard_bits;
+  for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x) s_hist[i] = 0;
+  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
+  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    __syncthreads();
+    const NLane L = nword_stage_tile(N, base, tile * kTilePos, lo, hi, s_codes, s_inv);
+    for_each_kmer_nword(N, L, [&](int, const K256& key, bool valid) {
+      const uint32_t s = valid ? (uint32_t)(hash_tables_n256(s_fwd, key, N.g.nbytes) >> N.g.lsize_l) : 0u;
+      nword_wave_rank(valid, s, s_hist);
+    });
+  }
+  __syncthreads();
+  for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x)
+    if(s_hist[i]) atomicAdd(&shard_counts[i], (unsigned long long)s_hist[i]);
+}
+
+__global__ __launch_bounds__(kBlock) void partition_scatter_nword_kernel(NTable T, const uint8_t* __restrict__ base, int64_t lo, int64_t hi,
+                                                                         unsigned long long* __restrict__ cursors, uint64_t* __restrict__ out, uint32_t kw) {
+  JF_DYN_LDS(s_raw);
+  const NGeom& N = T.N;
+  uint64_t* s_fwd = reinterpret_cast<uint64_t*>(s_raw);
+  unsigned long long* s_base = reinterpret_cast<unsigned long long*>(s_fwd + (size_t)N.g.nbytes * 256);
+  uint32_t* s_hist = reinterpret_cast<uint32_t*>(s_base + 256);
+  uint32_t* s_codes = s_hist + 256;
+  uint32_t* s_inv = s_codes + kBlock + 8;
+  load_tables_lds(s_fwd, T.fwd_tbl, N.g.nbytes);
+  const uint32_t n_shards = 1u << N.g.shard_bits;
+  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
+  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    __syncthreads();
+    for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x) s_hist[i] = 0;
+    const NLane L = nword_stage_tile(N, base, tile * kTilePos, lo, hi, s_codes, s_inv);     // contains a barrier
+    // two sweeps over the lane's windows (the keys are 32 bytes: they are rolled again rather than kept): ranks, then stores
+    uint32_t rank[kPerLane], sh[kPerLane];
+    for_each_kmer_nword(N, L, [&](int j, const K256& key, bool valid) {
+      sh[j] = valid ? (uint32_t)(hash_tables_n256(s_fwd, key, N.g.nbytes) >> N.g.lsize_l) : 0u;
+      rank[j] = nword_wave_rank(valid, sh[j], s_hist);
+    });
+    __syncthreads();
+    for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x)
+      s_base[i] = s_hist[i] ? atomicAdd(&cursors[i], (unsigned long long)s_hist[i]) : 0ull;
+    __syncthreads();
+    for_each_kmer_nword(N, L, [&](int j, const K256& key, bool valid) {
+      if(!valid) return;
+      uint64_t* dst = out + (uint64_t)kw * (s_base[sh[j]] + rank[j]);
+#pragma unroll
+      for(uint32_t q = 0; q < 4; ++q) if(q < kw) dst[q] = key.w[q];
+    });
   }
 }
 

@@ -14,6 +14,12 @@
 
 namespace jfgpu {
 
+// Sharded tables of keys of three and four words (k > 64): a step of the exchange is cut into pieces whose send buffer
+// (k-mers of the piece x key_words x 8 bytes, at most one k-mer per input byte) stays under this many bytes.  Two send
+// buffers (the turn pair) and two receive buffers of about this size live on every rank.  Keys of one and two words are
+// not cut (a step is one piece unless the shards grow).
+constexpr uint64_t kCommNWordPieceBytes = 1ull << 30;
+
 struct Tuning {
   // ---- tables (jfgpu_create)
   int mode = 0;                  // JFGPU_MODE=direct|partitioned            0: not set, 1 direct, 2 partitioned
@@ -50,6 +56,7 @@ struct Tuning {
   int comm_gbits = 10;           // JFGPU_COMM_GBITS       bits of (owner, coarse bucket) the sender routes by (tests: fewer, so that small shards get the wide receive split of full-size ones)
   uint32_t comm_split_cap = 0;   // JFGPU_COMM_SPLIT_CAP   items per region of the receive split (tests: forces region overflow there)
   int comm_split = 1;            // JFGPU_COMM_SPLIT=0     the receive split by round 4's sort-based kernel instead of the wave-per-stream one (A/B)
+  uint64_t comm_piece_bytes = 0; // JFGPU_COMM_PIECE_BYTES keys of three and four words: send-buffer bytes of a piece of a step (0: kCommNWordPieceBytes; tests: small, so that steps go in many pieces)
 
   static Tuning from_env() {
     Tuning u;
@@ -86,6 +93,7 @@ struct Tuning {
     if(const char* e = str("JFGPU_COMM_SPLIT_CAP")) u.comm_split_cap = (uint32_t)std::max(64, atoi(e));
     if(const char* e = str("JFGPU_COMM_SLACK")) u.comm_slack = std::min(1.0, std::max(0.0, atof(e)));
     if(const char* e = str("JFGPU_COMM_GBITS")) u.comm_gbits = std::min(10, std::max(1, atoi(e)));
+    if(const char* e = str("JFGPU_COMM_PIECE_BYTES")) u.comm_piece_bytes = strtoull(e, 0, 10);
     return u;
   }
 };

@@ -94,9 +94,14 @@ __device__ __forceinline__ uint32_t inf_bits(InfBits& s, int n) {   // n <= 32, 
 }
 
 // Canonical Huffman tables from lens[0..n): counts, symbols in code order, and the first-level lookup (codes of at most
-// kInfLut bits; longer ones read bit by bit from cnt / sym).  Over-subscribed sets fail; incomplete ones are kept (an
-// unassigned code then fails to decode).  Every lane calls it; lane 0 does the serial part.
-__device__ void inf_build(uint8_t* lds, const uint8_t* lens, int n, uint16_t* cnt, uint16_t* sym, uint16_t* lut, unsigned lane) {
+// kInfLut bits; longer ones read bit by bit from cnt / sym).  Over-subscribed sets fail.  Incomplete sets fail as they
+// do in zlib (inftrees.c), so that the verdict on a stream is the reference reader's: the code-length code must be
+// complete (INF_SET_COMPLETE); a literal / length or distance set may be incomplete only when it has no code longer
+// than one bit, that is a single code of length 1 or no code at all (INF_SET_DYNAMIC); the fixed distance code, 30 of
+// 32 codes, is kept as it is (INF_SET_ANY).  An unassigned code of a set that was kept fails to decode.  Every lane
+// calls it; lane 0 does the serial part.
+enum : int { INF_SET_COMPLETE = 0, INF_SET_DYNAMIC = 1, INF_SET_ANY = 2 };
+__device__ void inf_build(uint8_t* lds, const uint8_t* lens, int n, int rule, uint16_t* cnt, uint16_t* sym, uint16_t* lut, unsigned lane) {
   uint16_t* offs = (uint16_t*)(lds + kInfOffOffs);
   uint32_t* flag = (uint32_t*)(lds + kInfOffFlag);
   __syncthreads();                                             // every lane is done with the previous tables
@@ -105,8 +110,9 @@ __device__ void inf_build(uint8_t* lds, const uint8_t* lens, int n, uint16_t* cn
     for(int l = 0; l < 16; ++l) cnt[l] = 0;
     for(int s = 0; s < n; ++s) cnt[lens[s]]++;
     cnt[0] = 0;
-    int left = 1, bad = 0;
-    for(int l = 1; l < 16; ++l) { left <<= 1; left -= cnt[l]; if(left < 0) bad = 1; }
+    int left = 1, bad = 0, longest = 0;
+    for(int l = 1; l < 16 && !bad; ++l) { left <<= 1; left -= cnt[l]; if(left < 0) bad = 1; if(cnt[l]) longest = l; }
+    if(left > 0 && (rule == INF_SET_COMPLETE || (rule == INF_SET_DYNAMIC && longest > 1))) bad = 1;
     offs[1] = 0;
     for(int l = 1; l < 15; ++l) offs[l + 1] = offs[l] + cnt[l];
     for(int s = 0; s < n; ++s) if(lens[s]) sym[offs[lens[s]]++] = (uint16_t)s;
@@ -202,8 +208,8 @@ __global__ __launch_bounds__(64) void bgzf_inflate_kernel(const uint8_t* __restr
         for(int i = 0; i < 30; ++i) lens[288 + i] = 5;
       }
       __syncthreads();
-      inf_build(lds, lens, 288, lit_cnt, lit_sym, lit_lut, lane);
-      inf_build(lds, lens + 288, 30, dist_cnt, dist_sym, dist_lut, lane);
+      inf_build(lds, lens, 288, INF_SET_COMPLETE, lit_cnt, lit_sym, lit_lut, lane);
+      inf_build(lds, lens + 288, 30, INF_SET_ANY, dist_cnt, dist_sym, dist_lut, lane);
     } else {                                                     // dynamic: the code-length code, then the two codes
       const uint32_t nlen = inf_bits(s, 5) + 257, ndist = inf_bits(s, 5) + 1, ncode = inf_bits(s, 4) + 4;
       if(nlen > 286 || ndist > 30) { err = INF_BAD_TABLE; break; }
@@ -218,10 +224,10 @@ __global__ __launch_bounds__(64) void bgzf_inflate_kernel(const uint8_t* __restr
       }
       __syncthreads();
       if(err) break;
-      inf_build(lds, lens, 19, lit_cnt, lit_sym, lit_lut, lane);
+      inf_build(lds, lens, 19, INF_SET_COMPLETE, lit_cnt, lit_sym, lit_lut, lane);
       if(*flag) { err = INF_BAD_TABLE; break; }
       // literal / length lengths go to lens[0..nlen), distance lengths to lens[288..288+ndist)
-      uint32_t idx = 0, prev = 0;
+      uint32_t idx = 0, prev = 0;                                 // prev: the last length written, by whichever symbol
       while(idx < nlen + ndist) {
         if(!inf_refill(s)) { err = INF_OVERRUN; break; }
         const int sym = inf_decode(s, lit_cnt, lit_sym, lit_lut);
@@ -229,8 +235,8 @@ __global__ __launch_bounds__(64) void bgzf_inflate_kernel(const uint8_t* __restr
         uint32_t v, rep;
         if(sym < 16) { v = (uint32_t)sym; rep = 1; prev = v; }
         else if(sym == 16) { if(idx == 0) { err = INF_BAD_TABLE; break; } v = prev; rep = 3 + inf_bits(s, 2); }
-        else if(sym == 17) { v = 0; rep = 3 + inf_bits(s, 3); }
-        else { v = 0; rep = 11 + inf_bits(s, 7); }
+        else if(sym == 17) { v = 0; rep = 3 + inf_bits(s, 3); prev = 0; }
+        else { v = 0; rep = 11 + inf_bits(s, 7); prev = 0; }
         if(idx + rep > nlen + ndist) { err = INF_BAD_TABLE; break; }
         if(lane == 0) for(uint32_t r = 0; r < rep; ++r) { const uint32_t i = idx + r; lens[i < nlen ? i : 288 + i - nlen] = (uint8_t)v; }
         idx += rep;
@@ -238,9 +244,9 @@ __global__ __launch_bounds__(64) void bgzf_inflate_kernel(const uint8_t* __restr
       if(err) break;
       __syncthreads();
       if(lens[256] == 0) { err = INF_BAD_TABLE; break; }         // no end-of-block code
-      inf_build(lds, lens, (int)nlen, lit_cnt, lit_sym, lit_lut, lane);
+      inf_build(lds, lens, (int)nlen, INF_SET_DYNAMIC, lit_cnt, lit_sym, lit_lut, lane);
       if(*flag) { err = INF_BAD_TABLE; break; }
-      inf_build(lds, lens + 288, (int)ndist, dist_cnt, dist_sym, dist_lut, lane);
+      inf_build(lds, lens + 288, (int)ndist, INF_SET_DYNAMIC, dist_cnt, dist_sym, dist_lut, lane);
     }
     if(*flag) { err = INF_BAD_TABLE; break; }
     for(;;) {                                                    // the codes of one block
@@ -277,7 +283,7 @@ __global__ __launch_bounds__(64) void bgzf_inflate_kernel(const uint8_t* __restr
   }
   __syncthreads();
   if(!err && op != isize) err = INF_BAD_ISIZE;
-  if(!err && (s.ip - (uint64_t)(s.bc >> 3)) > (uint64_t)B.c_off + B.c_len + 4) err = INF_OVERRUN;
+  if(!err && (s.ip - (uint64_t)(s.bc >> 3)) > (uint64_t)B.c_off + B.c_len) err = INF_OVERRUN;   // the last bit used lies inside the data
   if(!err) {
     // CRC32: lane j takes bytes [j*seg, (j+1)*seg), its register moved past the bytes behind them, xor over the wave
     const uint32_t seg = (isize + 63) / 64;

@@ -110,14 +110,23 @@ def deflate(data, variant):
     return c.compress(data) + c.flush()
 
 
-def bgzf_member(data, variant="default", extra_first=b""):
-    """One BGZF member; extra_first: gzip extra subfields (SI1 SI2 LEN data) placed before the 'BC' one."""
-    assert len(data) <= 65536
-    cdata = deflate(data, variant)
+def bgzf_member(data, variant="default", extra_first=b"", cdata=None, crc32=None, isize=None, oversize=False):
+    """One BGZF member; extra_first: gzip extra subfields (SI1 SI2 LEN data) placed before the 'BC' one.
+
+    cdata: ready-made deflate bytes to wrap instead of compressing data (data may then be None when crc32 and isize are
+    given); crc32 / isize: the trailer's fields when they are not to be those of data; oversize: let the member be longer
+    than BSIZE can say (the field wraps: such a member is only reachable through a caller's own block table)."""
+    if cdata is None:
+        assert len(data) <= 65536
+        cdata = deflate(data, variant)
+    if crc32 is None:
+        crc32 = zlib.crc32(data) & 0xFFFFFFFF
+    if isize is None:
+        isize = len(data)
     bsize = 18 + len(extra_first) + len(cdata) + 8
-    assert bsize <= 65536, "member does not fit BGZF: use a smaller block size with this variant"
-    head = b"\x1f\x8b\x08\x04\0\0\0\0\0\xff" + struct.pack("<H", 6 + len(extra_first)) + extra_first + b"BC" + struct.pack("<HH", 2, bsize - 1)
-    return head + cdata + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data))
+    assert oversize or bsize <= 65536, "member does not fit BGZF: use a smaller block size with this variant"
+    head = b"\x1f\x8b\x08\x04\0\0\0\0\0\xff" + struct.pack("<H", 6 + len(extra_first)) + extra_first + b"BC" + struct.pack("<HH", 2, (bsize - 1) & 0xFFFF)
+    return head + cdata + struct.pack("<II", crc32 & 0xFFFFFFFF, isize & 0xFFFFFFFF)
 
 
 def bgzf(data, block_size=65280, variants=("default",), empty_at=(), eof=True, cuts=None, extra_first=b""):

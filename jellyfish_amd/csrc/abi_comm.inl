@@ -959,77 +959,31 @@ int comm_exchange_items_ipc(jfgpu_comm*) { return fail(JFGPU_E_UNSUPPORTED, "no 
 // hash_counter::double_size (hash_counter.hpp:200-238) for a table spread over ranks.  The doubled table has a new matrix
 // (the next one of the reference's random() stream, the same on every rank), so an entry's owner changes: every rank
 // walks its old shard, puts what stays with it into its new shard and sends the rest -- (key, count) pairs, grouped by
-// new owner -- through the key path's exchange, twice (keys, then counts, same grouping).  One-word keys.
+// new owner -- through the key path's exchange, twice (keys, then counts, same grouping).  Every key width (KeyOps): a
+// pair is kw key words (low first) and a count.
 //   pass 0: how many pairs for every owner;  pass 1: the pairs, at the cursors (= offsets), and the local inserts
-__global__ __launch_bounds__(kBlock) void reshard_kernel(DevTable old, DevTable neu, int have_ovf, int pass, unsigned long long* __restrict__ cursors,
+template <class Table>
+__global__ __launch_bounds__(kBlock) void reshard_kernel(Table old, Table neu, int have_ovf, int pass, uint32_t kw, unsigned long long* __restrict__ cursors,
                                                          uint64_t* __restrict__ keys_out, uint64_t* __restrict__ cnts_out) {
-  const uint64_t n = 1ull << old.g.lsize_l;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t w = slot_ld(old, i);
-    if(!w) continue;
-    const uint64_t key = slot_key(old.g, old.inv_tbl, w, i & ~old.g.tile_mask);
-    const uint32_t owner = (uint32_t)(hash_tables(neu.fwd_tbl, key, neu.g.nbytes) >> neu.g.lsize_l);
-    if(owner == neu.g.shard_id) { if(pass) table_add_val(neu, neu.fwd_tbl, key, full_count(old, w, i, have_ovf)); }
-    else {
-      const unsigned long long at = atomicAdd(&cursors[owner], 1ull);
-      if(pass) { keys_out[at] = key; cnts_out[at] = full_count(old, w, i, have_ovf); }
-    }
-  }
-}
-__global__ __launch_bounds__(kBlock) void add_pairs_kernel(DevTable T, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ cnts, uint64_t n) {
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    table_add_val(T, T.fwd_tbl, keys[i], cnts[i]);
-}
-
-// The same for two-word keys: a pair is two key words (low, high) and a count.
-__global__ __launch_bounds__(kBlock) void reshard_wide_kernel(WideTable old, WideTable neu, int have_ovf, int pass, unsigned long long* __restrict__ cursors,
-                                                              uint64_t* __restrict__ keys_out, uint64_t* __restrict__ cnts_out) {
-  const TableGeom& g = old.W.g;
-  const DevTable od = ovf_view(old);
+  typedef KeyOps<Table> K;
+  const TableGeom& g = K::geom(old);
   const uint64_t n = 1ull << g.lsize_l;
   for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t hi = old.slots[2 * i + 1];
-    if(!hi) continue;
-    const uint64_t lo = old.slots[2 * i];
-    if(!lo) continue;                                    // hi claimed, never completed: holds no key
-    const u128 key = wide_slot_key(old, old.inv_tbl, lo, hi, i & ~g.tile_mask);
-    uint64_t cnt = slot_count(g, hi);
-    if(have_ovf) cnt += ovf_get(od, i) << g.cnt_bits;
-    const uint32_t owner = slot_addr(neu.W.g, hash_tables_wide(neu.fwd_tbl, key, neu.W.g.nbytes)).shard;
-    if(owner == neu.W.g.shard_id) { if(pass) wide_add_val(neu, neu.fwd_tbl, key, cnt); }
+    typename K::Slot s;
+    if(!K::load(old, i, s)) continue;                    // (a claim that was never completed holds no key)
+    const typename K::Key key = K::key(old, s, i & ~g.tile_mask);
+    const uint32_t owner = K::owner(neu, key);
+    if(owner == K::geom(neu).shard_id) { if(pass) K::add_val(neu, key, K::count(old, s, i, have_ovf)); }
     else {
       const unsigned long long at = atomicAdd(&cursors[owner], 1ull);
-      if(pass) { keys_out[2 * at] = (uint64_t)key; keys_out[2 * at + 1] = (uint64_t)(key >> 64); cnts_out[at] = cnt; }
+      if(pass) { K::store_key(keys_out + (uint64_t)kw * at, key, kw); cnts_out[at] = K::count(old, s, i, have_ovf); }
     }
   }
 }
-__global__ __launch_bounds__(kBlock) void add_pairs_wide_kernel(WideTable T, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ cnts, uint64_t n) {
+template <class Table>
+__global__ __launch_bounds__(kBlock) void add_pairs_kernel(Table T, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ cnts, uint64_t n, uint32_t kw) {
   for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    wide_add_val(T, T.fwd_tbl, ((u128)keys[2 * i + 1] << 64) | keys[2 * i], cnts[i]);
-}
-
-// The same for keys of three and four words: a pair is kw key words (low first) and a count.
-__global__ __launch_bounds__(kBlock) void reshard_nword_kernel(NTable old, NTable neu, int have_ovf, int pass, uint32_t kw, unsigned long long* __restrict__ cursors,
-                                                               uint64_t* __restrict__ keys_out, uint64_t* __restrict__ cnts_out) {
-  const TableGeom& g = old.N.g;
-  const DevTable od = ovf_view(old);
-  const uint64_t n = 1ull << g.lsize_l;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t* sp = &old.slots[4 * i];
-    if(!nword_complete(sp)) continue;                    // (a claim that was never completed holds no key)
-    const K256 key = nword_slot_key(old, old.inv_tbl, sp, i & ~g.tile_mask);
-    const uint64_t cnt = nword_count_at(old, od, i, sp[3], have_ovf);
-    const uint32_t owner = slot_addr(neu.N.g, hash_tables_n256(neu.fwd_tbl, key, neu.N.g.nbytes)).shard;
-    if(owner == neu.N.g.shard_id) { if(pass) nword_add_val(neu, key, cnt); }
-    else {
-      const unsigned long long at = atomicAdd(&cursors[owner], 1ull);
-      if(pass) { for(uint32_t q = 0; q < kw; ++q) keys_out[(uint64_t)kw * at + q] = key.w[q]; cnts_out[at] = cnt; }
-    }
-  }
-}
-__global__ __launch_bounds__(kBlock) void add_pairs_nword_kernel(NTable T, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ cnts, uint64_t n, uint32_t kw) {
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    nword_add_val(T, load_key4(keys, i, kw, T.N.key_mask), cnts[i]);
+    KeyOps<Table>::add_val(T, KeyOps<Table>::load_key(T, keys, i, kw), cnts[i]);
 }
 
 int comm_exchange_rccl(jfgpu_comm* c); int comm_exchange_local(jfgpu_comm* c); int comm_exchange_ipc(jfgpu_comm* c);
@@ -1084,9 +1038,9 @@ int comm_grow(jfgpu_comm* c) {
     const int have_ovf = (int)(N[q].ctr[CTR_OVF_USED] != 0);
     const dim3 grid(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), block(kBlock);
     HIP_TRY(hipMemsetAsync(R.d_cnt, 0, sizeof(unsigned long long) * W, t->stream));
-    if(t->nword) hipLaunchKernelGGL(reshard_nword_kernel, grid, block, 0, t->stream, t->nt, N[q].nn, have_ovf, 0, (uint32_t)kw, R.d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
-    else if(t->wide) hipLaunchKernelGGL(reshard_wide_kernel, grid, block, 0, t->stream, t->wt, N[q].nw, have_ovf, 0, R.d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
-    else hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, t->dt, N[q].nd, have_ovf, 0, R.d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
+    with_view(t, N[q], [&](const auto& old, const auto& neu) {
+      hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, old, neu, have_ovf, 0, (uint32_t)kw, R.d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
+    });
     std::vector<unsigned long long> h(W);
     HIP_TRY(hipMemcpyAsync(h.data(), R.d_cnt, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
@@ -1102,9 +1056,9 @@ int comm_grow(jfgpu_comm* c) {
     rc = comm_reserve_send(c, R, 0, std::max<uint64_t>(total * kw, 1), t->stream); if(rc) return rc;
     rc = comm_reserve_send(c, R, 1, std::max<uint64_t>(total, 1), t->stream); if(rc) return rc;
     HIP_TRY(hipMemcpyAsync(R.d_cnt, h.data(), sizeof(unsigned long long) * W, hipMemcpyHostToDevice, t->stream));   // cursors = offsets
-    if(t->nword) hipLaunchKernelGGL(reshard_nword_kernel, grid, block, 0, t->stream, t->nt, N[q].nn, have_ovf, 1, (uint32_t)kw, R.d_cnt, R.send[0], R.send[1]);
-    else if(t->wide) hipLaunchKernelGGL(reshard_wide_kernel, grid, block, 0, t->stream, t->wt, N[q].nw, have_ovf, 1, R.d_cnt, R.send[0], R.send[1]);
-    else hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, t->dt, N[q].nd, have_ovf, 1, R.d_cnt, R.send[0], R.send[1]);
+    with_view(t, N[q], [&](const auto& old, const auto& neu) {
+      hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, old, neu, have_ovf, 1, (uint32_t)kw, R.d_cnt, R.send[0], R.send[1]);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(t->stream));
     R.used[0] = R.used[1] = false;                            // (everything before is complete: the exchanges below start from a clean slate)
@@ -1138,9 +1092,9 @@ int comm_grow(jfgpu_comm* c) {
       }
       IPC_TRACE(c, "grow: shard %u, arrived/not mine per sender:%s", t->g.shard_id, hs.c_str());
     }
-    if(n && t->nword) hipLaunchKernelGGL(add_pairs_nword_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, N[q].nn, (const uint64_t*)R.recv[0], (const uint64_t*)R.recv[1], n, t->key_words);
-    else if(n && t->wide) hipLaunchKernelGGL(add_pairs_wide_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, N[q].nw, (const uint64_t*)R.recv[0], (const uint64_t*)R.recv[1], n);
-    else if(n) hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, N[q].nd, (const uint64_t*)R.recv[0], (const uint64_t*)R.recv[1], n);
+    if(n) with_view(t, N[q], [&](const auto&, const auto& neu) {
+      hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, neu, (const uint64_t*)R.recv[0], (const uint64_t*)R.recv[1], n, t->key_words);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(R.consumed[0], t->stream));
     HIP_TRY(hipEventRecord(R.consumed[1], t->stream));
@@ -1687,8 +1641,9 @@ int jfgpu_add_key_vals(jfgpu_table* t, const uint64_t* keys, const uint64_t* val
     rc = part_flush(t); if(rc) return done(rc);
     t->pristine = false;
     const dim3 grid(grid_for(t, take / kBlock + 1)), block(kBlock);
-    if(t->wide) hipLaunchKernelGGL(add_pairs_wide_kernel, grid, block, 0, t->stream, t->wt, (const uint64_t*)(d_k + off * kw), (const uint64_t*)(d_v + off), (uint64_t)take);
-    else hipLaunchKernelGGL(add_pairs_kernel, grid, block, 0, t->stream, t->dt, (const uint64_t*)(d_k + off), (const uint64_t*)(d_v + off), (uint64_t)take);
+    with_view(t, [&](const auto& T) {
+      hipLaunchKernelGGL(add_pairs_kernel, grid, block, 0, t->stream, T, (const uint64_t*)(d_k + off * kw), (const uint64_t*)(d_v + off), (uint64_t)take, t->key_words);
+    });
     if(hipGetLastError() != hipSuccess) return done(fail(JFGPU_E_HIP, "add_key_vals: launch"));
     off += (size_t)take;
   }

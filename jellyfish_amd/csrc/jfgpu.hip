@@ -414,22 +414,60 @@ int ensure_stage(jfgpu_table* t) {
 
 #include "host_partition.inl"
 
+// The view of the table for its key width (one, two, or three and four words), handed to a generic callable.
+template <class F> void with_view(jfgpu_table* t, F&& f) {
+  if(t->nword) f(t->nt); else if(t->wide) f(t->wt); else f(t->dt);
+}
+
+// stats / histo / tile counts / digest: the one-word kernels, scan_kernel for the wider keys.
+// out: 64-bit counters, zeroed by the caller (tile_counts for SCAN_TILES: the wider keys want them zeroed as well).
+struct ScanArgs { int what; uint64_t lower = 0, upper = ~0ull; int have_ovf = 0; uint64_t hbase = 0, hceil = 0, hinc = 1, nb = 1; };
+void launch_scan(jfgpu_table* t, const DevTable& T, const ScanArgs& a, unsigned long long* out, uint32_t* tile_counts) {
+  const dim3 grid(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), block(kBlock);
+  if(a.what == SCAN_STATS) hipLaunchKernelGGL(stats_kernel, grid, block, 0, t->stream, T, a.lower, a.upper, a.have_ovf, out);
+  else if(a.what == SCAN_HISTO) hipLaunchKernelGGL(histo_kernel, grid, block, 0, t->stream, T, a.hbase, a.hceil, a.hinc, a.nb, a.have_ovf, out);
+  else if(a.what == SCAN_DIGEST) hipLaunchKernelGGL(digest_kernel, grid, block, 0, t->stream, T, a.lower, a.upper, a.have_ovf, out);
+  else hipLaunchKernelGGL(tile_count_kernel, dim3(grid_for(t, n_tiles_of(t))), block, 0, t->stream, T, a.lower, a.upper, a.have_ovf, n_tiles_of(t), tile_counts);
+}
+template <class Table>
+void launch_scan(jfgpu_table* t, const Table& T, const ScanArgs& a, unsigned long long* out, uint32_t* tile_counts) {
+  hipLaunchKernelGGL(scan_kernel, dim3(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), dim3(kBlock), 0, t->stream, T, a.what, a.lower, a.upper, a.have_ovf,
+                     a.hbase, a.hceil, a.hinc, a.nb, out, tile_counts);
+}
+
+// Pass 2 of the sorted dump (jfgpu_dump_next) for tiles [t0, t0 + ntile): records at d_tile_off, into d_dump.
+void launch_dump(jfgpu_table* t, const DevTable& T, uint64_t t0, uint64_t ntile, uint32_t key_bytes) {
+  const size_t lds = ((size_t)8 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits) + (size_t)t->g.nbytes * 2048;
+  hipLaunchKernelGGL(dump_tiles_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), lds, t->stream, T, t->dump_lower,
+                     t->dump_upper, t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump, key_bytes,
+                     t->out_counter_len);
+}
+template <class Table>
+void launch_dump(jfgpu_table* t, const Table& T, uint64_t t0, uint64_t ntile, uint32_t key_bytes) {
+  const size_t lds = ((size_t)(8 * KeyOps<Table>::kSlotWords) << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits);     // 16 or 32 bytes of slot, 2 of index
+  hipLaunchKernelGGL(dump_tiles_words_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), lds, t->stream, T, t->dump_lower, t->dump_upper,
+                     t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump, key_bytes, t->out_counter_len);
+}
+
+// One scan into n 64-bit counters of its own (4, or a histogram's buckets), copied to `out` when it is complete.
+int scan_to_host(jfgpu_table* t, const ScanArgs& a, uint64_t n, uint64_t* out) {
+  unsigned long long* d = nullptr;
+  HIP_TRY(hipMalloc((void**)&d, n * sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(d, 0, n * sizeof(unsigned long long), t->stream));
+  with_view(t, [&](const auto& T) { launch_scan(t, T, a, d, (uint32_t*)nullptr); });
+  hipError_t e = hipMemcpyAsync(out, d, n * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream);
+  if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  hipFree(d);
+  if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
+  return JFGPU_OK;
+}
+
 int measure_occupancy(jfgpu_table* t) {
   int rc = part_flush(t); if(rc) return rc;
   uint64_t c[CTR_COUNT];
   rc = check_deferred(t, c); if(rc) return rc;
-  unsigned long long* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, 4 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), t->stream));
-  const int grid = grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1);
-  if(t->nword) hipLaunchKernelGGL(scan_nword_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->nt, 0, 0ull, ~0ull, 0, 0ull, 0ull, 1ull, 1ull, d, (uint32_t*)nullptr);
-  else if(t->wide) hipLaunchKernelGGL(scan_wide_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, 0, 0ull, ~0ull, 0, 0ull, 0ull, 1ull, 1ull, d, (uint32_t*)nullptr);
-  else hipLaunchKernelGGL(stats_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, 0ull, ~0ull, 0, d);
-  unsigned long long h[4];
-  hipError_t e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, t->stream);
-  if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  hipFree(d);
-  if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
+  uint64_t h[4];
+  rc = scan_to_host(t, ScanArgs{SCAN_STATS}, 4, h); if(rc) return rc;
   t->occ_known = h[1]; t->fed_since = 0;
   return JFGPU_OK;
 }
@@ -447,6 +485,10 @@ struct GrowNew {
   uint64_t cap2 = 0;
   uint64_t ctr[CTR_COUNT];
 };
+// ... and the old view together with the new one
+template <class F> void with_view(jfgpu_table* t, GrowNew& N, F&& f) {
+  if(t->nword) f(t->nt, N.nn); else if(t->wide) f(t->wt, N.nw); else f(t->dt, N.nd);
+}
 
 int grow_prepare(jfgpu_table* t, GrowNew& N) {
   int rc = part_flush(t); if(rc) return rc;
@@ -539,7 +581,7 @@ int grow_swap(jfgpu_table* t, GrowNew& N) {
   if(t->wide) {
     t->wt = N.nw;
     const int wl = (int)(((size_t)16 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits));
-    HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
+    HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_words_kernel<WideTable>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
   }
   part_geom_init(t);
   if(t->mode == MODE_PARTITIONED && !t->part_ok) t->mode = MODE_AUTO;
@@ -553,9 +595,7 @@ int table_grow(jfgpu_table* t) {
   int rc = grow_prepare(t, N); if(rc) return rc;
   const int have_ovf = (int)(N.ctr[CTR_OVF_USED] != 0);
   const dim3 grid(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), block(kBlock);
-  if(t->nword) hipLaunchKernelGGL(rehash_nword_kernel, grid, block, 0, t->stream, t->nt, N.nn, have_ovf);
-  else if(t->wide) hipLaunchKernelGGL(rehash_wide_kernel, grid, block, 0, t->stream, t->wt, N.nw, have_ovf);
-  else hipLaunchKernelGGL(rehash_kernel, grid, block, 0, t->stream, t->dt, N.nd, have_ovf);
+  with_view(t, N, [&](const auto& old, const auto& neu) { hipLaunchKernelGGL(rehash_kernel, grid, block, 0, t->stream, old, neu, have_ovf); });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(t->stream));
   return grow_swap(t, N);
@@ -697,7 +737,7 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
     w.ovf_mask = d.ovf_mask; w.counters = d.counters; w.max_probe = d.max_probe;
     t->part_ok = false; t->mode = MODE_DIRECT;
     const int nl = (int)(((size_t)32 << kNTileBits) + ((size_t)2 << kNTileBits));
-    HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_nword_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, nl));
+    HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_words_kernel<NTable>, hipFuncAttributeMaxDynamicSharedMemorySize, nl));
     {                                                                          // the routing passes of a shard, world 1 included (abi_comm.inl)
       const int rl = (int)nword_route_lds(t->g.nbytes);
       HIP_TRY(hipFuncSetAttribute((const void*)partition_count_nword_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
@@ -710,7 +750,7 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
     memset(&w.bloom, 0, sizeof w.bloom);
     part_geom_init(t.get());
     const int wl = (int)(((size_t)16 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits));
-    HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
+    HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_words_kernel<WideTable>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
   } else part_geom_init(t.get());
   if(!nword) {
     if(t->tun.mode == 1) t->mode = MODE_DIRECT;
@@ -1082,18 +1122,8 @@ int jfgpu_stats_compute(jfgpu_table* t, uint64_t lower, uint64_t upper, jfgpu_st
   if(!out) return fail(JFGPU_E_INVALID, "null out");
   uint64_t c[CTR_COUNT];
   rc = check_deferred(t, c); if(rc) return rc;
-  unsigned long long* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, 4 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), t->stream));
-  const int grid = grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1);
-  if(t->nword) hipLaunchKernelGGL(scan_nword_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->nt, 0, lower, upper, (int)(c[CTR_OVF_USED] != 0), 0ull, 0ull, 1ull, 1ull, d, (uint32_t*)nullptr);
-  else if(t->wide) hipLaunchKernelGGL(scan_wide_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, 0, lower, upper, (int)(c[CTR_OVF_USED] != 0), 0ull, 0ull, 1ull, 1ull, d, (uint32_t*)nullptr);
-  else hipLaunchKernelGGL(stats_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, lower, upper, (int)(c[CTR_OVF_USED] != 0), d);
-  unsigned long long h[4];
-  hipError_t e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, t->stream);
-  if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  hipFree(d);
-  if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
+  uint64_t h[4];
+  rc = scan_to_host(t, ScanArgs{SCAN_STATS, lower, upper, (int)(c[CTR_OVF_USED] != 0)}, 4, h); if(rc) return rc;
   out->unique = h[0]; out->distinct = h[1]; out->total = h[2]; out->max_count = h[3];
   out->occupied = h[1]; out->mers_fed = c[CTR_MERS];
   return JFGPU_OK;
@@ -1105,18 +1135,7 @@ int jfgpu_digest(jfgpu_table* t, uint64_t lower, uint64_t upper, uint64_t* out4)
   if(!out4) return fail(JFGPU_E_INVALID, "null out");
   uint64_t c[CTR_COUNT];
   rc = check_deferred(t, c); if(rc) return rc;
-  unsigned long long* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, 4 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), t->stream));
-  const int grid = grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1);
-  if(t->nword) hipLaunchKernelGGL(scan_nword_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->nt, 3, lower, upper, (int)(c[CTR_OVF_USED] != 0), 0ull, 0ull, 1ull, 1ull, d, (uint32_t*)nullptr);
-  else if(t->wide) hipLaunchKernelGGL(digest_wide_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, lower, upper, (int)(c[CTR_OVF_USED] != 0), d);
-  else hipLaunchKernelGGL(digest_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, lower, upper, (int)(c[CTR_OVF_USED] != 0), d);
-  hipError_t e = hipMemcpyAsync(out4, d, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream);
-  if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  hipFree(d);
-  if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
-  return JFGPU_OK;
+  return scan_to_host(t, ScanArgs{SCAN_DIGEST, lower, upper, (int)(c[CTR_OVF_USED] != 0)}, 4, out4);
 }
 
 int jfgpu_histo(jfgpu_table* t, uint64_t base, uint64_t ceil, uint64_t inc, uint64_t* histo, uint64_t nb) {
@@ -1125,18 +1144,7 @@ int jfgpu_histo(jfgpu_table* t, uint64_t base, uint64_t ceil, uint64_t inc, uint
   if(!histo || !nb || !inc) return fail(JFGPU_E_INVALID, "bad histogram arguments");
   uint64_t c[CTR_COUNT];
   rc = check_deferred(t, c); if(rc) return rc;
-  unsigned long long* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, nb * sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(d, 0, nb * sizeof(unsigned long long), t->stream));
-  const int grid = grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1);
-  if(t->nword) hipLaunchKernelGGL(scan_nword_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->nt, 1, 0ull, ~0ull, (int)(c[CTR_OVF_USED] != 0), base, ceil, inc, nb, d, (uint32_t*)nullptr);
-  else if(t->wide) hipLaunchKernelGGL(scan_wide_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, 1, 0ull, ~0ull, (int)(c[CTR_OVF_USED] != 0), base, ceil, inc, nb, d, (uint32_t*)nullptr);
-  else hipLaunchKernelGGL(histo_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, ceil, inc, nb, (int)(c[CTR_OVF_USED] != 0), d);
-  hipError_t e = hipMemcpyAsync(histo, d, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream);
-  if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  hipFree(d);
-  if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
-  return JFGPU_OK;
+  return scan_to_host(t, ScanArgs{SCAN_HISTO, 0ull, ~0ull, (int)(c[CTR_OVF_USED] != 0), base, ceil, inc, nb}, nb, histo);
 }
 
 int jfgpu_dump_begin(jfgpu_table* t, uint64_t lower, uint64_t upper, uint64_t* n_records, uint32_t* record_bytes) {
@@ -1148,17 +1156,8 @@ int jfgpu_dump_begin(jfgpu_table* t, uint64_t lower, uint64_t upper, uint64_t* n
   uint32_t* d_cnt = nullptr;
   HIP_TRY(hipMalloc((void**)&d_cnt, nt * sizeof(uint32_t)));
   t->dump_have_ovf = c[CTR_OVF_USED] != 0;
-  if(t->nword) {
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, nt * sizeof(uint32_t), t->stream));
-    hipLaunchKernelGGL(scan_nword_kernel, dim3(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), dim3(kBlock), 0, t->stream, t->nt, 2, lower, upper,
-                       t->dump_have_ovf, 0ull, 0ull, 1ull, 1ull, (unsigned long long*)nullptr, d_cnt);
-  } else if(t->wide) {
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, nt * sizeof(uint32_t), t->stream));
-    hipLaunchKernelGGL(scan_wide_kernel, dim3(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), dim3(kBlock), 0, t->stream, t->wt, 2, lower, upper,
-                       t->dump_have_ovf, 0ull, 0ull, 1ull, 1ull, (unsigned long long*)nullptr, d_cnt);
-  } else
-  hipLaunchKernelGGL(tile_count_kernel, dim3(grid_for(t, nt)), dim3(kBlock), 0, t->stream, t->dt, lower, upper,
-                     t->dump_have_ovf, nt, d_cnt);
+  if(t->slot_words > 1) HIP_TRY(hipMemsetAsync(d_cnt, 0, nt * sizeof(uint32_t), t->stream));      // (scan_kernel adds to them; tile_count_kernel writes every one)
+  with_view(t, [&](const auto& T) { launch_scan(t, T, ScanArgs{SCAN_TILES, lower, upper, t->dump_have_ovf}, (unsigned long long*)nullptr, d_cnt); });
   std::vector<uint32_t> h(nt);
   hipError_t e = hipMemcpyAsync(h.data(), d_cnt, nt * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream);
   if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
@@ -1204,20 +1203,7 @@ int jfgpu_dump_next(jfgpu_table* t, void* out, uint64_t capacity_records, uint64
   std::vector<uint64_t> offs(ntile);
   for(uint64_t i = 0; i < ntile; ++i) offs[i] = t->dump_prefix[t0 + i] - t->dump_prefix[t0];
   HIP_TRY(hipMemcpyAsync(t->d_tile_off, offs.data(), ntile * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
-  if(t->nword) {
-    const size_t nl = ((size_t)32 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits);
-    hipLaunchKernelGGL(dump_tiles_nword_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), nl, t->stream, t->nt, t->dump_lower, t->dump_upper,
-                       t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump, key_bytes, t->out_counter_len);
-  } else if(t->wide) {
-    const size_t wl = ((size_t)16 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits);
-    hipLaunchKernelGGL(dump_tiles_wide_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), wl, t->stream, t->wt, t->dump_lower, t->dump_upper,
-                       t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump, key_bytes, t->out_counter_len);
-  } else {
-  const size_t lds = ((size_t)8 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits) + (size_t)t->g.nbytes * 2048;
-  hipLaunchKernelGGL(dump_tiles_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), lds, t->stream, t->dt, t->dump_lower,
-                     t->dump_upper, t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump, key_bytes,
-                     t->out_counter_len);
-  }
+  with_view(t, [&](const auto& T) { launch_dump(t, T, t0, ntile, key_bytes); });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, t->d_dump, nrec * rec, hipMemcpyDeviceToHost, t->stream));
   HIP_TRY(hipStreamSynchronize(t->stream));

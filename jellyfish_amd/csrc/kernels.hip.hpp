@@ -267,6 +267,36 @@ __device__ inline bool table_add_val(const DevTable& T, const uint64_t* fwd_lds,
   return false;
 }
 
+// ---- slot access per key width ------------------------------------------------------
+// What a kernel that walks a whole table needs from its view (DevTable here, WideTable in kernels_wide.hip.hpp, NTable in
+// kernels_nword.hip.hpp), so that such a kernel is written once: rehash_kernel, scan_kernel and dump_tiles_words_kernel
+// below, reshard_kernel and add_pairs_kernel in abi_comm.inl.  A specialisation has
+//   Key, Slot                        a key, and what was read of a slot
+//   geom(T)                          the table's TableGeom
+//   load(T, i, s)                    reads slot i; true when it holds a key
+//   occupied(T, i, s)                the cheaper read where one word tells (the multi-word views; the counting scans use it)
+//   count(T, s, i, have_ovf)         the full count, with the overflow side table when have_ovf
+//   key(T, s, tile_base)             the key, rebuilt through inv_tbl
+//   add_val(T, key, val)             hash_counter::add(key, val) into T
+//   owner(T, key)                    the shard that owns key under T's matrix
+//   store_key / load_key             a key as kw little-endian 64-bit words
+//   digest(T, key, c)                (the multi-word views) an entry's digest hash
+//   kSlotWords, slot_of(w), key_byte (the multi-word views, for the dump) words per slot, a slot from a copy of its words, byte b of a key
+template <class Table> struct KeyOps;
+
+template <> struct KeyOps<DevTable> {
+  typedef uint64_t Key;
+  struct Slot { uint64_t w; };
+  __device__ static const TableGeom& geom(const DevTable& T) { return T.g; }
+  __device__ static bool load(const DevTable& T, uint64_t i, Slot& s) { s.w = slot_ld(T, i); return s.w != 0; }
+  __device__ static uint64_t count(const DevTable& T, const Slot& s, uint64_t i, int have_ovf) { return full_count(T, s.w, i, have_ovf); }
+  __device__ static Key key(const DevTable& T, const Slot& s, uint64_t tile_base) { return slot_key(T.g, T.inv_tbl, s.w, tile_base); }
+  __device__ static bool add_val(const DevTable& T, Key key, uint64_t val) { return table_add_val(T, T.fwd_tbl, key, val); }
+  __device__ static uint32_t owner(const DevTable& T, Key key) { return (uint32_t)(hash_tables(T.fwd_tbl, key, T.g.nbytes) >> T.g.lsize_l); }
+  __device__ static void store_key(uint64_t* dst, Key key, uint32_t) { dst[0] = key; }
+  __device__ static Key load_key(const DevTable&, const uint64_t* keys, uint64_t i, uint32_t) { return keys[i]; }
+};
+
 __device__ inline LaneWords stage_tile(const uint8_t* __restrict__ base, int64_t tile_start, int64_t lo, int64_t hi,
                                        uint32_t* s_codes, uint32_t* s_inv) {
   const int tid = threadIdx.x;
@@ -513,14 +543,17 @@ __global__ __launch_bounds__(kBlock) void partition_scatter_kernel(DevTable T, c
 // ---- cooperative size doubling (hash_counter::double_size, hash_counter.hpp:200-238) -------------
 // Every entry of the old table is re-derived (slot -> key by the inverse tables) and inserted with its
 // full count into the new, twice as large table (one more matrix row).  Hash tables are read through
-// the caches here: growth is rare and the kernel is bound by the random inserts anyway.
-__global__ __launch_bounds__(kBlock) void rehash_kernel(DevTable old, DevTable neu, int have_ovf) {
-  const uint64_t n = 1ull << old.g.lsize_l;
+// the caches here: growth is rare and the kernel is bound by the random inserts anyway.  Every key width (KeyOps).
+template <class Table>
+__global__ __launch_bounds__(kBlock) void rehash_kernel(Table old, Table neu, int have_ovf) {
+  typedef KeyOps<Table> K;
+  const TableGeom& g = K::geom(old);
+  const uint64_t n = 1ull << g.lsize_l;
   for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t w = slot_ld(old, i);
-    if(!w) continue;
-    const uint64_t key = slot_key(old.g, old.inv_tbl, w, i & ~old.g.tile_mask);
-    table_add_val(neu, neu.fwd_tbl, key, full_count(old, w, i, have_ovf));
+    typename K::Slot s;
+    if(!K::load(old, i, s)) continue;
+    const typename K::Key key = K::key(old, s, i & ~g.tile_mask);
+    K::add_val(neu, key, K::count(old, s, i, have_ovf));
   }
 }
 
@@ -695,6 +728,127 @@ __global__ __launch_bounds__(kBlock) void dump_tiles_kernel(DevTable T, uint64_t
       uint8_t* d = dst0 + (uint64_t)i * rec;
       for(uint32_t b = 0; b < key_bytes; ++b) d[b] = (uint8_t)(key >> (8 * b));
       for(uint32_t b = 0; b < val_bytes; ++b) d[key_bytes + b] = (uint8_t)(cnt >> (8 * b));
+    }
+  }
+}
+
+// ---- the same passes over multi-word keys (WideTable, NTable) ------------------------------------------------
+// stats / histo / tile counts / content digest as one strided scan (the one-word kernels above are shaped for k <= 32:
+// tables in LDS, a privatised histogram, one block per tile).  The counting scans take KeyOps::occupied, the digest needs
+// the key and takes the whole slot.
+enum { SCAN_STATS = 0, SCAN_HISTO = 1, SCAN_TILES = 2, SCAN_DIGEST = 3 };   // out[0..3] = unique, distinct, total, max | histogram | tile_counts | digest
+template <class Table>
+__global__ __launch_bounds__(kBlock) void scan_kernel(Table T, int what, uint64_t lower, uint64_t upper, int have_ovf,
+                                                      uint64_t hbase, uint64_t hceil, uint64_t hinc, uint64_t nb,
+                                                      unsigned long long* __restrict__ out, uint32_t* __restrict__ tile_counts) {
+  typedef KeyOps<Table> K;
+  const TableGeom& g = K::geom(T);
+  const uint64_t n = 1ull << g.lsize_l;
+  uint64_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    typename K::Slot s;
+    if(!(what == SCAN_DIGEST ? K::load(T, i, s) : K::occupied(T, i, s))) continue;
+    const uint64_t c = K::count(T, s, i, have_ovf);
+    if(what == SCAN_HISTO) {
+      uint64_t b;
+      if(c < hbase) b = 0; else if(c > hceil) b = nb - 1; else b = (c - hbase) / hinc;
+      atomicAdd(&out[b], 1ull);
+      continue;
+    }
+    if(c < lower || c > upper) continue;
+    if(what == SCAN_TILES) { atomicAdd(&tile_counts[i >> g.tile_bits], 1u); continue; }
+    if(what == SCAN_DIGEST) {
+      const uint64_t h = K::digest(T, K::key(T, s, i & ~g.tile_mask), c);
+      ++a0; a1 += c; a2 += h; a3 ^= h;
+      continue;
+    }
+    a0 += (c == 1); ++a1; a2 += c; a3 = c > a3 ? c : a3;
+  }
+  if(what == SCAN_DIGEST) { digest_reduce(a0, a1, a2, a3, out); return; }
+  if(what == SCAN_STATS) {
+    for(int o = 32; o > 0; o >>= 1) {
+      a0 += __shfl_down(a0, o, 64); a1 += __shfl_down(a1, o, 64); a2 += __shfl_down(a2, o, 64);
+      const uint64_t m2 = __shfl_down(a3, o, 64); a3 = m2 > a3 ? m2 : a3;
+    }
+    if((threadIdx.x & 63) == 0) {
+      if(a0) atomicAdd(&out[0], (unsigned long long)a0);
+      if(a1) atomicAdd(&out[1], (unsigned long long)a1);
+      if(a2) atomicAdd(&out[2], (unsigned long long)a2);
+      if(a3) atomicMax(&out[3], (unsigned long long)a3);
+    }
+  }
+}
+
+// Sorted dump of slots of NW = KeyOps::kSlotWords words { lo words ..., hi }: one block per tile, bitonic sort in LDS on
+// the tag (masked hi word, then the lo words from the most significant) == (pos, key) order (mer_heap.hpp:26-30), keys
+// rebuilt through the inverse tables (read through the caches), records as binary_dumper.hpp:36-40 lays them out.
+// Dynamic LDS: tsz * 8 * NW (word q of entry i at s_w[q * tsz + i]) + tsz * 2 (slot index): 8192 x 16 B = 128 KiB + 16 KiB
+// for two-word keys, 2048 x 32 B = 64 KiB + 4 KiB for three and four.
+template <class Table>
+__global__ __launch_bounds__(kBlock) void dump_tiles_words_kernel(Table T, uint64_t lower, uint64_t upper, int have_ovf,
+                                                                  uint64_t tile0, uint64_t n_tiles, const uint64_t* __restrict__ tile_offsets,
+                                                                  uint8_t* __restrict__ out, uint32_t key_bytes, uint32_t val_bytes) {
+  typedef KeyOps<Table> K;
+  constexpr int NW = K::kSlotWords;
+  JF_DYN_LDS(s_raw);
+  const TableGeom& g = K::geom(T);
+  const uint32_t tsz = 1u << g.tile_bits;
+  uint64_t* s_w = reinterpret_cast<uint64_t*>(s_raw);
+  uint64_t* s_hi = s_w + (NW - 1) * (size_t)tsz;
+  uint16_t* s_idx = reinterpret_cast<uint16_t*>(s_w + NW * (size_t)tsz);
+  const uint64_t tagmask = g.occ_bit - 1, SENT = ~g.occ_bit;     // (a stored hi word has the occupied bit: a saturated count field over an all-ones tag is not the sentinel)
+  const uint64_t maxval = val_bytes >= 8 ? ~0ull : ((1ull << (8 * val_bytes)) - 1);
+  const uint32_t rec = key_bytes + val_bytes;
+  for(uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const uint64_t tb = (tile0 + t) << g.tile_bits;
+    __syncthreads();
+    for(uint32_t i = threadIdx.x; i < tsz; i += blockDim.x) {
+      const uint64_t* sp = &T.slots[NW * (tb + i)];
+      typename K::Slot s;
+      uint64_t kh = SENT;
+      if(K::occupied(T, tb + i, s)) {
+        const uint64_t c = K::count(T, s, tb + i, have_ovf);
+        if(c >= lower && c <= upper) kh = sp[NW - 1];
+      }
+#pragma unroll
+      for(int q = 0; q < NW - 1; ++q) s_w[q * tsz + i] = sp[q];
+      s_hi[i] = kh; s_idx[i] = (uint16_t)i;
+    }
+    __syncthreads();
+    for(uint32_t size = 2; size <= tsz; size <<= 1) {
+      for(uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+        for(uint32_t i = threadIdx.x; i < tsz / 2; i += blockDim.x) {
+          const uint32_t l = ((i & ~(stride - 1)) << 1) | (i & (stride - 1)), h = l | stride;
+          const bool up = (l & size) == 0;
+          const uint64_t ah = s_hi[l], bh = s_hi[h];
+          const uint64_t ka = ah == SENT ? SENT : (ah & tagmask), kb = bh == SENT ? SENT : (bh & tagmask);
+          bool gt = ka > kb;
+          if(ka == kb) {
+#pragma unroll
+            for(int q = NW - 2; q >= 0; --q) { const uint64_t x = s_w[q * tsz + l], y = s_w[q * tsz + h]; if(x != y) { gt = x > y; break; } }
+          }
+          if(gt == up) {
+#pragma unroll
+            for(int q = 0; q < NW; ++q) { const uint64_t x = s_w[q * tsz + l]; s_w[q * tsz + l] = s_w[q * tsz + h]; s_w[q * tsz + h] = x; }
+            const uint16_t ia = s_idx[l]; s_idx[l] = s_idx[h]; s_idx[h] = ia;
+          }
+        }
+        __syncthreads();
+      }
+    }
+    uint8_t* dst0 = out + tile_offsets[t] * rec;
+    for(uint32_t i = threadIdx.x; i < tsz; i += blockDim.x) {
+      if(s_hi[i] == SENT) continue;
+      uint64_t sl[NW];
+#pragma unroll
+      for(int q = 0; q < NW; ++q) sl[q] = s_w[q * tsz + i];
+      const typename K::Slot s = K::slot_of(sl);
+      const typename K::Key key = K::key(T, s, tb);
+      uint64_t cnt = K::count(T, s, tb + s_idx[i], have_ovf);
+      if(cnt > maxval) cnt = maxval;
+      uint8_t* dd = dst0 + (uint64_t)i * rec;
+      for(uint32_t b = 0; b < key_bytes; ++b) dd[b] = K::key_byte(key, b);
+      for(uint32_t b = 0; b < val_bytes; ++b) dd[key_bytes + b] = (uint8_t)(cnt >> (8 * b));
     }
   }
 }

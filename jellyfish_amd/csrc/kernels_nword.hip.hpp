@@ -340,123 +340,29 @@ __global__ __launch_bounds__(kBlock) void lookup_nword_kernel(NTable T, const ui
   }
 }
 
-// hash_counter::double_size: every complete slot re-inserted with its full count into the doubled table
-__global__ __launch_bounds__(kBlock) void rehash_nword_kernel(NTable old, NTable neu, int have_ovf) {
-  const DevTable od = ovf_view(old);
-  const uint64_t n = 1ull << old.N.g.lsize_l;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t* sp = &old.slots[4 * i];
-    if(!nword_complete(sp)) continue;
-    const K256 key = nword_slot_key(old, old.inv_tbl, sp, i & ~old.N.g.tile_mask);
-    nword_add_val(neu, key, nword_count_at(old, od, i, sp[3], have_ovf));
+// Slot access for the kernels that walk a whole table (KeyOps, kernels.hip.hpp).  A slot is looked at where it lies (in
+// the table, or in the dump's copy of it); only a complete one -- every word set -- holds a key, whatever the kernel.
+template <> struct KeyOps<NTable> {
+  typedef K256 Key;
+  struct Slot { const uint64_t* sp; };
+  static constexpr int kSlotWords = kNWords;
+  __device__ static const TableGeom& geom(const NTable& T) { return T.N.g; }
+  __device__ static bool load(const NTable& T, uint64_t i, Slot& s) { s.sp = &T.slots[4 * i]; return nword_complete(s.sp); }
+  __device__ static bool occupied(const NTable& T, uint64_t i, Slot& s) { return load(T, i, s); }
+  __device__ static Slot slot_of(const uint64_t* w) { Slot s; s.sp = w; return s; }
+  __device__ static uint64_t count(const NTable& T, const Slot& s, uint64_t i, int have_ovf) { return nword_count_at(T, ovf_view(T), i, s.sp[3], have_ovf); }
+  __device__ static Key key(const NTable& T, const Slot& s, uint64_t tile_base) { return nword_slot_key(T, T.inv_tbl, s.sp, tile_base); }
+  __device__ static bool add_val(const NTable& T, const Key& key, uint64_t val) { return nword_add_val(T, key, val); }
+  __device__ static uint32_t owner(const NTable& T, const Key& key) { return slot_addr(T.N.g, hash_tables_n256(T.fwd_tbl, key, T.N.g.nbytes)).shard; }
+  __device__ static void store_key(uint64_t* dst, const Key& key, uint32_t kw) { for(uint32_t q = 0; q < kw; ++q) dst[q] = key.w[q]; }
+  __device__ static Key load_key(const NTable& T, const uint64_t* keys, uint64_t i, uint32_t kw) { return load_key4(keys, i, kw, T.N.key_mask); }
+  __device__ static uint64_t digest(const NTable& T, const Key& key, uint64_t c) {
+    uint64_t h = kDigestSeed;
+    for(uint32_t q = 0; q < (T.N.g.k + 31) / 32; ++q) h = digest_mix(h ^ key.w[q]);
+    return digest_mix(h ^ c);
   }
-}
-
-// what: 0 stats (out[0..3] = unique, distinct, total, max), 1 histo, 2 per-tile record counts, 3 content digest
-__global__ __launch_bounds__(kBlock) void scan_nword_kernel(NTable T, int what, uint64_t lower, uint64_t upper, int have_ovf,
-                                                            uint64_t hbase, uint64_t hceil, uint64_t hinc, uint64_t nb,
-                                                            unsigned long long* __restrict__ out, uint32_t* __restrict__ tile_counts) {
-  const TableGeom& g = T.N.g;
-  const DevTable d = ovf_view(T);
-  const uint64_t n = 1ull << g.lsize_l;
-  uint64_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t* sp = &T.slots[4 * i];
-    if(!nword_complete(sp)) continue;
-    const uint64_t c = nword_count_at(T, d, i, sp[3], have_ovf);
-    if(what == 1) {
-      uint64_t b;
-      if(c < hbase) b = 0; else if(c > hceil) b = nb - 1; else b = (c - hbase) / hinc;
-      atomicAdd(&out[b], 1ull);
-      continue;
-    }
-    if(c < lower || c > upper) continue;
-    if(what == 2) { atomicAdd(&tile_counts[i >> g.tile_bits], 1u); continue; }
-    if(what == 3) {
-      const K256 key = nword_slot_key(T, T.inv_tbl, sp, i & ~g.tile_mask);
-      uint64_t h = kDigestSeed;
-      for(uint32_t q = 0; q < (g.k + 31) / 32; ++q) h = digest_mix(h ^ key.w[q]);
-      h = digest_mix(h ^ c);
-      ++a0; a1 += c; a2 += h; a3 ^= h;
-      continue;
-    }
-    a0 += (c == 1); ++a1; a2 += c; a3 = c > a3 ? c : a3;
-  }
-  if(what == 3) { digest_reduce(a0, a1, a2, a3, out); return; }
-  if(what == 0) {
-    for(int o = 32; o > 0; o >>= 1) {
-      a0 += __shfl_down(a0, o, 64); a1 += __shfl_down(a1, o, 64); a2 += __shfl_down(a2, o, 64);
-      const uint64_t m2 = __shfl_down(a3, o, 64); a3 = m2 > a3 ? m2 : a3;
-    }
-    if((threadIdx.x & 63) == 0) {
-      if(a0) atomicAdd(&out[0], (unsigned long long)a0);
-      if(a1) atomicAdd(&out[1], (unsigned long long)a1);
-      if(a2) atomicAdd(&out[2], (unsigned long long)a2);
-      if(a3) atomicMax(&out[3], (unsigned long long)a3);
-    }
-  }
-}
-
-// Sorted dump: one block per tile, bitonic sort in LDS on the tag (hi tag bits, lo2, lo1, lo0) == (pos, key) order
-// (mer_heap.hpp:26-30), keys rebuilt through the inverse tables, records as binary_dumper.hpp:36-40 lays them out.
-__global__ __launch_bounds__(kBlock) void dump_tiles_nword_kernel(NTable T, uint64_t lower, uint64_t upper, int have_ovf,
-                                                                  uint64_t tile0, uint64_t n_tiles, const uint64_t* __restrict__ tile_offsets,
-                                                                  uint8_t* __restrict__ out, uint32_t key_bytes, uint32_t val_bytes) {
-  JF_DYN_LDS(s_raw);
-  const TableGeom& g = T.N.g;
-  const uint32_t tsz = 1u << g.tile_bits;
-  uint64_t* s_w = reinterpret_cast<uint64_t*>(s_raw);                    // [4][tsz]: word q of entry i at s_w[q * tsz + i]
-  uint16_t* s_idx = reinterpret_cast<uint16_t*>(s_w + 4 * (size_t)tsz);
-  const DevTable d = ovf_view(T);
-  const uint64_t tagmask = g.occ_bit - 1, SENT = ~g.occ_bit;     // (a stored hi word has the occupied bit: a saturated count field over an all-ones tag is not the sentinel)
-  const uint64_t maxval = val_bytes >= 8 ? ~0ull : ((1ull << (8 * val_bytes)) - 1);
-  const uint32_t rec = key_bytes + val_bytes;
-  for(uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    const uint64_t tb = (tile0 + t) << g.tile_bits;
-    __syncthreads();
-    for(uint32_t i = threadIdx.x; i < tsz; i += blockDim.x) {
-      const uint64_t* sp = &T.slots[4 * (tb + i)];
-      uint64_t kh = SENT;
-      if(nword_complete(sp)) {
-        const uint64_t c = nword_count_at(T, d, tb + i, sp[3], have_ovf);
-        if(c >= lower && c <= upper) kh = sp[3];
-      }
-      s_w[3 * tsz + i] = kh; s_w[i] = sp[0]; s_w[tsz + i] = sp[1]; s_w[2 * tsz + i] = sp[2]; s_idx[i] = (uint16_t)i;
-    }
-    __syncthreads();
-    for(uint32_t size = 2; size <= tsz; size <<= 1)
-      for(uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-        for(uint32_t i = threadIdx.x; i < tsz / 2; i += blockDim.x) {
-          const uint32_t l = ((i & ~(stride - 1)) << 1) | (i & (stride - 1)), h = l | stride;
-          const bool up = (l & size) == 0;
-          const uint64_t ah = s_w[3 * tsz + l], bh = s_w[3 * tsz + h];
-          const uint64_t ka = ah == SENT ? SENT : (ah & tagmask), kb = bh == SENT ? SENT : (bh & tagmask);
-          bool gt = ka > kb;
-          if(ka == kb) {
-            gt = false;
-            for(int q = 2; q >= 0; --q) { const uint64_t x = s_w[q * tsz + l], y = s_w[q * tsz + h]; if(x != y) { gt = x > y; break; } }
-          }
-          if(gt == up) {
-            for(int q = 0; q < 4; ++q) { const uint64_t x = s_w[q * tsz + l]; s_w[q * tsz + l] = s_w[q * tsz + h]; s_w[q * tsz + h] = x; }
-            const uint16_t ia = s_idx[l]; s_idx[l] = s_idx[h]; s_idx[h] = ia;
-          }
-        }
-        __syncthreads();
-      }
-    uint8_t* dst0 = out + tile_offsets[t] * rec;
-    for(uint32_t i = threadIdx.x; i < tsz; i += blockDim.x) {
-      const uint64_t hi = s_w[3 * tsz + i];
-      if(hi == SENT) continue;
-      const uint64_t sl[4] = {s_w[i], s_w[tsz + i], s_w[2 * tsz + i], hi};
-      const K256 key = nword_slot_key(T, T.inv_tbl, sl, tb);
-      uint64_t cnt = nword_count_at(T, d, tb + s_idx[i], hi, have_ovf);
-      if(cnt > maxval) cnt = maxval;
-      uint8_t* dd = dst0 + (uint64_t)i * rec;
-      for(uint32_t b = 0; b < key_bytes; ++b) dd[b] = (uint8_t)(key.w[b >> 3] >> (8 * (b & 7)));
-      for(uint32_t b = 0; b < val_bytes; ++b) dd[key_bytes + b] = (uint8_t)(cnt >> (8 * b));
-    }
-  }
-}
+  __device__ static uint8_t key_byte(const Key& key, uint32_t b) { return (uint8_t)(key.w[b >> 3] >> (8 * (b & 7))); }
+};
 
 // hash_counter::update_add on encoded keys of kw words, val == 1: the receive side of the exchange in the UPDATE pass of
 // count --if over shards (the two-word twin is update_keys_wide_kernel).  A key of another shard is counted as misrouted.

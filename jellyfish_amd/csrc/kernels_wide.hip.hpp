@@ -364,144 +364,36 @@ __global__ __launch_bounds__(kBlock) void lookup_wide_kernel(WideTable T, const 
   }
 }
 
-// hash_counter::double_size for two-word keys: every occupied slot is decoded and re-inserted with its full
-// count into the doubled table (new matrix, one more row).  Hash tables are read through the caches.
-__global__ __launch_bounds__(kBlock) void rehash_wide_kernel(WideTable old, WideTable neu, int have_ovf) {
-  const TableGeom& g = old.W.g;
-  const DevTable od = ovf_view(old);
-  const uint64_t n = 1ull << g.lsize_l;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t hi = old.slots[2 * i + 1];
-    if(!hi) continue;
-    const uint64_t lo = old.slots[2 * i];
-    if(!lo) continue;                                    // hi claimed, never completed: holds no key
-    const u128 key = wide_slot_key(old, old.inv_tbl, lo, hi, i & ~g.tile_mask);
-    uint64_t c = slot_count(g, hi);
-    if(have_ovf) c += ovf_get(od, i) << g.cnt_bits;
-    wide_add_val(neu, neu.fwd_tbl, key, c);
+// Slot access for the kernels that walk a whole table (KeyOps, kernels.hip.hpp): hash_counter::double_size, the scans,
+// the sorted dump and the redistribution between shards are written once there.  Hash tables are read through the caches.
+template <> struct KeyOps<WideTable> {
+  typedef u128 Key;
+  struct Slot { uint64_t lo, hi; };
+  static constexpr int kSlotWords = 2;
+  __device__ static const TableGeom& geom(const WideTable& T) { return T.W.g; }
+  // stats / histo / tile counts / dump: only the hi word (count + occupancy) matters, the lo word is never touched
+  __device__ static bool occupied(const WideTable& T, uint64_t i, Slot& s) { s.lo = 0; s.hi = T.slots[2 * i + 1]; return s.hi != 0; }
+  __device__ static bool load(const WideTable& T, uint64_t i, Slot& s) {
+    if(!occupied(T, i, s)) return false;
+    s.lo = T.slots[2 * i];
+    return s.lo != 0;                                    // hi claimed, never completed: holds no key
   }
-}
-
-// stats / histo / tile_count: only the hi word (count + occupancy) matters -> one strided scan.
-// what: 0 stats (out[0..3] = unique, distinct, total, max), 1 histo, 2 per-tile record counts
-__global__ __launch_bounds__(kBlock) void scan_wide_kernel(WideTable T, int what, uint64_t lower, uint64_t upper, int have_ovf,
-                                                           uint64_t hbase, uint64_t hceil, uint64_t hinc, uint64_t nb,
-                                                           unsigned long long* __restrict__ out, uint32_t* __restrict__ tile_counts) {
-  const TableGeom& g = T.W.g;
-  const DevTable d = ovf_view(T);
-  const uint64_t n = 1ull << g.lsize_l;
-  uint64_t uniq = 0, dist = 0, tot = 0, mx = 0;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t hi = T.slots[2 * i + 1];
-    if(!hi) continue;
-    uint64_t c = slot_count(g, hi);
-    if(have_ovf) c += ovf_get(d, i) << g.cnt_bits;
-    if(what == 1) {
-      uint64_t b;
-      if(c < hbase) b = 0; else if(c > hceil) b = nb - 1; else b = (c - hbase) / hinc;
-      atomicAdd(&out[b], 1ull);
-      continue;
-    }
-    if(c < lower || c > upper) continue;
-    if(what == 2) { atomicAdd(&tile_counts[i >> g.tile_bits], 1u); continue; }
-    uniq += (c == 1); ++dist; tot += c; mx = c > mx ? c : mx;
+  __device__ static Slot slot_of(const uint64_t* w) { Slot s; s.lo = w[0]; s.hi = w[1]; return s; }
+  __device__ static uint64_t count(const WideTable& T, const Slot& s, uint64_t i, int have_ovf) {
+    uint64_t c = slot_count(T.W.g, s.hi);
+    if(have_ovf) c += ovf_get(ovf_view(T), i) << T.W.g.cnt_bits;
+    return c;
   }
-  if(what == 0) {
-    for(int o = 32; o > 0; o >>= 1) {
-      uniq += __shfl_down(uniq, o, 64); dist += __shfl_down(dist, o, 64); tot += __shfl_down(tot, o, 64);
-      const uint64_t m2 = __shfl_down(mx, o, 64); mx = m2 > mx ? m2 : mx;
-    }
-    if((threadIdx.x & 63) == 0) {
-      if(uniq) atomicAdd(&out[0], (unsigned long long)uniq);
-      if(dist) atomicAdd(&out[1], (unsigned long long)dist);
-      if(tot) atomicAdd(&out[2], (unsigned long long)tot);
-      if(mx) atomicMax(&out[3], (unsigned long long)mx);
-    }
+  __device__ static Key key(const WideTable& T, const Slot& s, uint64_t tile_base) { return wide_slot_key(T, T.inv_tbl, s.lo, s.hi, tile_base); }
+  __device__ static bool add_val(const WideTable& T, Key key, uint64_t val) { return wide_add_val(T, T.fwd_tbl, key, val); }
+  __device__ static uint32_t owner(const WideTable& T, Key key) { return slot_addr(T.W.g, hash_tables_wide(T.fwd_tbl, key, T.W.g.nbytes)).shard; }
+  __device__ static void store_key(uint64_t* dst, Key key, uint32_t) { dst[0] = (uint64_t)key; dst[1] = (uint64_t)(key >> 64); }
+  __device__ static Key load_key(const WideTable&, const uint64_t* keys, uint64_t i, uint32_t) { return load_key2(keys, i, ~(u128)0); }   // (as they come: a pair's key was made by store_key or by the caller)
+  __device__ static uint64_t digest(const WideTable&, Key key, uint64_t c) {
+    return digest_mix(digest_mix(digest_mix(kDigestSeed ^ (uint64_t)key) ^ (uint64_t)(key >> 64)) ^ c);
   }
-}
-
-// Content digest of a two-word-key table (see digest_kernel in kernels.hip.hpp).
-__global__ __launch_bounds__(kBlock) void digest_wide_kernel(WideTable T, uint64_t lower, uint64_t upper, int have_ovf,
-                                                             unsigned long long* __restrict__ out) {
-  const TableGeom& g = T.W.g;
-  const DevTable d = ovf_view(T);
-  const uint64_t n = 1ull << g.lsize_l;
-  uint64_t cnt = 0, tot = 0, sum = 0, x = 0;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t hi = T.slots[2 * i + 1];
-    if(!hi) continue;
-    const uint64_t lo = T.slots[2 * i];
-    if(!lo) continue;
-    uint64_t c = slot_count(g, hi);
-    if(have_ovf) c += ovf_get(d, i) << g.cnt_bits;
-    if(c < lower || c > upper) continue;
-    const u128 key = wide_slot_key(T, T.inv_tbl, lo, hi, i & ~g.tile_mask);
-    const uint64_t h = digest_mix(digest_mix(digest_mix(kDigestSeed ^ (uint64_t)key) ^ (uint64_t)(key >> 64)) ^ c);
-    ++cnt; tot += c; sum += h; x ^= h;
-  }
-  digest_reduce(cnt, tot, sum, x, out);
-}
-
-// Sorted dump of 128-bit slots: one block per tile, bitonic sort on (tag_hi, tag_lo) in LDS
-// (8192 x 16 B = 128 KiB + 16 KiB of slot indices), inverse tables through the caches.
-__global__ __launch_bounds__(kBlock) void dump_tiles_wide_kernel(WideTable T, uint64_t lower, uint64_t upper, int have_ovf,
-                                                                 uint64_t tile0, uint64_t n_tiles,
-                                                                 const uint64_t* __restrict__ tile_offsets,
-                                                                 uint8_t* __restrict__ out, uint32_t key_bytes, uint32_t val_bytes) {
-  JF_DYN_LDS(s_raw);
-  const TableGeom& g = T.W.g;
-  const uint32_t tsz = 1u << g.tile_bits;
-  uint64_t* s_hi = reinterpret_cast<uint64_t*>(s_raw);
-  uint64_t* s_lo = s_hi + tsz;
-  uint16_t* s_idx = reinterpret_cast<uint16_t*>(s_lo + tsz);
-  const DevTable d = ovf_view(T);
-  const uint64_t tagmask = g.occ_bit - 1, SENT = ~g.occ_bit;     // (a stored hi word has the occupied bit: a saturated count field over an all-ones tag is not the sentinel)
-  const uint64_t maxval = val_bytes >= 8 ? ~0ull : ((1ull << (8 * val_bytes)) - 1);
-  const uint32_t rec = key_bytes + val_bytes;
-  for(uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    const uint64_t tb = (tile0 + t) << g.tile_bits;
-    __syncthreads();
-    for(uint32_t i = threadIdx.x; i < tsz; i += blockDim.x) {
-      uint64_t hi = T.slots[2 * (tb + i) + 1], lo = T.slots[2 * (tb + i)];
-      uint64_t kh = SENT;
-      if(hi) {
-        uint64_t c = slot_count(g, hi);
-        if(have_ovf) c += ovf_get(d, tb + i) << g.cnt_bits;
-        if(c >= lower && c <= upper) kh = hi;
-      }
-      s_hi[i] = kh; s_lo[i] = lo; s_idx[i] = (uint16_t)i;
-    }
-    __syncthreads();
-    for(uint32_t size = 2; size <= tsz; size <<= 1) {
-      for(uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-        for(uint32_t i = threadIdx.x; i < tsz / 2; i += blockDim.x) {
-          const uint32_t l = ((i & ~(stride - 1)) << 1) | (i & (stride - 1)), h = l | stride;
-          const bool up = (l & size) == 0;
-          const uint64_t ah = s_hi[l], bh = s_hi[h], al = s_lo[l], bl = s_lo[h];
-          const uint64_t ka = ah == SENT ? SENT : (ah & tagmask), kb = bh == SENT ? SENT : (bh & tagmask);
-          const bool gt = ka > kb || (ka == kb && al > bl);
-          if(gt == up) {
-            s_hi[l] = bh; s_hi[h] = ah; s_lo[l] = bl; s_lo[h] = al;
-            const uint16_t ia = s_idx[l]; s_idx[l] = s_idx[h]; s_idx[h] = ia;
-          }
-        }
-        __syncthreads();
-      }
-    }
-    uint8_t* dst0 = out + tile_offsets[t] * rec;
-    for(uint32_t i = threadIdx.x; i < tsz; i += blockDim.x) {
-      const uint64_t hi = s_hi[i];
-      if(hi == SENT) continue;
-      const u128 key = wide_slot_key(T, T.inv_tbl, s_lo[i], hi, tb);
-      uint64_t cnt = slot_count(g, hi);
-      if(have_ovf) cnt += ovf_get(d, tb + s_idx[i]) << g.cnt_bits;
-      if(cnt > maxval) cnt = maxval;
-      uint8_t* dd = dst0 + (uint64_t)i * rec;
-      for(uint32_t b = 0; b < key_bytes; ++b) dd[b] = (uint8_t)(key >> (8 * b));
-      for(uint32_t b = 0; b < val_bytes; ++b) dd[key_bytes + b] = (uint8_t)(cnt >> (8 * b));
-    }
-  }
-}
+  __device__ static uint8_t key_byte(Key key, uint32_t b) { return (uint8_t)(key >> (8 * b)); }
+};
 
 // ---- multi-GPU: a contract buffer's two-word k-mers grouped by owner (abi_comm.inl, key path) -------------------------
 // The two passes of kernels.hip.hpp's partition_count / partition_scatter kernels for 128-bit keys: out receives two

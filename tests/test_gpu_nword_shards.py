@@ -3,7 +3,7 @@
 Every rank routes the 256-bit k-mers of its input by owner (partition_count / scatter_nword_kernel), a message carries
 ceil(2k / 64) words per k-mer (3 for k <= 96, 4 above), receivers insert with the four-word claim (add_keys_nword_kernel)
 or, in the UPDATE pass of `count --if`, count what is present (update_keys_nword_kernel).  Shards grow together
-(reshard_nword_kernel, add_pairs_nword_kernel), and a step is cut into pieces whose send buffers stay under a byte budget
+(reshard_kernel<NTable>, add_pairs_kernel<NTable>), and a step is cut into pieces whose send buffers stay under a byte budget
 (JFGPU_COMM_PIECE_BYTES).  What the shards hold is what one table holds."""
 import hashlib
 import json
@@ -133,8 +133,8 @@ def test_sharded_nword_keys_equal_single_table(gpu, monkeypatch, k, canonical, w
 
 @pytest.mark.parametrize("k,world", [(100, 2), (65, 2), (65, 4), (100, 4)])
 def test_nword_shards_grow_together(gpu, k, world):
-    """Shards created at the minimum size double together (comm_grow: reshard_nword_kernel, pairs of kw key words and a
-    count through the key path's exchange, add_pairs_nword_kernel): every shard ends at the same lsize, at least two
+    """Shards created at the minimum size double together (comm_grow: reshard_kernel<NTable>, pairs of kw key words and a
+    count through the key path's exchange, add_pairs_kernel<NTable>): every shard ends at the same lsize, at least two
     doublings above where it started, under one matrix; every key sits on the shard its position names; no key is on two
     shards; the union is the oracle's map."""
     rng = random.Random(k * 11 + world)

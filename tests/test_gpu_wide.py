@@ -77,6 +77,12 @@ def test_wide_content_digest(gpu):
             t.sync()
             keys, cnts = gpu.decode_records(t.dump_records(), k, t.info.out_counter_len)
             assert t.digest() == gpu.digest_of(keys, cnts)
+            if k == 33:                                        # ... and of the records whose count lies in a window
+                t.add_keys(keys[:5], val=2)                    # (N-rich input: every k-mer occurs once)
+                keys, cnts = gpu.decode_records(t.dump_records(), k, t.info.out_counter_len)
+                sel = (cnts >= 2) & (cnts <= 3)
+                assert sel.any() and not sel.all()
+                assert t.digest(2, 3) == gpu.digest_of(keys[sel], cnts[sel])
 
 
 def test_wide_add_keys_and_overflow(gpu):
@@ -252,6 +258,14 @@ def test_keys_of_three_and_four_words(gpu, k, canonical, n, alphabet):
         kk, cc = gpu.decode_records(t.dump_records(chunk_records=1 << 16), k, t.info.out_counter_len)
         assert {tuple(r): c for r, c in zip(kk.tolist(), cc.tolist())} == exp
         assert t.digest() == gpu.digest_of(keys, cnt)
+        base, inc, h = t.histo(1, 100000, 1)
+        ref = {}
+        for v in exp.values():
+            ref[v] = ref.get(v, 0) + 1
+        assert {base + i * inc: int(c) for i, c in enumerate(h) if c} == ref
+        win = [v for v in exp.values() if 2 <= v <= 3]
+        st = t.stats(2, 3)
+        assert (st.unique, st.distinct, st.total, st.max_count) == (0, len(win), sum(win), max(win, default=0))
         if len(kk) > 1:
             pos = O.matrix_times(t.matrix(), t.info.lsize, 2 * k, kk[:4000])
             pk = [(p,) + tuple(reversed(r)) for p, r in zip(pos.tolist(), kk[:4000].tolist())]
@@ -266,6 +280,47 @@ def test_keys_of_three_and_four_words(gpu, k, canonical, n, alphabet):
             assert new.tolist() == [0] * 20 + [1] * len(absent[:5])
             vals, found = t.lookup(kk[:20])
             assert vals.tolist() == [int(c) + 2 ** 40 + 1 for c in cc[:20]]
+
+
+def test_large_values_survive_the_doubling_of_a_four_word_table(gpu):
+    """k = 100 with a 2^12 size hint, as test_wide_table_grows_like_the_reference does for two-word keys: a few keys carry
+    a value beyond the in-slot count field before the table doubles, so the overflow side table is read by rehash_kernel
+    and, afterwards, by the scans (stats, histo, windowed stats, digest), the dump and the look-up."""
+    k, n, big = 100, 30000, 2 ** 60            # (200 key bits leave 53 count bits at 2^12 slots and more as it grows: 2^50 would fit)
+    rng = random.Random(k + n)
+    seq = rnd_seq(rng, n, "ACGT")
+    exp = oracle_map(seq, k, True)
+    with gpu.Table(k, 1 << 12, canonical=True, out_counter_len=8) as t:
+        first = t.info.lsize
+        third = len(seq) // 3
+        t.count_ascii(seq[:third])
+        t.sync()
+        assert t.info.val_len < 60
+        some = np.array(list(oracle_map(seq[:third], k, True).keys())[:5], dtype=np.uint64)
+        assert not t.add_keys(some, val=big, want_new=True).any()
+        t.sync()
+        with_big = t.info.lsize                                # (the first third has doubled the table already)
+        t.count_ascii(seq[third - (k - 1):2 * third])
+        t.count_ascii(seq[2 * third - (k - 1):])
+        t.sync()
+        assert with_big > first and t.info.lsize > with_big and (1 << t.info.lsize) >= len(exp) and t.info.val_len < 60
+        want = dict(exp)
+        for key in some.tolist():
+            want[tuple(key)] += big
+        kk, cc = gpu.decode_records(t.dump_records(chunk_records=1 << 16), k, 8)
+        assert {tuple(r): c for r, c in zip(kk.tolist(), cc.tolist())} == want
+        vals, found = t.lookup(some)
+        assert found.all() and vals.tolist() == [want[tuple(x)] for x in some.tolist()]
+        st = t.stats()
+        assert (st.distinct, st.total, st.max_count) == (len(exp), sum(want.values()), max(want.values()))
+        st = t.stats(big, 2 ** 64 - 1)
+        assert (st.distinct, st.total) == (5, sum(v for v in want.values() if v >= big))
+        base, inc, h = t.histo(1, 100000, 1)
+        assert int(h[-1]) == 5 and int(h.sum()) == len(exp)
+        wk = np.array(list(want.keys()), dtype=np.uint64)
+        wc = np.array(list(want.values()), dtype=np.uint64)
+        assert t.digest() == gpu.digest_of(wk, wc)
+        assert t.digest(big, 2 ** 64 - 1) == gpu.digest_of(wk[wc >= big], wc[wc >= big])
 
 
 @pytest.mark.parametrize("k", [35, 21, 100])
@@ -377,8 +432,8 @@ def test_sharded_two_word_keys_equal_single_table(gpu, monkeypatch, k, world, ma
 @pytest.mark.parametrize("k,world", [(40, 2), (48, 4), (33, 1)])
 def test_two_word_shards_grow_together(gpu, k, world):
     """hash_counter::double_size (hash_counter.hpp:200-238) for sharded tables of two-word keys: shards created far too
-    small double together (abi_comm.inl: comm_grow -- reshard_wide_kernel, pairs of (two key words, count) through the
-    key path's exchange, add_pairs_wide_kernel).  What the shards hold afterwards is what one table that grew on its own
+    small double together (abi_comm.inl: comm_grow -- reshard_kernel<WideTable>, pairs of (two key words, count) through the
+    key path's exchange, add_pairs_kernel<WideTable>).  What the shards hold afterwards is what one table that grew on its own
     holds: the same k-mers with the same counts, every k-mer on the shard its position names, nothing lost in transit."""
     rng = random.Random(k * 11 + world)
     steps = [[rnd_seq(rng, rng.choice([20000, 50000, 80000]), "ACGT") + b"N" + rnd_seq(rng, 300, "ACGTN") for _ in range(world)] for _step in range(4)]

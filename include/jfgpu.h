@@ -433,8 +433,9 @@ int  jfgpu_profile_spans(jfgpu_table* t, int* which, double* ms, size_t cap, siz
  * overflow, runs of one k-mer), 6 / 7 items placed / items past rank 3 in the sampling launch of the last flush that
  * sampled (host_partition.inl), 8 flushes that ran the plain tile kernel, 9 flushes that ran the HEAVY one, 10-13 launches
  * of the second partition level by kernel (loader / storer rings, shared rings, sort-based single pass, exact count +
- * scatter), 14 / 15 launches of the first level (ring kernel / any other). */
-#define JFGPU_N_COUNTERS 16
+ * scatter), 14 / 15 launches of the first level (ring kernel / any other), 16 launches of the tile kernel's instantiation
+ * for hole-free regions (the output of the loader / storer rings). */
+#define JFGPU_N_COUNTERS 17
 int  jfgpu_get_counters(jfgpu_table* t, uint64_t* out, uint32_t n);
 /* Synthetic reads: n_reads records of read_len uniform iid bases, each followed by
  * one 'N' separator (the contract buffer the parser would produce for a FASTA of

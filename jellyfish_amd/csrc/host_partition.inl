@@ -105,9 +105,12 @@ int trace_strag_lists(hipStream_t stream, const uint32_t* d_n, uint32_t n_lists,
 constexpr uint32_t kG2Blocks = 4;      // workgroups per bucket of the single-pass P2 kernels that share regions
 bool p2_rings_roles(const jfgpu_table* t, uint32_t b2e, uint32_t nbk) { return t->tun.p2_ring != 3 && nbk >= 2 * (uint32_t)t->n_cu && (b2e == 10 || b2e == 9); }
 bool p2_rings_fit(const jfgpu_table* t, uint32_t b2e, uint32_t nbk) { return t->tun.p2_ring && (b2e == 10 || p2_rings_roles(t, b2e, nbk)); }
+// *dense: the regions written hold items only (the loader / storer kernel ran: one writer per region, which ends it
+// exactly behind its last item; what the straggler kernel appends are items too).
 int launch_p2_rings(jfgpu_table* t, uint32_t b2e, uint32_t tag_bits, const SegList& S1, uint32_t cap2, unsigned int* d_gcur2, uint32_t n_dest, uint32_t* out_v,
-                    uint32_t b0, uint32_t nbk, bool rt) {
+                    uint32_t b0, uint32_t nbk, bool rt, bool* dense) {
   const bool roles = p2_rings_roles(t, b2e, nbk);
+  *dense = roles;
   const uint32_t n_lists = roles ? nbk : kG2Blocks * nbk;
   if(!t->d_strag2 || t->strag2_lists < n_lists) {
     if(t->d_strag2) { hipFree(t->d_strag2); hipFree(t->d_strag2_n); t->d_strag2 = nullptr; t->d_strag2_n = nullptr; }
@@ -409,12 +412,21 @@ int flush_sizes(jfgpu_table* t, FlushSizes& fs) {
 // ---- the tile insert of one-word keys (kernels_tile.hip.hpp) --------------------------------------------------------
 // One instantiation of tile_rank_insert_kernel over tiles [tile0, tile0 + TPB * ntile): HV the HEAVY variant, SM the plain
 // one with its two sample counters on.
-template <typename ITEM, typename SLOT, int TPB, bool HV, bool SM>
-void launch_tile_rank_variant(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, hipStream_t ts) {
+// HL: the hole-aware instantiation.  The one for hole-free regions (SegList::dense) exists where such regions do: 4-byte
+// items into pairs of tiles, the plain kernel (HEAVY keeps the hole-aware code on both kinds of input).
+template <typename ITEM, typename SLOT, int TPB, bool HV, bool SM, bool HL>
+void launch_tile_rank_inst(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, hipStream_t ts) {
   const size_t lds = tile_rank_lds(sizeof(SLOT), t->g.tile_bits, TPB);
   const dim3 grid((unsigned)std::min<uint64_t>(ntile, (uint64_t)t->n_cu * 16)), block(kTileBlock);
-  if(t->returning) hipLaunchKernelGGL((tile_rank_insert_kernel<ITEM, true, SLOT, TPB, kTileBlock, HV, SM>), grid, block, lds, ts, t->dt, S, tile0, ntile);
-  else             hipLaunchKernelGGL((tile_rank_insert_kernel<ITEM, false, SLOT, TPB, kTileBlock, HV, SM>), grid, block, lds, ts, t->dt, S, tile0, ntile);
+  if(t->returning) hipLaunchKernelGGL((tile_rank_insert_kernel<ITEM, true, SLOT, TPB, kTileBlock, HV, SM, HL>), grid, block, lds, ts, t->dt, S, tile0, ntile);
+  else             hipLaunchKernelGGL((tile_rank_insert_kernel<ITEM, false, SLOT, TPB, kTileBlock, HV, SM, HL>), grid, block, lds, ts, t->dt, S, tile0, ntile);
+}
+template <typename ITEM, typename SLOT, int TPB, bool HV, bool SM>
+void launch_tile_rank_variant(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, hipStream_t ts) {
+  if constexpr(sizeof(ITEM) == 4 && TPB == 2 && !HV) {
+    if(S.n == 1 && S.sh[0] == 1 && S.dense[0]) { ++t->n_tile_dense; launch_tile_rank_inst<ITEM, SLOT, TPB, HV, SM, false>(t, S, tile0, ntile, ts); return; }
+  }
+  launch_tile_rank_inst<ITEM, SLOT, TPB, HV, SM, true>(t, S, tile0, ntile, ts);
 }
 // Which instantiation (plain, or HEAVY for high-coverage input) is decided from the flush itself: the first 64th of a
 // large launch's units goes through the plain kernel with its counters on, the host reads them (one wait inside the
@@ -535,7 +547,7 @@ int part_flush_t(jfgpu_table* t) {
       // whose owners ask for the next reservation a round ahead -- and the holes behind the blocks' last units
       const uint64_t mean = total / n_dest, strand = (uint64_t)kG2Single * kGran * (sizeof(ITEM) == 4 && t->tun.p2_ring ? 2 : 1) + (sizeof(ITEM) == 4 && t->tun.p2_ring ? kGran : 0);
       // ... except with the loader / storer kernel: one workgroup owns a bucket's regions, nothing is reserved, a region
-      // loses at most its last partial unit -- worth it from a few units per destination (a 155 Mbp sample in the
+      // ends behind its last item and loses nothing -- worth it from a few units per destination (a 155 Mbp sample in the
       // metric's 2^34-slot table takes the timed job's kernels: bench.py's digest check against the reference)
       const bool roles_geom = sizeof(ITEM) == 4 && pair && p2_rings_fit(t, t->pg.b2 - 1, nb1) && p2_rings_roles(t, t->pg.b2 - 1, nb1);
       if(mean >= (roles_geom ? 32 : 8 * strand) || t->tun.p2_single > 1) {
@@ -637,10 +649,11 @@ int part_flush_t(jfgpu_table* t) {
           const uint64_t d0 = (uint64_t)b0 << pg2.b2, nd = (uint64_t)nbk << pg2.b2;
           // destination d of the whole table sits at d * cap2 of a buffer that only holds this group's: shifted base
           ITEM* out_v = out2 - (share_groups ? (int64_t)d0 * (int64_t)cap2 : 0);
+          bool dense = false;                                // the regions of this group hold no holes (SegList::dense)
           if constexpr(sizeof(ITEM) == 4) {
             const size_t lds = (size_t)kPBlock * kP2PairPer * sizeof(ITEM);
             if(p2_rings_fit(t, pg2.b2, nbk) && (all_granule || p2_rings_roles(t, pg2.b2, nbk))) {
-              const int rc_ = launch_p2_rings(t, pg2.b2, p2_tag_bits, S1, cap2, d_gcur2, (uint32_t)n_dest, (uint32_t*)out_v, b0, nbk, rt);
+              const int rc_ = launch_p2_rings(t, pg2.b2, p2_tag_bits, S1, cap2, d_gcur2, (uint32_t)n_dest, (uint32_t*)out_v, b0, nbk, rt, &dense);
               if(rc_) return rc_;
             } else {
               ++t->n_p2_sort;
@@ -662,7 +675,7 @@ int part_flush_t(jfgpu_table* t) {
           if(n_groups == 1) hipLaunchKernelGGL(granule_finish_kernel, dim3(1024), dim3(256), 0, t->stream, d_gcur2, cap2, (uint32_t)n_dest, d_off2);
           else hipLaunchKernelGGL(granule_finish_range_kernel, dim3(256), dim3(256), 0, t->stream, d_gcur2, cap2, (uint32_t)n_dest, d_off2, (uint32_t)d0, (uint32_t)nd);
           SegList S2; memset(&S2, 0, sizeof S2);
-          S2.n = 1; S2.items[0] = out_v; S2.off[0] = d_off2 + 2 * d0; S2.sh[0] = 1;     // offsets from the group's first destination, items absolute
+          S2.n = 1; S2.items[0] = out_v; S2.off[0] = d_off2 + 2 * d0; S2.sh[0] = 1; S2.dense[0] = dense;     // offsets from the group's first destination, items absolute
           hipStream_t ts = t->stream;
           if(share_groups) {    // one stream, P2 and T alternate (the next group overwrites the regions): timed per group
             uint64_t gtot = 0; for(uint32_t j = b0; j < b0 + nbk; ++j) gtot += bucket_tot[j];

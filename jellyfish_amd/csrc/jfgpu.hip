@@ -87,7 +87,7 @@ struct jfgpu_table {
   // count --bc: the cache of admitted k-mers (kernels_bloom.hip.hpp) -- 0 undecided, 1 on, -1 off; decided from the first
   // filtered batches (host_partition.inl: bloom_cache_decide), dropped when the counter is detached
   uint64_t* d_bcache = nullptr; int bcache_state = 0; uint64_t mers_seen = 0;
-  uint64_t n_p2_roles = 0, n_p2_ring = 0, n_p2_sort = 0, n_p2_exact = 0, n_p1_ring = 0, n_p1_other = 0;
+  uint64_t n_p2_roles = 0, n_p2_ring = 0, n_p2_sort = 0, n_p2_exact = 0, n_p1_ring = 0, n_p1_other = 0, n_tile_dense = 0;
   uint64_t ovf_failed_need = 0;                  // the side-table size whose allocation failed (not retried per batch)
   bool returning = false;
   uint32_t out_counter_len = 4;
@@ -757,13 +757,18 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
     else if(t->tun.mode == 2 && t->part_ok) t->mode = MODE_PARTITIONED;
   }
   {
-#define TATTR1(I, R, S, P, H, M) HIP_TRY(hipFuncSetAttribute((const void*)tile_rank_insert_kernel<I, R, S, P, kTileBlock, H, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_rank_lds(sizeof(S), kMaxTileBits, P)))
+#define TATTR2(I, R, S, P, H, M, HL) HIP_TRY(hipFuncSetAttribute((const void*)tile_rank_insert_kernel<I, R, S, P, kTileBlock, H, M, HL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_rank_lds(sizeof(S), kMaxTileBits, P)))
+#define TATTR1(I, R, S, P, H, M) TATTR2(I, R, S, P, H, M, true)
 #define TATTR(I, S, P) TATTR1(I, true, S, P, false, false); TATTR1(I, false, S, P, false, false); TATTR1(I, true, S, P, true, false); TATTR1(I, false, S, P, true, false); \
                        TATTR1(I, true, S, P, false, true); TATTR1(I, false, S, P, false, true)
     TATTR(uint32_t, unsigned int, 1); TATTR(uint32_t, unsigned int, 2); TATTR(uint32_t, unsigned long long, 1);
     TATTR(uint64_t, unsigned int, 1); TATTR(uint64_t, unsigned int, 2); TATTR(uint64_t, unsigned long long, 1);
+    // the instantiations for hole-free regions (launch_tile_rank_variant: 4-byte items into pairs of tiles, plain and sampling)
+    TATTR2(uint32_t, true, unsigned int, 2, false, false, false); TATTR2(uint32_t, false, unsigned int, 2, false, false, false);
+    TATTR2(uint32_t, true, unsigned int, 2, false, true, false); TATTR2(uint32_t, false, unsigned int, 2, false, true, false);
 #undef TATTR
 #undef TATTR1
+#undef TATTR2
     HIP_TRY(hipFuncSetAttribute((const void*)p1_scatter_sorted_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
     HIP_TRY(hipFuncSetAttribute((const void*)p1_scatter_sorted_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
     HIP_TRY(hipFuncSetAttribute((const void*)p1_scatter_sorted_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
@@ -900,7 +905,7 @@ int jfgpu_clear(jfgpu_table* t) {
   HIP_TRY(hipStreamSynchronize(t->stream));
   t->pristine = true; t->occ_known = 0; t->fed_since = 0; t->direct_seen = 0; t->occ_bound = 0; t->bigval_bound = 0; t->ovf_failed_need = 0;
   t->flushes_plain = 0; t->flushes_heavy = 0;
-  t->n_p2_roles = t->n_p2_ring = t->n_p2_sort = t->n_p2_exact = t->n_p1_ring = t->n_p1_other = 0;
+  t->n_p2_roles = t->n_p2_ring = t->n_p2_sort = t->n_p2_exact = t->n_p1_ring = t->n_p1_other = t->n_tile_dense = 0;
   return JFGPU_OK;
 }
 
@@ -1330,7 +1335,7 @@ int jfgpu_get_counters(jfgpu_table* t, uint64_t* out, uint32_t n) {
   rc = read_counters(t, c); if(rc) return rc;
   const uint64_t v[JFGPU_N_COUNTERS] = {c[CTR_FULL], c[CTR_MERS], c[CTR_OVF_FULL], c[CTR_OVF_USED], c[CTR_MISROUTED], c[CTR_DIRECT],
                                         c[CTR_T_ITEMS], c[CTR_T_QUEUED], t->flushes_plain, t->flushes_heavy,
-                                        t->n_p2_roles, t->n_p2_ring, t->n_p2_sort, t->n_p2_exact, t->n_p1_ring, t->n_p1_other};
+                                        t->n_p2_roles, t->n_p2_ring, t->n_p2_sort, t->n_p2_exact, t->n_p1_ring, t->n_p1_other, t->n_tile_dense};
   for(uint32_t i = 0; i < n; ++i) out[i] = i < JFGPU_N_COUNTERS ? v[i] : 0;
   return JFGPU_OK;
 }

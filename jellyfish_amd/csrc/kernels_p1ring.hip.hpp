@@ -153,7 +153,10 @@ __device__ __forceinline__ void ring_flush(ITEM* s_ring, uint32_t* s_fill, uint3
 #pragma unroll
       for(int q = 0; q < 4; ++q) dst[q] = v[q];
       const uint32_t real = cnt - s * R::kUnit < R::kUnit ? cnt - s * R::kUnit : R::kUnit;
-      B.gpos += R::kUnit; B.room -= R::kUnit; B.stored += real;
+      // A region with one writer ends exactly behind its last item: the holes of the partial last unit (`all`) are stored
+      // with it, past the region's end -- where p1_stragglers_kernel appends next -- so the region itself holds items only
+      // (kernels_tile.hip.hpp: HOLES = false).  Shared regions keep whole units: the next reservation starts behind them.
+      B.gpos += OWNED ? real : R::kUnit; B.room -= R::kUnit; B.stored += real;
     } else {                                                       // the region is exhausted (skewed input): the list
 #pragma unroll
       for(int q = 0; q < 4; ++q) chunk_items<ITEM>(v[q], [&](ITEM x) { if(x != hole) straggler(t, x, 1u); });

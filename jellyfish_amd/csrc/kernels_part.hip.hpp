@@ -53,11 +53,15 @@ struct PartGeom {
 // sh[s] == 0: buckets are packed, bucket j = [off[j], off[j+1]).
 // sh[s] == 1: "granule" batches of the single-pass P1: bucket j = [off[2j], off[2j+1]) inside its own
 //             fixed-capacity region, and entries equal to the all-ones item are holes to skip.
+// dense[s] != 0 (with sh[s] == 1): the producer promises that no region of the batch holds a hole -- every entry of
+//             [off[2j], off[2j+1]) is an item.  Only p2_ring_roles_kernel (one writer per region) makes that promise; the
+//             host picks the tile kernel's instantiation by it (kernels_tile.hip.hpp: HOLES).
 struct SegList {
   const void* items[kMaxSeg];
   const uint64_t* off[kMaxSeg];
   uint32_t sh[kMaxSeg];
   uint32_t n;
+  uint8_t dense[kMaxSeg];
 };
 __device__ inline uint64_t seg_lo(const SegList& S, uint32_t s, uint32_t j) { return S.off[s][(size_t)j << S.sh[s]]; }
 __device__ inline uint64_t seg_hi(const SegList& S, uint32_t s, uint32_t j) { return S.off[s][((size_t)j << S.sh[s]) + 1]; }

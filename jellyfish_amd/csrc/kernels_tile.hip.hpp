@@ -39,6 +39,22 @@ __device__ __attribute__((noinline)) void ovf_add_call(uint64_t* ovf_key, uint64
   ovf_add(V, slot, units);
 }
 
+// a value every lane of the workgroup holds alike, kept in a scalar register (branches on it are scalar branches)
+__device__ __forceinline__ uint32_t wg_uniform(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(JFGPU_EMU)
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+#else
+  return v;
+#endif
+}
+
+// s_waitcnt lgkmcnt(0): every LDS (and scalar-memory) operation of the wave issued so far has completed
+__device__ __forceinline__ void lds_wait_all() {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(JFGPU_EMU)
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+#endif
+}
+
 #ifndef JFGPU_T_BLOCK
 #define JFGPU_T_BLOCK 512
 #endif
@@ -49,10 +65,13 @@ constexpr uint32_t kQueueLook = 2;             // buckets one look of phase C fe
 #endif
 constexpr uint32_t kTileQueueBytes = JFGPU_T_QUEUE;    // LDS queue of phase C (what does not fit stays with the lane)
 
-// dynamic LDS of one workgroup: slots | bucket counters (16 bit each) | queue header | queue
+// dynamic LDS of one workgroup: bucket counters (16 bit each) | queue header (16 bytes) | slots | queue.  The counters
+// come first: a rank request then addresses its counter word with a DS instruction's 16-bit immediate offset (behind
+// 64 KiB of slots the base, byte 65536, took an address add per item); the slots start below byte 65536 too.
+constexpr size_t tile_rank_hdr(size_t nslots) { return (nslots >> kBucketBits) * 2 + 16; }
 inline size_t tile_rank_lds(size_t slot_bytes, uint32_t tile_bits, int tpb) {
   const size_t nslots = (size_t)tpb << tile_bits;
-  return nslots * slot_bytes + (nslots >> kBucketBits) * 2 + 16 + kTileQueueBytes;
+  return tile_rank_hdr(nslots) + nslots * slot_bytes + kTileQueueBytes;
 }
 
 // HEAVY: the instantiation for high-coverage input, where most of a round's items find their bucket full of -- after M --
@@ -63,7 +82,13 @@ inline size_t tile_rank_lds(size_t slot_bytes, uint32_t tile_bits, int tpb) {
 // M.  Which instantiation a flush runs is decided by the host from a sample of the flush itself (the first units go
 // through the plain kernel, which counts how many items went past rank 3: SAMPLE) -- both paths in one kernel cost the
 // common case 3 % (instruction cache).
-template <typename ITEM, bool RETURNING, typename SLOT, int TPB, int BLOCK = kTileBlock, bool HEAVY = false, bool SAMPLE = false>
+// HOLES = false: the instantiation for regions that hold items only (SegList::dense: the output of p2_ring_roles_kernel).
+// What is workgroup-uniform about a round -- n0 items, so n0 / BLOCK full rows of BLOCK items, one partial row, nothing
+// behind it -- is then decided by scalar branches: a full row is fetched by plain loads, asks for its ranks and is placed
+// without a validity mask or a lane-conditional block around the item; the partial row lives in a register of its own
+// (`tail`) and is the only masked one; rows behind it are skipped.  The hole-aware code tests every item of every row
+// (index below n0, not the hole marker) three times over: at the fetch, the rank request and the placement.
+template <typename ITEM, bool RETURNING, typename SLOT, int TPB, int BLOCK = kTileBlock, bool HEAVY = false, bool SAMPLE = false, bool HOLES = true>
 __global__ __launch_bounds__(BLOCK, (BLOCK >= 512 ? 2 * BLOCK / 256 : 4)) void tile_rank_insert_kernel(DevTable T, SegList S, uint64_t tile0, uint32_t n_tiles) {
   // S holds ONE item array (the P2 output, or one pending batch of a single-level table: the host launches per batch)
   // register-held items per lane and round: 9216 items per round; 4608 for 8-byte items (k = 31 into a single tile of
@@ -80,13 +105,14 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 512 ? 2 * BLOCK / 256 : 4)) void t
   // (the partitioned path only exists for full-size tiles: part_geom_init)
   constexpr uint32_t tsz = 1u << kMaxTileBits, nslots = TPB * tsz, nbkt = nslots >> kBucketBits, tmask = tsz - 1;
   constexpr uint32_t NBK = nbkt / BLOCK;                    // buckets per lane
-  SLOT* const s_tile = reinterpret_cast<SLOT*>(s_raw);
-  uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(s_raw + (size_t)nslots * sizeof(SLOT));      // two 16-bit counters per word
-  uint32_t* const s_qn = s_cnt + (nbkt >> 1);                 // (16 bytes of padding)
+  static_assert(HOLES || (!HEAVY && sizeof(ITEM) == 4), "the hole-free instantiation is the plain kernel's, for 4-byte items");
+  constexpr uint32_t kHdr = (uint32_t)tile_rank_hdr(nslots);                  // (tile_rank_lds: counters and queue header in front of the slots)
+  uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(s_raw);                                       // two 16-bit counters per word
+  SLOT* const s_tile = reinterpret_cast<SLOT*>(s_raw + kHdr);
   // phase C's queue: one segment per wave (positions come from a ballot: no atomic, no count to read back)
   constexpr uint32_t qcap = kTileQueueBytes / sizeof(ITEM) / (BLOCK / 64);
   static_assert(qcap >= 64, "phase C stages one held-back item per lane through the queue");
-  ITEM* const s_q = reinterpret_cast<ITEM*>(s_qn + 4) + (threadIdx.x >> 6) * qcap;
+  ITEM* const s_q = reinterpret_cast<ITEM*>(s_raw + kHdr + (size_t)nslots * sizeof(SLOT)) + (threadIdx.x >> 6) * qcap;
   SLOT* const gslots = reinterpret_cast<SLOT*>(T.slots);
   const SLOT lmask = (SLOT)g.low_mask, inc = (SLOT)g.inc, occ = (SLOT)g.occ_bit;
   const uint32_t cshift = g.tag_bits + 1, idshift = kSlotBits - cshift;
@@ -322,34 +348,60 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 512 ? 2 * BLOCK / 256 : 4)) void t
     for(int r = 0; r < NP; ++r)
       if((vm >> r) & 1) { const uint32_t b = home_of(it[r]) >> kBucketBits; old[r] = atomicAdd(&s_cnt[b >> 1], 1u << ((b & 1) * 16)); }
   };
+  // the same for hole-free input: nf full rows (workgroup-uniform), then the partial row's item (tv: this lane has one)
+  auto rank_request_dense = [&](const ITEM (&it)[NP], uint32_t nf, ITEM tail, bool tv, uint32_t (&old)[NP], uint32_t& told) {
+#pragma unroll
+    for(int r = 0; r < NP; ++r)
+      if((uint32_t)r < nf) { const uint32_t b = home_of(it[r]) >> kBucketBits; old[r] = atomicAdd(&s_cnt[b >> 1], 1u << ((b & 1) * 16)); }
+    if(tv) { const uint32_t b = home_of(tail) >> kBucketBits; told = atomicAdd(&s_cnt[b >> 1], 1u << ((b & 1) * 16)); }
+  };
   // A, second half, then M and C.  `again`: where the round's items came from (held-back items are read again from there:
   // indexing the register array would put it in scratch).  after_a(): it[] is dead from there on.
   [[maybe_unused]] uint32_t smp_items = 0, smp_queued = 0;   // SAMPLE: this lane's items / this wave's items past rank 3
-  auto place_round = [&](ITEM (&it)[NP], uint32_t vm, const uint32_t (&old)[NP], uint64_t unit_slot0, const ITEM* again, auto&& after_a) {
+  // (hole-free input: vm is the number of full rows, `tail` / `told` / `tv` the partial row's item, its counter word
+  //  before the add, whether this lane has one; a held-back tail is bit NP of `pend`)
+  auto place_round = [&](ITEM (&it)[NP], uint32_t vm, const uint32_t (&old)[NP], uint64_t unit_slot0, const ITEM* again, auto&& after_a,
+                         [[maybe_unused]] ITEM tail = 0, [[maybe_unused]] uint32_t told = 0, [[maybe_unused]] bool tv = false) {
     uint32_t qn = 0, pend = 0;                                 // qn: items of this wave past rank 3 (wave-uniform)
     [[maybe_unused]] uint32_t ovm = 0;
 #pragma unroll
     for(int r = 0; r < NP; ++r) JF_OPAQUE(it[r]);
-#pragma unroll
-    for(int r = 0; r < NP; ++r) {
+    // one item: the slot its rank names, or -- past rank 3 -- the wave's queue
+    auto place_item = [&](ITEM x, uint32_t o, bool valid, uint32_t bit) {
       bool ov = false;
-      if((vm >> r) & 1) {
-        const uint32_t b = home_of(it[r]) >> kBucketBits;
-        const uint32_t rank = (old[r] >> ((b & 1) * 16)) & 0xFFFFu;
-        if(rank < kB) s_tile[(b << kBucketBits) + rank] = inc | occ | (SLOT)((uint64_t)it[r] & (g.occ_bit - 1));
+      if(valid) {
+        const uint32_t b = home_of(x) >> kBucketBits;
+        const uint32_t rank = (o >> ((b & 1) * 16)) & 0xFFFFu;
+        if(rank < kB) s_tile[(b << kBucketBits) + rank] = inc | occ | (SLOT)((uint64_t)x & (g.occ_bit - 1));
         else ov = true;
       }
-      if constexpr(HEAVY) { if(ov) ovm |= 1u << r; }
+      if constexpr(HEAVY) { if(ov) ovm |= 1u << bit; }
       else {
         const unsigned long long m = __ballot(ov);
         if(ov) {
           const uint32_t at = qn + (uint32_t)__popcll(m & below);
-          if(at < qcap) s_q[at] = it[r]; else pend |= 1u << r;
+          if(at < qcap) s_q[at] = x; else pend |= 1u << bit;
         }
         qn += (uint32_t)__popcll(m);
       }
+    };
+    if constexpr(HOLES) {
+#pragma unroll
+      for(int r = 0; r < NP; ++r) place_item(it[r], old[r], (vm >> r) & 1, (uint32_t)r);
+      if constexpr(SAMPLE) smp_items += (uint32_t)__popc(vm);
+    } else {
+      // The rank adds of full rows were issued unconditionally, but each in a basic block of its own (the scalar branch on
+      // the row count), and the compiler then waits for LDS at every item -- for the previous item's store too.  One wait
+      // for all the ranks here, and it places none of its own below.
+      lds_wait_all();
+#pragma unroll
+      for(int r = 0; r < NP; ++r)
+        if((uint32_t)r < vm) place_item(it[r], old[r], true, (uint32_t)r);      // (workgroup-uniform)
+      JF_OPAQUE(tail);
+      place_item(tail, told, tv, (uint32_t)NP);
+      if constexpr(SAMPLE) smp_items += vm + (tv ? 1u : 0u);
     }
-    if constexpr(SAMPLE) { smp_items += (uint32_t)__popc(vm); smp_queued += qn; }
+    if constexpr(SAMPLE) smp_queued += qn;
     if constexpr(!HEAVY) after_a();
     lds_barrier();
     JF_PHASE(pc, 2);
@@ -419,8 +471,9 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 512 ? 2 * BLOCK / 256 : 4)) void t
       const unsigned long long m = __ballot(pend != 0);      // (wave-uniform; nearly always 0)
       if(!m) break;
       if(pend) {
-        const uint32_t r = (uint32_t)__ffs((int)pend) - 1u;
+        uint32_t r = (uint32_t)__ffs((int)pend) - 1u;
         pend &= pend - 1;
+        if constexpr(!HOLES) { if(r == (uint32_t)NP) r = vm; }   // (the partial row sits behind the full ones)
         s_q[(uint32_t)__popcll(m & below)] = again[r * BLOCK + threadIdx.x];
       }
       nq = (uint32_t)__popcll(m);
@@ -439,18 +492,29 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 512 ? 2 * BLOCK / 256 : 4)) void t
   const uint64_t* off = S.off[0];
   const uint32_t sh = S.sh[0];                              // 0: packed offsets off[t], off[t + 1]; 1: pairs (begin, end), items may be holes
   const bool holes = sh != 0;
+  static_assert(NP < 32, "a round's items and the partial row are bits of one word");
   const ITEM* src = reinterpret_cast<const ITEM*>(S.items[0]);
   const uint32_t G = gridDim.x;
   constexpr uint64_t kRound = (uint64_t)NP * BLOCK;
   uint32_t t = blockIdx.x;
   uint64_t a0 = 0, b0 = 0, a1 = 0, b1 = 0; uint32_t d0 = 0, d1 = 0;
   ITEM cur[NP];
+  [[maybe_unused]] ITEM tail = 0;                           // hole-free input: the partial row's item
   auto fetch = [&](uint64_t a, uint64_t b) {                // items src[a .. min(b, a + NP x BLOCK)): block-uniform base + 32-bit index
     const ITEM* ub = src + a;
     const uint32_t n = (uint32_t)((b - a) < kRound ? (b - a) : kRound);
     if(b <= a) return;                                      // (block-uniform; such a unit is skipped)
     uint32_t tid = threadIdx.x;
     JF_OPAQUE(tid);                                         // (or the item indices are hoisted out of the loop and spilled)
+    if constexpr(!HOLES) {                                  // full rows: plain loads; one clamped load for the partial row
+      const uint32_t nf = wg_uniform(n / BLOCK);
+#pragma unroll
+      for(int r = 0; r < NP; ++r)
+        if((uint32_t)r < nf) cur[r] = ub[(uint32_t)r * BLOCK + tid];
+      const uint32_t i = nf * BLOCK + tid;
+      tail = ub[i < n ? i : n - 1];
+      return;
+    }
 #pragma unroll
     for(int r = 0; r < NP; ++r) {                           // unconditional loads at clamped indices: no branch per item
       const uint32_t i = (uint32_t)r * BLOCK + tid;
@@ -476,19 +540,28 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 512 ? 2 * BLOCK / 256 : 4)) void t
     const uint32_t n0 = (uint32_t)((b0 - c0) < kRound ? (b0 - c0) : kRound);
     uint32_t vm = 0, tid = threadIdx.x;
     JF_OPAQUE(tid);
+    [[maybe_unused]] bool tv = false;
+    if constexpr(HOLES) {
 #pragma unroll
-    for(int r = 0; r < NP; ++r)
-      if((uint32_t)r * BLOCK + tid < n0 && !(holes && cur[r] == hole)) vm |= 1u << r;      // (what a clamped load fetched is not an item)
+      for(int r = 0; r < NP; ++r)
+        if((uint32_t)r * BLOCK + tid < n0 && !(holes && cur[r] == hole)) vm |= 1u << r;      // (what a clamped load fetched is not an item)
+    } else {
+      vm = wg_uniform(n0 / BLOCK);                           // full rows
+      tv = vm * BLOCK + tid < n0;
+    }
     // a further round of the same unit (more items than one round holds: skewed input) starts from the tile as the previous round
     // stored it -- merged, compacted, counted again on the way in -- by the lanes that stored it
     const uint32_t d_eff = first ? d0 : (TPB == 2 ? 0x0101u : 1u);
     if(d_eff) { load_tile(gt, d_eff); lds_barrier(); }       // (otherwise the previous store left tile and counters zeroed)
     uint32_t old[NP];
-    rank_request(cur, vm, old);
+    [[maybe_unused]] uint32_t told = 0;
+    if constexpr(HOLES) rank_request(cur, vm, old);
+    else rank_request_dense(cur, vm, tail, tv, old, told);
     JF_PHASE(pc, 1);
     uint64_t a2 = 0, b2 = 0; uint32_t d2 = 0;
     if(last && t + 2 * G < n_tiles) { a2 = off[(size_t)(t + 2 * G) << sh]; b2 = off[((size_t)(t + 2 * G) << sh) + 1]; d2 = unit_dirty(t + 2 * G); }
-    place_round(cur, vm, old, unit_slot0, src + c0, [&] { if(last) fetch(a1, b1); else fetch(c0 + kRound, b0); });
+    if constexpr(HOLES) place_round(cur, vm, old, unit_slot0, src + c0, [&] { if(last) fetch(a1, b1); else fetch(c0 + kRound, b0); });
+    else place_round(cur, vm, old, unit_slot0, src + c0, [&] { if(last) fetch(a1, b1); else fetch(c0 + kRound, b0); }, tail, told, tv);
     store_tile(gt, t);                            // (every round ends on a barrier)
     lds_barrier();
     JF_PHASE(pc, 4);

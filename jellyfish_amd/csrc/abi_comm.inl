@@ -510,13 +510,12 @@ int comm_insert_prev(jfgpu_comm* c, jfgpu_comm::Rank& R) {
     rc = part_flush(t); if(rc) return rc;
     ProfScope ps(t, 1, n);
     const int grid = grid_for(t, (n + kBlock - 1) / kBlock);
-    if(t->nword) hipLaunchKernelGGL(update_keys_nword_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->nt, (const uint64_t*)R.recv[prev], (uint64_t)n, t->key_words);
-    else if(t->wide) {
-      if(t->returning) hipLaunchKernelGGL(update_keys_wide_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, (const uint64_t*)R.recv[prev], (uint64_t)n);
-      else             hipLaunchKernelGGL(update_keys_wide_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, (const uint64_t*)R.recv[prev], (uint64_t)n);
-    }
-    else if(t->returning) hipLaunchKernelGGL(update_keys_one_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, (const uint64_t*)R.recv[prev], (uint64_t)n);
-    else             hipLaunchKernelGGL(update_keys_one_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, (const uint64_t*)R.recv[prev], (uint64_t)n);
+    with_view(t, [&](const auto& T) {
+      typedef std::decay_t<decltype(T)> Table;
+      if constexpr(KeyOps<Table>::kUpdateReturns) hipLaunchKernelGGL((update_keys_kernel<Table, true>), dim3(grid), dim3(kBlock), 0, t->stream, T, (const uint64_t*)R.recv[prev], (uint64_t)n, t->key_words);
+      else if(t->returning) hipLaunchKernelGGL((update_keys_kernel<Table, true>), dim3(grid), dim3(kBlock), 0, t->stream, T, (const uint64_t*)R.recv[prev], (uint64_t)n, t->key_words);
+      else hipLaunchKernelGGL((update_keys_kernel<Table, false>), dim3(grid), dim3(kBlock), 0, t->stream, T, (const uint64_t*)R.recv[prev], (uint64_t)n, t->key_words);
+    });
     HIP_TRY(hipGetLastError());
   } else if(n) rc = add_keys_piece(t, R.recv[prev], (size_t)n, t->operation == 1 ? 0 : 1, nullptr);
   HIP_TRY(hipEventRecord(R.consumed[prev], t->stream));
@@ -972,8 +971,8 @@ __global__ __launch_bounds__(kBlock) void reshard_kernel(Table old, Table neu, i
     typename K::Slot s;
     if(!K::load(old, i, s)) continue;                    // (a claim that was never completed holds no key)
     const typename K::Key key = K::key(old, s, i & ~g.tile_mask);
-    const uint32_t owner = K::owner(neu, key);
-    if(owner == K::geom(neu).shard_id) { if(pass) K::add_val(neu, key, K::count(old, s, i, have_ovf)); }
+    const uint32_t owner = K::owner(neu, neu.fwd_tbl, key);
+    if(owner == K::geom(neu).shard_id) { if(pass) K::add_val(neu, neu.fwd_tbl, key, K::count(old, s, i, have_ovf)); }
     else {
       const unsigned long long at = atomicAdd(&cursors[owner], 1ull);
       if(pass) { K::store_key(keys_out + (uint64_t)kw * at, key, kw); cnts_out[at] = K::count(old, s, i, have_ovf); }
@@ -983,7 +982,7 @@ __global__ __launch_bounds__(kBlock) void reshard_kernel(Table old, Table neu, i
 template <class Table>
 __global__ __launch_bounds__(kBlock) void add_pairs_kernel(Table T, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ cnts, uint64_t n, uint32_t kw) {
   for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    KeyOps<Table>::add_val(T, KeyOps<Table>::load_key(T, keys, i, kw), cnts[i]);
+    KeyOps<Table>::add_val(T, T.fwd_tbl, KeyOps<Table>::load_key(T, keys, i, kw, false), cnts[i]);      // (keys as they come: made by store_key or by the caller)
 }
 
 int comm_exchange_rccl(jfgpu_comm* c); int comm_exchange_local(jfgpu_comm* c); int comm_exchange_ipc(jfgpu_comm* c);

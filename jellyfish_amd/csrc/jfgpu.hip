@@ -973,32 +973,23 @@ static int add_keys_piece(jfgpu_table* t, const uint64_t* d_keys, size_t n, uint
   if(!n) return JFGPU_OK;
   { const bool big = t->g.cnt_bits < 64 && (val >> t->g.cnt_bits) != 0;
     rc = ensure_ovf(t, big ? 0 : (uint64_t)n * val, big ? n : 0); if(rc) return rc; }
-  if(t->nword) {
-    ProfScope ps(t, 1, n);
-    t->pristine = false;
-    hipLaunchKernelGGL(add_keys_nword_kernel, dim3(grid_for(t, (n + kBlock - 1) / kBlock)), dim3(kBlock), 0, t->stream, t->nt, d_keys, (uint64_t)n, t->key_words, val, d_is_new);
-    HIP_TRY(hipGetLastError());
-    return JFGPU_OK;
-  }
-  if(t->wide) {
-    ProfScope ps(t, 1, n);
-    hipLaunchKernelGGL(add_keys_wide_kernel, dim3(grid_for(t, (n + kBlock - 1) / kBlock)), dim3(kBlock), 0, t->stream, t->wt, d_keys, (uint64_t)n, val, d_is_new);
-    HIP_TRY(hipGetLastError());
-    return JFGPU_OK;
-  }
-  if(val == 1 && !d_is_new && use_partitioned(t, n * 8)) {
+  // the partitioned path and its pending batch take keys of one word only
+  const bool one_word = !t->wide && !t->nword;
+  if(one_word && val == 1 && !d_is_new && use_partitioned(t, n * 8)) {
     const int prc = part_ingest(t, (const uint8_t*)d_keys, 0, (int64_t)n, true, n);
     if(prc >= 0) return prc;
   }
-  if(d_is_new || val != 1) { rc = part_flush(t); if(rc) return rc; }   // is_new / set() must see earlier adds
-  t->pristine = false;
+  if(one_word && (d_is_new || val != 1)) { rc = part_flush(t); if(rc) return rc; }   // is_new / set() must see earlier adds
+  if(!t->wide) t->pristine = false;                      // (an add of two-word keys never cleared it: kept so)
   const int grid = grid_for(t, (n + kBlock - 1) / kBlock);
   ProfScope ps(t, 1, n);
-  if(val == 1 && !d_is_new) {
+  if(one_word && val == 1 && !d_is_new) {
     if(t->returning) hipLaunchKernelGGL(add_keys_one_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, d_keys, (uint64_t)n);
     else             hipLaunchKernelGGL(add_keys_one_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, d_keys, (uint64_t)n);
   } else {
-    hipLaunchKernelGGL(add_keys_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, d_keys, (uint64_t)n, val, d_is_new);
+    with_view(t, [&](const auto& T) {
+      hipLaunchKernelGGL(add_keys_kernel, dim3(grid), dim3(kBlock), 0, t->stream, T, d_keys, (uint64_t)n, t->key_words, val, d_is_new);
+    });
   }
   HIP_TRY(hipGetLastError());
   return JFGPU_OK;
@@ -1046,18 +1037,9 @@ int jfgpu_lookup_dev(jfgpu_table* t, const uint64_t* d_keys, size_t n, uint64_t*
   rc = check_deferred(t, c); if(rc) return rc;
   const int grid = grid_for(t, (n + kBlock - 1) / kBlock);
   ProfScope ps(t, 3, n);
-  if(t->nword) {
-    hipLaunchKernelGGL(lookup_nword_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->nt, d_keys, (uint64_t)n, t->key_words, d_vals, d_found, (int)(c[CTR_OVF_USED] != 0));
-    HIP_TRY(hipGetLastError());
-    return JFGPU_OK;
-  }
-  if(t->wide) {
-    hipLaunchKernelGGL(lookup_wide_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, d_keys, (uint64_t)n, d_vals, d_found, (int)(c[CTR_OVF_USED] != 0));
-    HIP_TRY(hipGetLastError());
-    return JFGPU_OK;
-  }
-  hipLaunchKernelGGL(lookup_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, d_keys, (uint64_t)n, d_vals, d_found,
-                     (int)(c[CTR_OVF_USED] != 0));
+  with_view(t, [&](const auto& T) {
+    hipLaunchKernelGGL(lookup_kernel, dim3(grid), dim3(kBlock), 0, t->stream, T, d_keys, (uint64_t)n, t->key_words, d_vals, d_found, (int)(c[CTR_OVF_USED] != 0));
+  });
   HIP_TRY(hipGetLastError());
   return JFGPU_OK;
 }

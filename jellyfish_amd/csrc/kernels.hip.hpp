@@ -200,9 +200,24 @@ __device__ inline bool table_add(const DevTable& T, const uint64_t* fwd_lds, uin
   return false;
 }
 
+// Slot holding `key` in the tile of `a`, or ~0 when it is absent.  Probes like a look-up: the first empty slot ends the search.
+__device__ inline uint64_t table_find_at(const DevTable& T, uint64_t key, const SlotAddr& a) {
+  const TableGeom& g = T.g;
+  const uint64_t low = g.occ_bit | make_tag(g, key, a.idx0);
+  const uint32_t tmask = (uint32_t)g.tile_mask;
+  for(uint32_t p = 0; p <= T.max_probe; ++p) {
+    const uint64_t slot = a.tile_base + probe_lin(a.idx0, p, tmask);
+    const uint64_t old = slot_ld_relaxed(T, slot);
+    if(old == 0ull) return ~0ull;
+    if((old & g.low_mask) == low) return slot;
+  }
+  return ~0ull;
+}
+
 // hash_counter::update_add (hash_counter.hpp:150-166, large_hash_array.hpp update_add): increment only
-// if the key is already there -- the UPDATE pass of `count --if` (count_main.cc:173-181).  Probes like a
-// look-up: the first empty slot ends the search.
+// if the key is already there -- the UPDATE pass of `count --if` (count_main.cc:173-181).  The probe of table_find_at,
+// written out with the add inside the loop: on top of table_find_at the compiler gives count_ascii_kernel, which inlines
+// this sixteen times, another register allocation (profiles/keyed_kernel_resources.txt).
 template <bool RETURNING>
 __device__ inline bool table_update_add(const DevTable& T, const uint64_t* fwd_lds, uint64_t key, uint64_t cnt) {
   const TableGeom& g = T.g;
@@ -268,33 +283,63 @@ __device__ inline bool table_add_val(const DevTable& T, const uint64_t* fwd_lds,
 }
 
 // ---- slot access per key width ------------------------------------------------------
-// What a kernel that walks a whole table needs from its view (DevTable here, WideTable in kernels_wide.hip.hpp, NTable in
-// kernels_nword.hip.hpp), so that such a kernel is written once: rehash_kernel, scan_kernel and dump_tiles_words_kernel
-// below, reshard_kernel and add_pairs_kernel in abi_comm.inl.  A specialisation has
+// What a kernel needs from its view (DevTable here, WideTable in kernels_wide.hip.hpp, NTable in kernels_nword.hip.hpp), so
+// that it is written once.  The kernels that walk a whole table: rehash_kernel, scan_kernel and dump_tiles_words_kernel
+// below, reshard_kernel and add_pairs_kernel in abi_comm.inl.  The kernels that are handed a list of keys: add_keys_kernel,
+// update_keys_kernel and lookup_kernel below.  A specialisation has
 //   Key, Slot                        a key, and what was read of a slot
 //   geom(T)                          the table's TableGeom
 //   load(T, i, s)                    reads slot i; true when it holds a key
 //   occupied(T, i, s)                the cheaper read where one word tells (the multi-word views; the counting scans use it)
 //   count(T, s, i, have_ovf)         the full count, with the overflow side table when have_ovf
+//   count_at(T, i, have_ovf)         the same of the slot at index i, read here
 //   key(T, s, tile_base)             the key, rebuilt through inv_tbl
-//   add_val(T, key, val)             hash_counter::add(key, val) into T
-//   owner(T, key)                    the shard that owns key under T's matrix
-//   store_key / load_key             a key as kw little-endian 64-bit words
+//   kFwdLdsWords, stage_fwd(T)       how the forward hash tables reach a keyed kernel: the 64-bit words of static LDS they are
+//                                    staged in (0: NTable's 64 KiB stay in global memory, read through the caches), and the
+//                                    staging with its barrier, which returns the pointer H the hash is to read.  The
+//                                    whole-table kernels hash rarely and pass T.fwd_tbl
+//   add_val(T, H, key, val)          hash_counter::add(key, val) into T
+//   update_add<RETURNING>(T, H, key, cnt)  hash_counter::update_add: only if the key is there; kUpdateReturns: the view's
+//                                    update_add reads the old count back whatever RETURNING says (only <true> is to be compiled)
+//   find(T, H, key)                  the slot that holds key, or ~0; a key of another shard is not here
+//   owner(T, H, key)                 the shard that owns key under T's matrix
+//   store_key / load_key             a key as kw little-endian 64-bit words; load_key masks with the table's key mask when asked
 //   digest(T, key, c)                (the multi-word views) an entry's digest hash
 //   kSlotWords, slot_of(w), key_byte (the multi-word views, for the dump) words per slot, a slot from a copy of its words, byte b of a key
 template <class Table> struct KeyOps;
 
+__device__ inline void load_tables_lds(uint64_t* dst, const uint64_t* src, uint32_t nbytes) {
+  for(uint32_t i = threadIdx.x; i < nbytes * 256; i += blockDim.x) dst[i] = src[i];
+}
+template <uint32_t WORDS>
+__device__ inline const uint64_t* stage_tables_lds(const uint64_t* src, uint32_t nbytes) {     // (KeyOps::stage_fwd of the views that stage)
+  __shared__ uint64_t s_tbl[WORDS];
+  load_tables_lds(s_tbl, src, nbytes);
+  __syncthreads();
+  return s_tbl;
+}
+
 template <> struct KeyOps<DevTable> {
   typedef uint64_t Key;
   struct Slot { uint64_t w; };
+  static constexpr uint32_t kFwdLdsWords = 8 * 256;
+  static constexpr bool kUpdateReturns = false;
   __device__ static const TableGeom& geom(const DevTable& T) { return T.g; }
   __device__ static bool load(const DevTable& T, uint64_t i, Slot& s) { s.w = slot_ld(T, i); return s.w != 0; }
   __device__ static uint64_t count(const DevTable& T, const Slot& s, uint64_t i, int have_ovf) { return full_count(T, s.w, i, have_ovf); }
+  __device__ static uint64_t count_at(const DevTable& T, uint64_t i, int have_ovf) { return full_count(T, slot_ld(T, i), i, have_ovf); }
   __device__ static Key key(const DevTable& T, const Slot& s, uint64_t tile_base) { return slot_key(T.g, T.inv_tbl, s.w, tile_base); }
-  __device__ static bool add_val(const DevTable& T, Key key, uint64_t val) { return table_add_val(T, T.fwd_tbl, key, val); }
-  __device__ static uint32_t owner(const DevTable& T, Key key) { return (uint32_t)(hash_tables(T.fwd_tbl, key, T.g.nbytes) >> T.g.lsize_l); }
+  __device__ static const uint64_t* stage_fwd(const DevTable& T) { return stage_tables_lds<kFwdLdsWords>(T.fwd_tbl, T.g.nbytes); }
+  __device__ static bool add_val(const DevTable& T, const uint64_t* H, Key key, uint64_t val) { return table_add_val(T, H, key, val); }
+  template <bool RETURNING>
+  __device__ static bool update_add(const DevTable& T, const uint64_t* H, Key key, uint64_t cnt) { return table_update_add<RETURNING>(T, H, key, cnt); }
+  __device__ static uint64_t find(const DevTable& T, const uint64_t* H, Key key) {
+    const SlotAddr a = slot_addr(T.g, hash_tables(H, key, T.g.nbytes));
+    return a.shard == T.g.shard_id ? table_find_at(T, key, a) : ~0ull;
+  }
+  __device__ static uint32_t owner(const DevTable& T, const uint64_t* H, Key key) { return (uint32_t)(hash_tables(H, key, T.g.nbytes) >> T.g.lsize_l); }
   __device__ static void store_key(uint64_t* dst, Key key, uint32_t) { dst[0] = key; }
-  __device__ static Key load_key(const DevTable&, const uint64_t* keys, uint64_t i, uint32_t) { return keys[i]; }
+  __device__ static Key load_key(const DevTable& T, const uint64_t* keys, uint64_t i, uint32_t, bool masked) { return masked ? keys[i] & T.g.key_mask : keys[i]; }
 };
 
 __device__ inline LaneWords stage_tile(const uint8_t* __restrict__ base, int64_t tile_start, int64_t lo, int64_t hi,
@@ -358,10 +403,6 @@ __device__ inline LaneWords tile_stage(const TileRaw& R, int64_t tile_start, int
   return L;
 }
 
-__device__ inline void load_tables_lds(uint64_t* dst, const uint64_t* src, uint32_t nbytes) {
-  for(uint32_t i = threadIdx.x; i < nbytes * 256; i += blockDim.x) dst[i] = src[i];
-}
-
 // ---- K2+K3 fused: count every k-mer of a contract buffer ----------------------
 // base: 16-byte aligned; valid bytes are [lo, hi).
 // op: 0 COUNT add(m, 1); 1 PRIME set(m) = claim with count 0; 2 UPDATE update_add(m, 1) (count_main.cc:152-184).
@@ -408,20 +449,8 @@ __global__ __launch_bounds__(kBlock) void count_ascii_kernel(DevTable T, const u
   if((threadIdx.x & 63) == 0 && w) atomicAdd((unsigned long long*)&T.counters[CTR_MERS], (unsigned long long)w);
 }
 
-// ---- hash_counter::add on encoded keys -----------------------------------------
-__global__ __launch_bounds__(kBlock) void add_keys_kernel(DevTable T, const uint64_t* __restrict__ keys, uint64_t n,
-                                                          uint64_t val, uint8_t* __restrict__ is_new) {
-  __shared__ uint64_t s_fwd[8 * 256];
-  load_tables_lds(s_fwd, T.fwd_tbl, T.g.nbytes);
-  __syncthreads();
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t key = keys[i] & T.g.key_mask;
-    const bool nw = table_add_val(T, s_fwd, key, val);
-    if(is_new) is_new[i] = nw ? 1 : 0;
-  }
-}
-
-// Same, but val == 1 and no is_new: the receive side of the multi-GPU exchange.
+// ---- hash_counter::add on encoded keys, val == 1 and no is_new: the receive side of the multi-GPU exchange ----
+// (the one-word fast path; every other add of keys is add_keys_kernel below)
 template <bool RETURNING>
 __global__ __launch_bounds__(kBlock) void add_keys_one_kernel(DevTable T, const uint64_t* __restrict__ keys, uint64_t n) {
   __shared__ uint64_t s_fwd[8 * 256];
@@ -429,45 +458,6 @@ __global__ __launch_bounds__(kBlock) void add_keys_one_kernel(DevTable T, const 
   __syncthreads();
   for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
     table_add<RETURNING>(T, s_fwd, keys[i] & T.g.key_mask, 1);
-}
-
-// hash_counter::update_add on encoded keys, val == 1: the receive side of the exchange in the UPDATE pass of count --if
-// (count_main.cc:152-184 with --gpus): only keys that are present are counted.
-template <bool RETURNING>
-__global__ __launch_bounds__(kBlock) void update_keys_one_kernel(DevTable T, const uint64_t* __restrict__ keys, uint64_t n) {
-  __shared__ uint64_t s_fwd[8 * 256];
-  load_tables_lds(s_fwd, T.fwd_tbl, T.g.nbytes);
-  __syncthreads();
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    table_update_add<RETURNING>(T, s_fwd, keys[i] & T.g.key_mask, 1);
-}
-
-// ---- get_val_for_key -------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void lookup_kernel(DevTable T, const uint64_t* __restrict__ keys, uint64_t n,
-                                                        uint64_t* __restrict__ vals, uint8_t* __restrict__ found,
-                                                        int have_ovf) {
-  __shared__ uint64_t s_fwd[8 * 256];
-  load_tables_lds(s_fwd, T.fwd_tbl, T.g.nbytes);
-  __syncthreads();
-  const TableGeom& g = T.g;
-  const uint32_t tmask = (uint32_t)g.tile_mask;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t key = keys[i] & g.key_mask;
-    const uint64_t pos = hash_tables(s_fwd, key, g.nbytes);
-    const SlotAddr a = slot_addr(g, pos);
-    uint64_t val = 0; uint8_t fnd = 0;
-    if(a.shard == g.shard_id) {
-      const uint64_t low = g.occ_bit | make_tag(g, key, a.idx0);
-      for(uint32_t p = 0; p <= T.max_probe; ++p) {
-        const uint64_t slot = a.tile_base + probe_lin(a.idx0, p, tmask);
-        const uint64_t w = slot_ld(T, slot);
-        if(w == 0) break;
-        if((w & g.low_mask) == low) { val = full_count(T, w, slot, have_ovf); fnd = 1; break; }
-      }
-    }
-    vals[i] = val;
-    if(found) found[i] = fnd;
-  }
 }
 
 // ---- multi-GPU routing: count per shard, then scatter ----------------------------
@@ -553,7 +543,43 @@ __global__ __launch_bounds__(kBlock) void rehash_kernel(Table old, Table neu, in
     typename K::Slot s;
     if(!K::load(old, i, s)) continue;
     const typename K::Key key = K::key(old, s, i & ~g.tile_mask);
-    K::add_val(neu, key, K::count(old, s, i, have_ovf));
+    K::add_val(neu, neu.fwd_tbl, key, K::count(old, s, i, have_ovf));
+  }
+}
+
+// ---- the kernels that are handed keys, kw words each (low first): every key width (KeyOps) ---------------------------
+// hash_counter::add(key, val) on encoded mers (hash_counter.hpp:91-126)
+template <class Table>
+__global__ __launch_bounds__(kBlock) void add_keys_kernel(Table T, const uint64_t* __restrict__ keys, uint64_t n, uint32_t kw, uint64_t val,
+                                                          uint8_t* __restrict__ is_new) {
+  typedef KeyOps<Table> K;
+  const uint64_t* H = K::stage_fwd(T);
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const bool nw = K::add_val(T, H, K::load_key(T, keys, i, kw, true), val);
+    if(is_new) is_new[i] = nw ? 1 : 0;
+  }
+}
+
+// hash_counter::update_add(key, 1): the receive side of the exchange in the UPDATE pass of count --if over shards
+// (count_main.cc:152-184 with --gpus): only keys that are present are counted, a key of another shard is counted as misrouted.
+template <class Table, bool RETURNING>
+__global__ __launch_bounds__(kBlock) void update_keys_kernel(Table T, const uint64_t* __restrict__ keys, uint64_t n, uint32_t kw) {
+  typedef KeyOps<Table> K;
+  const uint64_t* H = K::stage_fwd(T);
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    K::template update_add<RETURNING>(T, H, K::load_key(T, keys, i, kw, true), 1);
+}
+
+// array_base::get_val_for_key (large_hash_array.hpp:354-372)
+template <class Table>
+__global__ __launch_bounds__(kBlock) void lookup_kernel(Table T, const uint64_t* __restrict__ keys, uint64_t n, uint32_t kw,
+                                                        uint64_t* __restrict__ vals, uint8_t* __restrict__ found, int have_ovf) {
+  typedef KeyOps<Table> K;
+  const uint64_t* H = K::stage_fwd(T);
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t s = K::find(T, H, K::load_key(T, keys, i, kw, true));
+    vals[i] = s == ~0ull ? 0 : K::count_at(T, s, have_ovf);
+    if(found) found[i] = s != ~0ull;
   }
 }
 

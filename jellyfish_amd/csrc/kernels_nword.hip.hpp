@@ -162,8 +162,8 @@ __device__ inline K256 nword_slot_key(const NTable& T, const uint64_t* inv_tbl, 
 
 // Where `key` lives, or false when its position names another shard (counted: a key is never silently inserted or
 // credited on a shard that does not own it -- jfgpu_sync reports it).
-__device__ inline bool nword_addr(const NTable& T, const K256& key, SlotAddr& a) {
-  a = slot_addr(T.N.g, hash_tables_n256(T.fwd_tbl, key, T.N.g.nbytes));
+__device__ inline bool nword_addr(const NTable& T, const uint64_t* fwd, const K256& key, SlotAddr& a) {
+  a = slot_addr(T.N.g, hash_tables_n256(fwd, key, T.N.g.nbytes));
   if(a.shard == T.N.g.shard_id) return true;
   atomicAdd((unsigned long long*)&T.counters[CTR_MISROUTED], 1ull);
   return false;
@@ -204,7 +204,7 @@ __device__ inline bool nword_add_at(const NTable& T, const K256& key, const Slot
 template <bool RETURNING>
 __device__ inline bool nword_add(const NTable& T, const K256& key, uint64_t cnt) {
   SlotAddr a;
-  return nword_addr(T, key, a) && nword_add_at<RETURNING>(T, key, a, cnt);
+  return nword_addr(T, T.fwd_tbl, key, a) && nword_add_at<RETURNING>(T, key, a, cnt);
 }
 
 // Slot holding `key` in the tile of `a`, or ~0 when it is absent (a look-up: the first never-claimed slot ends the search).
@@ -223,8 +223,8 @@ __device__ inline uint64_t nword_find_at(const NTable& T, const K256& key, const
   }
   return ~0ull;
 }
-__device__ inline uint64_t nword_find(const NTable& T, const K256& key) {     // (a key of another shard is not here)
-  const SlotAddr a = slot_addr(T.N.g, hash_tables_n256(T.fwd_tbl, key, T.N.g.nbytes));
+__device__ inline uint64_t nword_find(const NTable& T, const uint64_t* fwd, const K256& key) {     // (a key of another shard is not here)
+  const SlotAddr a = slot_addr(T.N.g, hash_tables_n256(fwd, key, T.N.g.nbytes));
   return a.shard == T.N.g.shard_id ? nword_find_at(T, key, a) : ~0ull;
 }
 
@@ -235,14 +235,23 @@ __device__ inline void nword_credit(const NTable& T, uint64_t slot, uint64_t cnt
 }
 
 // hash_counter::add(key, val) with any 64-bit val
-__device__ inline bool nword_add_val(const NTable& T, const K256& key, uint64_t val) {
+__device__ inline bool nword_add_val(const NTable& T, const uint64_t* fwd, const K256& key, uint64_t val) {
   const TableGeom& g = T.N.g;
   const uint64_t lowpart = val & g.cnt_max, units = val >> g.cnt_bits;
   SlotAddr a;
-  if(!nword_addr(T, key, a)) return false;
+  if(!nword_addr(T, fwd, key, a)) return false;
   const bool is_new = nword_add_at<true>(T, key, a, lowpart);
   if(units) { const uint64_t s = nword_find_at(T, key, a); if(s != ~0ull) { const DevTable d = ovf_view(T); ovf_add(d, s, units); } }
   return is_new;
+}
+
+// update_add: increment only if the key is there (the UPDATE pass of `count --if`); the add always reads the old count back
+__device__ inline bool nword_update_add(const NTable& T, const uint64_t* fwd, const K256& key, uint64_t cnt) {
+  SlotAddr a;
+  if(!nword_addr(T, fwd, key, a)) return false;
+  const uint64_t s = nword_find_at(T, key, a);
+  if(s != ~0ull) nword_credit(T, s, cnt);
+  return s != ~0ull;
 }
 
 __device__ inline uint64_t nword_count_at(const NTable& T, const DevTable& d, uint64_t slot, uint64_t hi, int have_ovf) {
@@ -292,7 +301,7 @@ __global__ __launch_bounds__(kBlock) void count_ascii_nword_kernel(NTable T, con
     auto apply = [&](const K256& key, uint32_t n) {
       if(op == 0) nword_add<RETURNING>(T, key, n);
       else if(op == 1) nword_add<RETURNING>(T, key, 0);
-      else { const uint64_t s = nword_find(T, key); if(s != ~0ull) nword_credit(T, s, n); }
+      else { const uint64_t s = nword_find(T, T.fwd_tbl, key); if(s != ~0ull) nword_credit(T, s, n); }
     };
 #pragma unroll 1
     for(int j = 0; j < kPerLane; ++j) {
@@ -322,40 +331,29 @@ __device__ inline K256 load_key4(const uint64_t* keys, uint64_t i, uint32_t kw, 
   return k256_and(r, mask);
 }
 
-__global__ __launch_bounds__(kBlock) void add_keys_nword_kernel(NTable T, const uint64_t* __restrict__ keys, uint64_t n, uint32_t kw, uint64_t val,
-                                                                uint8_t* __restrict__ is_new) {
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const bool nw = nword_add_val(T, load_key4(keys, i, kw, T.N.key_mask), val);
-    if(is_new) is_new[i] = nw ? 1 : 0;
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void lookup_nword_kernel(NTable T, const uint64_t* __restrict__ keys, uint64_t n, uint32_t kw,
-                                                              uint64_t* __restrict__ vals, uint8_t* __restrict__ found, int have_ovf) {
-  const DevTable d = ovf_view(T);
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t s = nword_find(T, load_key4(keys, i, kw, T.N.key_mask));
-    vals[i] = s == ~0ull ? 0 : nword_count_at(T, d, s, T.slots[4 * s + 3], have_ovf);
-    if(found) found[i] = s != ~0ull;
-  }
-}
-
-// Slot access for the kernels that walk a whole table (KeyOps, kernels.hip.hpp).  A slot is looked at where it lies (in
+// Slot access for the kernels written once for every key width (KeyOps, kernels.hip.hpp).  A slot is looked at where it lies (in
 // the table, or in the dump's copy of it); only a complete one -- every word set -- holds a key, whatever the kernel.
 template <> struct KeyOps<NTable> {
   typedef K256 Key;
   struct Slot { const uint64_t* sp; };
   static constexpr int kSlotWords = kNWords;
+  static constexpr uint32_t kFwdLdsWords = 0;            // up to 32 x 256 words = 64 KiB: read through the caches
+  static constexpr bool kUpdateReturns = true;
   __device__ static const TableGeom& geom(const NTable& T) { return T.N.g; }
   __device__ static bool load(const NTable& T, uint64_t i, Slot& s) { s.sp = &T.slots[4 * i]; return nword_complete(s.sp); }
   __device__ static bool occupied(const NTable& T, uint64_t i, Slot& s) { return load(T, i, s); }
   __device__ static Slot slot_of(const uint64_t* w) { Slot s; s.sp = w; return s; }
   __device__ static uint64_t count(const NTable& T, const Slot& s, uint64_t i, int have_ovf) { return nword_count_at(T, ovf_view(T), i, s.sp[3], have_ovf); }
   __device__ static Key key(const NTable& T, const Slot& s, uint64_t tile_base) { return nword_slot_key(T, T.inv_tbl, s.sp, tile_base); }
-  __device__ static bool add_val(const NTable& T, const Key& key, uint64_t val) { return nword_add_val(T, key, val); }
-  __device__ static uint32_t owner(const NTable& T, const Key& key) { return slot_addr(T.N.g, hash_tables_n256(T.fwd_tbl, key, T.N.g.nbytes)).shard; }
+  __device__ static uint64_t count_at(const NTable& T, uint64_t i, int have_ovf) { return nword_count_at(T, ovf_view(T), i, T.slots[4 * i + 3], have_ovf); }
+  __device__ static const uint64_t* stage_fwd(const NTable& T) { return T.fwd_tbl; }
+  __device__ static bool add_val(const NTable& T, const uint64_t* H, const Key& key, uint64_t val) { return nword_add_val(T, H, key, val); }
+  template <bool RETURNING>
+  __device__ static bool update_add(const NTable& T, const uint64_t* H, const Key& key, uint64_t cnt) { static_assert(RETURNING, "kUpdateReturns"); return nword_update_add(T, H, key, cnt); }
+  __device__ static uint64_t find(const NTable& T, const uint64_t* H, const Key& key) { return nword_find(T, H, key); }
+  __device__ static uint32_t owner(const NTable& T, const uint64_t* H, const Key& key) { return slot_addr(T.N.g, hash_tables_n256(H, key, T.N.g.nbytes)).shard; }
   __device__ static void store_key(uint64_t* dst, const Key& key, uint32_t kw) { for(uint32_t q = 0; q < kw; ++q) dst[q] = key.w[q]; }
-  __device__ static Key load_key(const NTable& T, const uint64_t* keys, uint64_t i, uint32_t kw) { return load_key4(keys, i, kw, T.N.key_mask); }
+  __device__ static Key load_key(const NTable& T, const uint64_t* keys, uint64_t i, uint32_t kw, bool) { return load_key4(keys, i, kw, T.N.key_mask); }   // (masked either way)
   __device__ static uint64_t digest(const NTable& T, const Key& key, uint64_t c) {
     uint64_t h = kDigestSeed;
     for(uint32_t q = 0; q < (T.N.g.k + 31) / 32; ++q) h = digest_mix(h ^ key.w[q]);
@@ -363,18 +361,6 @@ template <> struct KeyOps<NTable> {
   }
   __device__ static uint8_t key_byte(const Key& key, uint32_t b) { return (uint8_t)(key.w[b >> 3] >> (8 * (b & 7))); }
 };
-
-// hash_counter::update_add on encoded keys of kw words, val == 1: the receive side of the exchange in the UPDATE pass of
-// count --if over shards (the two-word twin is update_keys_wide_kernel).  A key of another shard is counted as misrouted.
-__global__ __launch_bounds__(kBlock) void update_keys_nword_kernel(NTable T, const uint64_t* __restrict__ keys, uint64_t n, uint32_t kw) {
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const K256 key = load_key4(keys, i, kw, T.N.key_mask);
-    SlotAddr a;
-    if(!nword_addr(T, key, a)) continue;
-    const uint64_t s = nword_find_at(T, key, a);
-    if(s != ~0ull) nword_credit(T, s, 1);
-  }
-}
 
 // ---- multi-GPU: a contract buffer's k-mers grouped by owner (abi_comm.inl, key path) ---------------------------------
 // The two passes of partition_count / scatter_wide_kernel for 256-bit keys, reading the buffer like count_ascii_nword_kernel

@@ -153,31 +153,56 @@ __device__ inline bool wide_add(const WideTable& T, const uint64_t* fwd_lds, u12
   return false;
 }
 
+// Where `key` lives, or false when its position names another shard (counted: jfgpu_sync reports it).  A shard's tag is
+// that of the whole table (rem_bits = key_bits - lsize_g): the shard id is not in the slot, so nothing below may probe for a
+// key before this has been asked.
+__device__ inline bool wide_addr(const WideTable& T, const uint64_t* fwd_lds, u128 key, SlotAddr& a) {
+  a = slot_addr(T.W.g, hash_tables_wide(fwd_lds, key, T.W.g.nbytes));
+  if(a.shard == T.W.g.shard_id) return true;
+  atomicAdd((unsigned long long*)&T.counters[CTR_MISROUTED], 1ull);
+  return false;
+}
+
+// Slot holding `key` in the tile of `a`, or ~0 when it is absent (a look-up: the first never-claimed slot ends the search).
+__device__ inline uint64_t wide_find_at(const WideTable& T, u128 key, const SlotAddr& a) {
+  const TableGeom& g = T.W.g;
+  const WideSlot w = wide_words(T.W, key, a.idx0);
+  for(uint32_t p = 0; p <= T.max_probe; ++p) {
+    const uint64_t slot = a.tile_base + probe_slot(a.idx0, p, (uint32_t)g.tile_mask);
+    const uint64_t hi = __hip_atomic_load(&T.slots[2 * slot + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if(hi == 0) return ~0ull;
+    if((hi & g.low_mask) != w.hi_low) continue;
+    if(__hip_atomic_load(&T.slots[2 * slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == w.lo) return slot;
+  }
+  return ~0ull;
+}
+__device__ inline uint64_t wide_find(const WideTable& T, const uint64_t* fwd_lds, u128 key) {     // (a key of another shard is not here)
+  const SlotAddr a = slot_addr(T.W.g, hash_tables_wide(fwd_lds, key, T.W.g.nbytes));
+  return a.shard == T.W.g.shard_id ? wide_find_at(T, key, a) : ~0ull;
+}
+
+template <bool RETURNING>
+__device__ inline void wide_credit(const WideTable& T, uint64_t slot, uint64_t cnt) {    // add to an existing slot
+  const TableGeom& g = T.W.g;
+  unsigned long long* hp = (unsigned long long*)&T.slots[2 * slot + 1];
+  const uint64_t add = cnt << (g.tag_bits + 1);
+  if(RETURNING) {
+    const unsigned long long prev = atomicAdd(hp, (unsigned long long)add);
+    if((prev >> (g.tag_bits + 1)) + cnt > g.cnt_max) { const DevTable d = ovf_view(T); ovf_add(d, slot, 1); }
+  } else {
+    __hip_atomic_fetch_add(hp, (unsigned long long)add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // update_add on a 128-bit slot: increment only if the key is there (the UPDATE pass of `count --if`).
 template <bool RETURNING>
 __device__ inline bool wide_update_add(const WideTable& T, const uint64_t* fwd_lds, u128 key, uint64_t cnt) {
-  const TableGeom& g = T.W.g;
-  const uint64_t pos = hash_tables_wide(fwd_lds, key, g.nbytes);
-  const SlotAddr a = slot_addr(g, pos);
-  const WideSlot w = wide_words(T.W, key, a.idx0);
-  const uint64_t add = cnt << (g.tag_bits + 1);
-  const uint32_t tmask = (uint32_t)g.tile_mask;
-  for(uint32_t p = 0; p <= T.max_probe; ++p) {
-    const uint64_t slot = a.tile_base + probe_slot(a.idx0, p, tmask);
-    const uint64_t hi = __hip_atomic_load(&T.slots[2 * slot + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if(hi == 0) return false;
-    if((hi & g.low_mask) != w.hi_low) continue;
-    if(__hip_atomic_load(&T.slots[2 * slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != w.lo) continue;
-    unsigned long long* hp = (unsigned long long*)&T.slots[2 * slot + 1];
-    if(RETURNING) {
-      const unsigned long long prev = atomicAdd(hp, (unsigned long long)add);
-      if((prev >> (g.tag_bits + 1)) + cnt > g.cnt_max) { const DevTable d = ovf_view(T); ovf_add(d, slot, 1); }
-    } else {
-      __hip_atomic_fetch_add(hp, (unsigned long long)add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return true;
-  }
-  return false;
+  SlotAddr a;
+  if(!wide_addr(T, fwd_lds, key, a)) return false;
+  const uint64_t slot = wide_find_at(T, key, a);
+  if(slot == ~0ull) return false;
+  wide_credit<RETURNING>(T, slot, cnt);
+  return true;
 }
 
 // hash_counter::add(key, val) with an arbitrary 64-bit val: low part in the slot, the rest in the side table
@@ -186,17 +211,8 @@ __device__ inline bool wide_add_val(const WideTable& T, const uint64_t* fwd_lds,
   const uint64_t lowpart = val & g.cnt_max, units = val >> g.cnt_bits;
   const bool is_new = wide_add<true>(T, fwd_lds, key, lowpart);
   if(units) {   // find the slot again (cheap: rare) and credit the overflow units
-    const uint64_t pos = hash_tables_wide(fwd_lds, key, g.nbytes);
-    const SlotAddr a = slot_addr(g, pos);
-    const WideSlot w = wide_words(T.W, key, a.idx0);
-    for(uint32_t p = 0; p <= T.max_probe; ++p) {
-      const uint64_t slot = a.tile_base + probe_slot(a.idx0, p, (uint32_t)g.tile_mask);
-      const uint64_t hi = __hip_atomic_load(&T.slots[2 * slot + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if(hi == 0) break;
-      if((hi & g.low_mask) == w.hi_low && __hip_atomic_load(&T.slots[2 * slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == w.lo) {
-        const DevTable d = ovf_view(T); ovf_add(d, slot, units); break;
-      }
-    }
+    const uint64_t s = wide_find(T, fwd_lds, key);
+    if(s != ~0ull) { const DevTable d = ovf_view(T); ovf_add(d, s, units); }
   }
   return is_new;
 }
@@ -314,62 +330,14 @@ __device__ inline u128 load_key2(const uint64_t* keys, uint64_t i, u128 mask) {
   return (((u128)keys[2 * i + 1] << 64) | keys[2 * i]) & mask;
 }
 
-__global__ __launch_bounds__(kBlock) void add_keys_wide_kernel(WideTable T, const uint64_t* __restrict__ keys, uint64_t n, uint64_t val,
-                                                               uint8_t* __restrict__ is_new) {
-  __shared__ uint64_t s_fwd[16 * 256];
-  load_tables_lds(s_fwd, T.fwd_tbl, T.W.g.nbytes);
-  __syncthreads();
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const bool nw = wide_add_val(T, s_fwd, load_key2(keys, i, T.W.key_mask), val);
-    if(is_new) is_new[i] = nw ? 1 : 0;
-  }
-}
-
-// hash_counter::update_add on encoded two-word keys, val == 1: the receive side of the exchange in the UPDATE pass of
-// count --if over shards (count_main.cc:152-184 with --gpus; the one-word twin is update_keys_one_kernel)
-template <bool RETURNING>
-__global__ __launch_bounds__(kBlock) void update_keys_wide_kernel(WideTable T, const uint64_t* __restrict__ keys, uint64_t n) {
-  __shared__ uint64_t s_fwd[16 * 256];
-  load_tables_lds(s_fwd, T.fwd_tbl, T.W.g.nbytes);
-  __syncthreads();
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    wide_update_add<RETURNING>(T, s_fwd, load_key2(keys, i, T.W.key_mask), 1);
-}
-
-__global__ __launch_bounds__(kBlock) void lookup_wide_kernel(WideTable T, const uint64_t* __restrict__ keys, uint64_t n,
-                                                             uint64_t* __restrict__ vals, uint8_t* __restrict__ found, int have_ovf) {
-  __shared__ uint64_t s_fwd[16 * 256];
-  load_tables_lds(s_fwd, T.fwd_tbl, T.W.g.nbytes);
-  __syncthreads();
-  const TableGeom& g = T.W.g;
-  const DevTable d = ovf_view(T);
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const u128 key = load_key2(keys, i, T.W.key_mask);
-    const uint64_t pos = hash_tables_wide(s_fwd, key, g.nbytes);
-    const SlotAddr a = slot_addr(g, pos);
-    const WideSlot w = wide_words(T.W, key, a.idx0);
-    uint64_t val = 0; uint8_t fnd = 0;
-    for(uint32_t p = 0; p <= T.max_probe; ++p) {
-      const uint64_t slot = a.tile_base + probe_slot(a.idx0, p, (uint32_t)g.tile_mask);
-      const uint64_t hi = T.slots[2 * slot + 1];
-      if(hi == 0) break;
-      if((hi & g.low_mask) == w.hi_low && T.slots[2 * slot] == w.lo) {
-        val = slot_count(g, hi);
-        if(have_ovf) val += ovf_get(d, slot) << g.cnt_bits;
-        fnd = 1; break;
-      }
-    }
-    vals[i] = val;
-    if(found) found[i] = fnd;
-  }
-}
-
-// Slot access for the kernels that walk a whole table (KeyOps, kernels.hip.hpp): hash_counter::double_size, the scans,
-// the sorted dump and the redistribution between shards are written once there.  Hash tables are read through the caches.
+// Slot access for the kernels written once for every key width (KeyOps, kernels.hip.hpp): hash_counter::double_size, the
+// scans, the sorted dump, the redistribution between shards, and add, update_add and look-up of a list of keys.
 template <> struct KeyOps<WideTable> {
   typedef u128 Key;
   struct Slot { uint64_t lo, hi; };
   static constexpr int kSlotWords = 2;
+  static constexpr uint32_t kFwdLdsWords = 16 * 256;
+  static constexpr bool kUpdateReturns = false;
   __device__ static const TableGeom& geom(const WideTable& T) { return T.W.g; }
   // stats / histo / tile counts / dump: only the hi word (count + occupancy) matters, the lo word is never touched
   __device__ static bool occupied(const WideTable& T, uint64_t i, Slot& s) { s.lo = 0; s.hi = T.slots[2 * i + 1]; return s.hi != 0; }
@@ -384,11 +352,16 @@ template <> struct KeyOps<WideTable> {
     if(have_ovf) c += ovf_get(ovf_view(T), i) << T.W.g.cnt_bits;
     return c;
   }
+  __device__ static uint64_t count_at(const WideTable& T, uint64_t i, int have_ovf) { Slot s; occupied(T, i, s); return count(T, s, i, have_ovf); }
   __device__ static Key key(const WideTable& T, const Slot& s, uint64_t tile_base) { return wide_slot_key(T, T.inv_tbl, s.lo, s.hi, tile_base); }
-  __device__ static bool add_val(const WideTable& T, Key key, uint64_t val) { return wide_add_val(T, T.fwd_tbl, key, val); }
-  __device__ static uint32_t owner(const WideTable& T, Key key) { return slot_addr(T.W.g, hash_tables_wide(T.fwd_tbl, key, T.W.g.nbytes)).shard; }
+  __device__ static const uint64_t* stage_fwd(const WideTable& T) { return stage_tables_lds<kFwdLdsWords>(T.fwd_tbl, T.W.g.nbytes); }
+  __device__ static bool add_val(const WideTable& T, const uint64_t* H, Key key, uint64_t val) { return wide_add_val(T, H, key, val); }
+  template <bool RETURNING>
+  __device__ static bool update_add(const WideTable& T, const uint64_t* H, Key key, uint64_t cnt) { return wide_update_add<RETURNING>(T, H, key, cnt); }
+  __device__ static uint64_t find(const WideTable& T, const uint64_t* H, Key key) { return wide_find(T, H, key); }
+  __device__ static uint32_t owner(const WideTable& T, const uint64_t* H, Key key) { return slot_addr(T.W.g, hash_tables_wide(H, key, T.W.g.nbytes)).shard; }
   __device__ static void store_key(uint64_t* dst, Key key, uint32_t) { dst[0] = (uint64_t)key; dst[1] = (uint64_t)(key >> 64); }
-  __device__ static Key load_key(const WideTable&, const uint64_t* keys, uint64_t i, uint32_t) { return load_key2(keys, i, ~(u128)0); }   // (as they come: a pair's key was made by store_key or by the caller)
+  __device__ static Key load_key(const WideTable& T, const uint64_t* keys, uint64_t i, uint32_t, bool masked) { return load_key2(keys, i, masked ? T.W.key_mask : ~(u128)0); }
   __device__ static uint64_t digest(const WideTable&, Key key, uint64_t c) {
     return digest_mix(digest_mix(digest_mix(kDigestSeed ^ (uint64_t)key) ^ (uint64_t)(key >> 64)) ^ c);
   }

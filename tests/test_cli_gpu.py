@@ -874,7 +874,7 @@ def test_count_gpus_n_with_if_files(cli, tmp_path, k):
     """`count --if wanted.fa --gpus 2` (count_main.cc:289-295 with hash-prefix shards; round-3 review, missing #1): the rank
     processes prime their shards with the --if k-mers (each reads its part of the file, every k-mer travels to its owner),
     then count only those; the file equals the single-process one.  k = 40 (round 6): shards of two-word keys -- the PRIME
-    pass adds with value 0, the UPDATE pass goes through update_keys_wide_kernel on arrival."""
+    pass adds with value 0, the UPDATE pass goes through update_keys_kernel<WideTable> on arrival."""
     import random
     rng = random.Random(77)
     wanted = ["".join(rng.choice("ACGT") for _ in range(200)) for _ in range(600)]

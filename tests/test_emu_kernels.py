@@ -40,6 +40,13 @@ SELECTION = [
     "tests/test_gpu_bloom.py::test_sharded_count_with_a_bloom_counter_equals_the_single_table[21-2-2]",
     "tests/test_gpu_bloom.py::test_count_bc_with_the_cache_of_admitted_kmers[bc_k21C-2]",
     "tests/test_gpu_bloom.py::test_bloom_counters_of_the_ranks_merge_into_the_counter_of_the_whole_input[2]",
+    "tests/test_gpu_wide.py::test_lookup_refuses_the_twin_key_of_the_other_shard[40]",
+    "tests/test_gpu_wide.py::test_lookup_refuses_the_twin_key_of_the_other_shard[21]",
+    "tests/test_gpu_wide.py::test_lookup_refuses_the_twin_key_of_the_other_shard[100]",
+    "tests/test_gpu_wide.py::test_prime_and_update_over_two_word_shards",
+    "tests/test_gpu_wide.py::test_add_keys_is_new_and_lookup_at_every_key_width[21]",
+    "tests/test_gpu_wide.py::test_add_keys_is_new_and_lookup_at_every_key_width[40]",
+    "tests/test_gpu_wide.py::test_add_keys_is_new_and_lookup_at_every_key_width[100]",
 ]
 
 

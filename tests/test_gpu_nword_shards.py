@@ -1,8 +1,8 @@
 """Hash-prefix shards of tables of keys of three and four words, 65 <= k <= 128 (-m gpu).
 
 Every rank routes the 256-bit k-mers of its input by owner (partition_count / scatter_nword_kernel), a message carries
-ceil(2k / 64) words per k-mer (3 for k <= 96, 4 above), receivers insert with the four-word claim (add_keys_nword_kernel)
-or, in the UPDATE pass of `count --if`, count what is present (update_keys_nword_kernel).  Shards grow together
+ceil(2k / 64) words per k-mer (3 for k <= 96, 4 above), receivers insert with the four-word claim (add_keys_kernel<NTable>)
+or, in the UPDATE pass of `count --if`, count what is present (update_keys_kernel<NTable, true>).  Shards grow together
 (reshard_kernel<NTable>, add_pairs_kernel<NTable>), and a step is cut into pieces whose send buffers stay under a byte budget
 (JFGPU_COMM_PIECE_BYTES).  What the shards hold is what one table holds."""
 import hashlib
@@ -175,7 +175,7 @@ def test_nword_shards_grow_together(gpu, k, world):
 
 def test_prime_and_update_over_nword_shards(gpu):
     """The two passes of `count --if` over shards of 100-mers: PRIME with one sequence set (count 0), UPDATE with reads that
-    overlap it in part (counted only if present, update_keys_nword_kernel).  The result equals one table run through the
+    overlap it in part (counted only if present, update_keys_kernel<NTable, true>).  The result equals one table run through the
     same two operations, keys primed with count 0 included, and the oracle."""
     rng = random.Random(100)
     k, world = 100, 2

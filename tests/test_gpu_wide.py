@@ -475,3 +475,138 @@ def test_two_word_shards_grow_together(gpu, k, world):
         comm.close()
         for t in shards:
             t.close()
+
+
+def rnd_keys(rng, n, k):
+    """n distinct random keys of k bases, (n, words) little-endian words."""
+    kw = (2 * k + 63) // 64
+    seen = set()
+    while len(seen) < n:
+        seen.add(rng.getrandbits(2 * k))
+    return np.array([[(v >> (64 * q)) & (2 ** 64 - 1) for q in range(kw)] for v in sorted(seen, key=lambda _: rng.random())], dtype=np.uint64)
+
+
+@pytest.mark.parametrize("k", [40, 21, 100])
+def test_lookup_refuses_the_twin_key_of_the_other_shard(gpu, k):
+    """A shard's slot does not hold the shard id (the tag is that of the whole table), so a look-up has to ask whose the
+    key is before it probes.  Two shards of one small table under one matrix; the map key -> position is linear over GF(2)
+    and one-to-one on the low lsize bits of the key, so exactly one d < 2^lsize has the single top position bit as its
+    position: K ^ d has K's local position and K's remainder, on the other shard.  K is found with its count on its owner
+    only; K ^ d is found nowhere.  (Before the keyed kernels were written once, the two-word look-up answered K's count for
+    K ^ d on K's owner; k = 21 and k = 100 guard the widths that always asked.)"""
+    rng = random.Random(k)
+    kw = (2 * k + 63) // 64
+    with gpu.Table(k, 1 << 14) as single:
+        cols = single.matrix()
+        lsize_g = single.info.lsize
+    shards = [gpu.Table(k, 1 << lsize_g, shard_bits=1, shard_id=r, matrix_columns=cols) for r in range(2)]
+    try:
+        assert all(t.info.lsize == lsize_g for t in shards) and lsize_g <= 18
+        low = np.zeros((1 << lsize_g, kw), dtype=np.uint64)
+        low[:, 0] = np.arange(1 << lsize_g, dtype=np.uint64)
+        hit = np.flatnonzero(O.matrix_times(cols, lsize_g, 2 * k, low) == np.uint64(1 << (lsize_g - 1)))
+        assert len(hit) == 1
+        d = np.uint64(hit[0])
+        keys = rnd_keys(rng, 300, k)
+        twins = keys.copy()
+        twins[:, 0] ^= d
+        assert not {tuple(r) for r in twins.tolist()} & {tuple(r) for r in keys.tolist()}
+        owner = (O.matrix_times(cols, lsize_g, 2 * k, keys) >> np.uint64(lsize_g - 1)).astype(np.int64)
+        assert (owner != (O.matrix_times(cols, lsize_g, 2 * k, twins) >> np.uint64(lsize_g - 1)).astype(np.int64)).all()
+        assert 50 < owner.sum() < 250
+        cnt = np.array([1 + i % 3 for i in range(len(keys))], dtype=np.uint64)
+        for r, t in enumerate(shards):
+            for c in (1, 2, 3):
+                t.add_keys(keys[(owner == r) & (cnt >= c)])
+            t.sync()
+        for r, t in enumerate(shards):
+            mine = owner == r
+            vals, found = t.lookup(keys)
+            assert (found == mine).all() and (vals[mine] == cnt[mine]).all() and not vals[~mine].any()
+            vals, found = t.lookup(twins)
+            assert not found.any() and not vals.any()
+            t.sync()
+    finally:
+        for t in shards:
+            t.close()
+
+
+def test_prime_and_update_over_two_word_shards(gpu):
+    """The two passes of `count --if` at k = 40, on one table and over two shards (tests/test_gpu_parity.py:
+    test_prime_and_update_over_shards is the one-word twin): PRIME enters a sequence set with count 0, UPDATE counts reads
+    that overlap it in part only where the key is present -- count_ascii_wide_kernel with op 1 and 2 on the single table,
+    update_keys_kernel<WideTable> for what a shard receives.  Both equal the oracle, keys primed and never seen included."""
+    rng = random.Random(40)
+    k, world = 40, 2
+    wanted = [rnd_seq(rng, 6000) for _ in range(world)]
+    reads = [wanted[r][1000:4000] + b"N" + rnd_seq(rng, 5000) + b"N" + wanted[(r + 1) % world][500:2500] for r in range(world)]
+    exp_w = oracle_map(b"N".join(wanted), k, True)
+    exp_r = oracle_map(b"N".join(reads), k, True)
+    exp = {key: exp_r.get(key, 0) for key in exp_w}
+    assert sum(exp.values()) > 1000 and any(v == 0 for v in exp.values())
+    with gpu.Table(k, 1 << 16) as single:
+        single.set_operation(1); single.count_ascii(b"N".join(wanted)); single.sync()
+        single.set_operation(2); single.count_ascii(b"N".join(reads)); single.sync()
+        assert table_map(gpu, single) == exp
+        cols = single.matrix()
+        lsize_g = single.info.lsize
+    shards = [gpu.Table(k, 1 << lsize_g, shard_bits=1, shard_id=r, matrix_columns=cols) for r in range(world)]
+    comm = gpu.Comm(world, local=True)
+    try:
+        bufs = []
+
+        def feed(seqs):
+            ptrs, ns = [], []
+            for r, seq in enumerate(seqs):
+                d = shards[r].malloc(len(seq) + 64)
+                shards[r].h2d(d, np.frombuffer(seq, dtype=np.uint8))
+                bufs.append((shards[r], d)); ptrs.append(d); ns.append(len(seq))
+            comm.local_step(shards, ptrs, ns)
+            comm.finish()
+        for t in shards:
+            t.set_operation(1)
+        feed(wanted)
+        for t in shards:
+            t.sync()
+        assert sum(t.stats().distinct for t in shards) == len(exp_w) and sum(t.stats().total for t in shards) == 0
+        for t in shards:
+            t.set_operation(2)
+        feed(reads)
+        got = {}
+        for t in shards:
+            t.sync()
+            part = table_map(gpu, t)
+            assert part and not (set(part) & set(got))
+            got.update(part)
+        assert got == exp
+        for t, d in bufs:
+            t.free(d)
+    finally:
+        comm.close()
+        for t in shards:
+            t.close()
+
+
+@pytest.mark.parametrize("k", [21, 40, 100])
+def test_add_keys_is_new_and_lookup_at_every_key_width(gpu, k):
+    """test_wide_add_keys_and_overflow's hash_counter::add / get_val_for_key checks at one, two and four key words, which
+    share add_keys_kernel and lookup_kernel: a first add is new everywhere, a second is new nowhere and adds up, absent
+    keys are not found and read 0, and a value wider than the slot's count field comes back exactly from the side table
+    (2^50 + 7 where the field is narrower than 50 bits; a table of 100-mers this small has 57, so 2 bits above the field)."""
+    rng = random.Random(k + 1)
+    with gpu.Table(k, 1 << 16, canonical=False) as t:
+        allk = rnd_keys(rng, 3500, k)
+        keys, absent = allk[:3000], allk[3000:]
+        assert t.add_keys(keys, val=3, want_new=True).all()
+        assert not t.add_keys(keys[:100], val=2, want_new=True).any()
+        vals, found = t.lookup(keys)
+        assert found.all() and vals[:100].tolist() == [5] * 100 and vals[100:].tolist() == [3] * 2900
+        vals, found = t.lookup(absent)
+        assert not found.any() and not vals.any()
+        big = 2 ** max(50, t.info.val_len + 2) + 7
+        assert t.info.val_len < 62 and big >> t.info.val_len
+        assert t.add_keys(absent[:1], val=big, want_new=True).all()
+        vals, found = t.lookup(absent[:2])
+        assert found.tolist() == [True, False] and vals.tolist() == [big, 0]
+        st = t.stats()
+        assert st.distinct == 3001 and st.max_count == big

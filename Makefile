@@ -1,6 +1,7 @@
 # Top-level build: the gfx950 engine (libjfgpu.so), the host CLI, the oracle.
 #   make            -> engine + CLI + oracle
 #   make engine     -> jellyfish_amd/lib/libjfgpu.so   (hipcc cross-compiles without a GPU)
+#   make kernel-harness -> tests/kernels/_build/libjfgpu_kt.so   (the stage tests' library; not product)
 HIPCC    ?= hipcc
 CXX      ?= g++
 ARCH     ?= gfx950
@@ -16,6 +17,15 @@ $(LIBDIR)/libjfgpu.so: $(wildcard $(CSRC)/*.hip) $(wildcard $(CSRC)/*.hpp) $(wil
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/jfgpu.hip -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
+# test infrastructure, not product: the engine's translation unit plus entry points that launch one stage of the
+# partitioned insert path alone (tests/kernels/stage_harness.hip; tests/test_gpu_stage_*.py)
+KTDIR    := tests/kernels/_build
+kernel-harness: $(KTDIR)/libjfgpu_kt.so
+
+$(KTDIR)/libjfgpu_kt.so: tests/kernels/stage_harness.hip $(wildcard $(CSRC)/*.hip) $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/*.inl) include/jfgpu.h
+	@mkdir -p $(KTDIR)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ tests/kernels/stage_harness.hip -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+
 cli: bin/jellyfish-amd
 
 bin/jellyfish-amd: $(wildcard jellyfish_amd/cli/*.cc) $(wildcard jellyfish_amd/include/jellyfish_amd/*.hpp) include/jfgpu.h $(LIBDIR)/libjfgpu.so
@@ -28,5 +38,5 @@ oracle:
 	$(MAKE) -C oracle all
 
 clean:
-	rm -rf $(LIBDIR) bin oracle/_build
-.PHONY: all engine cli oracle clean
+	rm -rf $(LIBDIR) bin oracle/_build $(KTDIR)
+.PHONY: all engine cli oracle clean kernel-harness

@@ -468,6 +468,10 @@ __global__ __launch_bounds__(256) void p1_stragglers_kernel(DIRECT D, unsigned l
       if(cnt == 1 && item != (ITEM)~(ITEM)0) {
         const uint32_t at = atomicAdd(&gcur[b], 1u);
         if(at < cap) { out[(uint64_t)b * cap + at] = item; if(tot) atomicAdd(&tot[b], 1ull); continue; }
+        // the region is full: the add above went past its end, and the cursor is taken back to it -- never below, so no
+        // place is handed out twice -- so that behind this kernel gcur[b] <= cap says how far a single-writer region is
+        // filled (granule_finish_kernel clamps too; tests/test_gpu_stage_p2.py reads the cursor itself)
+        atomicMin(&gcur[b], cap);
       }
       D(b, item, cnt);
       ++my_direct;

@@ -1,0 +1,295 @@
+// tests/kernels/stage_harness.hip -- TEST INFRASTRUCTURE: the engine's translation unit plus entry points (jfkt_*) that
+// launch ONE stage of the partitioned insert path -- P1 (p1_ring_kernel), P2 (p2_ring_roles_kernel / p2_ring_kernel, each
+// followed by p1_stragglers_kernel), T (tile_rank_insert_kernel) -- with the caller's arguments and copy its outputs back.
+//
+// The engine is one translation unit, so including it here gives the harness the anonymous namespace, jfgpu_table, the
+// descriptors and the kernels.  The library built from this file is a superset of the engine: a table made by ITS
+// jfgpu_create is what the launches take and what lookup / dump / stats / digest read back.  Never hand a handle made by
+// one library to the other.  Nothing here is part of the product; the product library does not change.
+//
+// The ring kernels are instantiated with a DIRECT functor that RECORDS its calls -- (destination, item, occurrences) into
+// a list with a counter -- so that what the product inserts with global atomics (a side effect somewhere in a table)
+// becomes an output a test can compare.  Template arguments are the ones host_partition.inl launches.
+//
+// Two builds: hipcc --offload-arch=gfx950 (make kernel-harness -> tests/kernels/_build/libjfgpu_kt.so) and
+// g++ -DJFGPU_EMU -Itests/host/hip_emu (tests/host/build_kt_emu.sh -> tests/host/_build/libjfgpu_kt_emu.so).
+#include "../../jellyfish_amd/csrc/jfgpu.hip"
+
+namespace {
+
+// DIRECT of the ring kernels and of p1_stragglers_kernel: the call is written down, nothing is inserted
+struct RecordDirect {
+  static constexpr bool kCountsDirect = true;
+  uint64_t* rec; unsigned long long* n; uint64_t cap;          // rec[3 i]: destination, item, occurrences
+  __device__ void operator()(uint32_t dest, uint64_t item, uint32_t cnt) const {
+    const unsigned long long at = atomicAdd(n, 1ull);
+    if(at < cap) { rec[3 * at] = dest; rec[3 * at + 1] = item; rec[3 * at + 2] = cnt; }
+  }
+};
+
+// device buffers of one call, freed when it returns
+struct DevBufs {
+  std::vector<void*> p;
+  ~DevBufs() { for(void* q : p) hipFree(q); }
+  template <typename T> int get(T** out, size_t n, int fill = -1) {
+    *out = nullptr;
+    void* q = nullptr;
+    HIP_TRY(hipMalloc(&q, std::max<size_t>(n * sizeof(T), 16)));
+    p.push_back(q);
+    if(fill >= 0) HIP_TRY(hipMemset(q, fill, std::max<size_t>(n * sizeof(T), 16)));
+    *out = (T*)q;
+    return JFGPU_OK;
+  }
+  template <typename T> int put(T** out, const T* host, size_t n, size_t pad = 0) {
+    int rc = get(out, n + pad, 0); if(rc) return rc;
+    if(n) HIP_TRY(hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice));
+    return JFGPU_OK;
+  }
+};
+#define KT_TRY(expr) do { int rc_ = (expr); if(rc_) return rc_; } while(0)
+
+void say(char* dst, size_t len, const std::string& s) { if(dst && len) { strncpy(dst, s.c_str(), len - 1); dst[len - 1] = 0; } }
+
+int kt_ring_attrs() {
+  static bool done = false;
+  if(done) return JFGPU_OK;
+  const int rl = kGranMaxB * 128 + 128;                         // (the engine's own value: jfgpu_create)
+  HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_kernel<RecordDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
+#define KT_A(NV, PD) HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_roles_kernel<uint32_t, NV, RecordDirect, PD>, hipFuncAttributeMaxDynamicSharedMemorySize, rl))
+  KT_A(1, 1); KT_A(1, 2); KT_A(1, 3); KT_A(2, 1); KT_A(2, 2); KT_A(2, 3);
+#undef KT_A
+#define KT_A(N, CN) HIP_TRY(hipFuncSetAttribute((const void*)p1_ring_kernel<uint32_t, false, N, CN, RecordDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, rl))
+  KT_A(0, 2); KT_A(6, 0); KT_A(6, 1); KT_A(kHashXSLow, 2);
+#undef KT_A
+  done = true;
+  return JFGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The kernels' constants, for tests that walk the round structure:
+// 0 kPBlock  1 kP2StragPerBlock  2 kStragPerBlock  3 kGran  4 Ring<uint32_t>::kSlots  5 Ring<uint32_t>::kUnit  6 kTileBlock
+// 7 items of a tile round (4-byte items)  8 the same for 8-byte items  9 kMaxTileBits  10 kBucketBits  11 kPTilePos
+// 12 kG2Blocks  13 kTileQueueBytes
+uint64_t jfkt_const(int which) {
+  switch(which) {
+    case 0: return kPBlock;
+    case 1: return kP2StragPerBlock;
+    case 2: return kStragPerBlock;
+    case 3: return kGran;
+    case 4: return Ring<uint32_t>::kSlots;
+    case 5: return Ring<uint32_t>::kUnit;
+    case 6: return kTileBlock;
+    case 7: return 9216;
+    case 8: return 4608;
+    case 9: return kMaxTileBits;
+    case 10: return kBucketBits;
+    case 11: return kPTilePos;
+    case 12: return kG2Blocks;
+    case 13: return kTileQueueBytes;
+  }
+  return 0;
+}
+
+// The table's geometry as the kernels see it (TableGeom), for tests that restate make_item:
+// 0 lsize_l 1 tile_bits 2 rem_bits 3 tag_bits 4 cnt_bits 5 slot32 6 hash_xs 7 nbytes 8 returning 9 part_ok 10 b1 11 b2
+// 12 rest_shift 13 item32 14 lsize_g 15 canonical
+int jfkt_geom(jfgpu_table* t, uint64_t* out, uint32_t n) {
+  if(!t || !out) return fail(JFGPU_E_INVALID, "null argument");
+  const uint64_t v[16] = {t->g.lsize_l, t->g.tile_bits, t->g.rem_bits, t->g.tag_bits, t->g.cnt_bits, t->g.slot32, t->g.hash_xs, t->g.nbytes,
+                          (uint64_t)t->returning, (uint64_t)t->part_ok, t->pg.b1, t->pg.b2, t->pg.rest_shift, (uint64_t)t->item32, t->g.lsize_g, t->g.canonical};
+  for(uint32_t i = 0; i < n && i < 16; ++i) out[i] = v[i];
+  return JFGPU_OK;
+}
+
+// ---- P2 alone ---------------------------------------------------------------------------------------------------------
+// kernel: 0 p2_ring_roles_kernel<uint32_t, nv, RecordDirect, pd>, 1 p2_ring_kernel<RecordDirect> (kG2Blocks workgroups a
+// bucket); then p1_stragglers_kernel<uint32_t, RecordDirect> over the launch's lists, as launch_p2_rings does.
+// seg_items[s] / seg_off[s]: host arrays of segment s (n_items[s] items, n_off[s] offsets; sh[s] as SegList::sh).
+// out: n_dest * cap items, in and out (the caller's sentinels come back where nothing was written).
+// gcur: 2 * n_dest words out (cursors, then p2_ring_kernel's overflow notes), zero before the launch.
+// rec: 3 * rec_cap words out, n_rec the number of DIRECT calls made (it may exceed rec_cap), ctr_direct what the kernels
+// added to their direct counter, strag_n the lists' lengths (nbk, or kG2Blocks * nbk).
+int jfkt_p2(jfgpu_table* t, int kernel, int nv, int pd, uint32_t b2e, uint32_t tag_bits, uint32_t n_seg,
+            const void* const* seg_items, const uint64_t* n_items, const uint64_t* const* seg_off, const uint64_t* n_off, const uint32_t* sh,
+            uint32_t cap, uint32_t bucket0, uint32_t nbk, uint32_t n_dest, uint32_t* out, uint32_t* gcur,
+            uint64_t* rec, uint64_t rec_cap, uint64_t* n_rec, uint64_t* ctr_direct, uint32_t* strag_n, char* launched, size_t launched_len) {
+  int rc = use(t); if(rc) return rc;
+  if(!n_seg || n_seg > (uint32_t)kMaxSeg || !nbk || !cap) return fail(JFGPU_E_INVALID, "jfkt_p2: bad segment count, bucket count or capacity");
+  if(b2e > 10 || (kernel == 0 && b2e != (nv == 2 ? 10u : 9u))) return fail(JFGPU_E_INVALID, "jfkt_p2: the host launches NV = 2 at 1024 destinations and NV = 1 at 512");
+  if(kernel == 0 && (nv < 1 || nv > 2 || pd < 1 || pd > 3)) return fail(JFGPU_E_INVALID, "jfkt_p2: NV in {1, 2}, PD in {1, 2, 3}");
+  if(kernel == 1 && b2e != 10) return fail(JFGPU_E_INVALID, "jfkt_p2: the shared-ring kernel is for 1024 destinations");
+  if(((uint64_t)(bucket0 + nbk) << b2e) > n_dest) return fail(JFGPU_E_INVALID, "jfkt_p2: launched destinations beyond n_dest");
+  if(cap % 4) return fail(JFGPU_E_INVALID, "jfkt_p2: regions start at multiples of 16 bytes");
+  for(uint32_t s = 0; s < n_seg; ++s) {
+    // what the kernels read must be inside what is allocated: offsets of every launched bucket within the items
+    const uint64_t need = ((uint64_t)(bucket0 + nbk - 1) << sh[s]) + 2;
+    if(sh[s] > 1 || n_off[s] < need) return fail(JFGPU_E_INVALID, "jfkt_p2: offsets do not cover the launched buckets");
+    if(kernel == 1 && sh[s] != 1) return fail(JFGPU_E_INVALID, "jfkt_p2: the shared-ring kernel takes granule segments only");
+    for(uint32_t j = bucket0; j < bucket0 + nbk; ++j) {
+      const uint64_t a = seg_off[s][(size_t)j << sh[s]], b = seg_off[s][((size_t)j << sh[s]) + 1];
+      if(a > b || b > n_items[s]) return fail(JFGPU_E_INVALID, "jfkt_p2: a bucket's range lies outside its segment");
+      if(sh[s] == 1 && (a % 4)) return fail(JFGPU_E_INVALID, "jfkt_p2: a granule region starts at a multiple of 16 bytes");
+    }
+  }
+  KT_TRY(kt_ring_attrs());
+  DevBufs D;
+  SegList S; memset(&S, 0, sizeof S);
+  S.n = n_seg;
+  for(uint32_t s = 0; s < n_seg; ++s) {
+    uint32_t* di; uint64_t* doff;
+    KT_TRY(D.put(&di, (const uint32_t*)seg_items[s], (size_t)n_items[s], 4));      // (+ 16 bytes: nothing reads them, a wrong bound would)
+    KT_TRY(D.put(&doff, seg_off[s], (size_t)n_off[s]));
+    S.items[s] = di; S.off[s] = doff; S.sh[s] = sh[s];
+  }
+  const uint32_t n_lists = kernel == 0 ? nbk : kG2Blocks * nbk;
+  uint32_t *d_out, *d_strag_n; unsigned int* d_gcur; uint64_t *d_strag, *d_rec; unsigned long long *d_nrec, *d_ctr;
+  KT_TRY(D.put(&d_out, out, (size_t)n_dest * cap));
+  KT_TRY(D.get(&d_gcur, 2 * (size_t)n_dest, 0));
+  KT_TRY(D.get(&d_strag, (size_t)n_lists * kP2StragPerBlock, 0));
+  KT_TRY(D.get(&d_strag_n, n_lists, 0));
+  KT_TRY(D.get(&d_rec, 3 * (size_t)rec_cap, 0));
+  KT_TRY(D.get(&d_nrec, 1, 0));
+  KT_TRY(D.get(&d_ctr, 1, 0));
+  const RecordDirect pd_{d_rec, d_nrec, rec_cap};
+  const size_t lds = ((size_t)1 << b2e) * 128 + 128;                              // (launch_p2_rings)
+  std::string name;
+#define KT_P2R(NV, PD) do { hipLaunchKernelGGL((p2_ring_roles_kernel<uint32_t, NV, RecordDirect, PD>), dim3(nbk), dim3(kPBlock), lds, t->stream, pd_, b2e, tag_bits, S, cap, d_gcur, d_out, bucket0, d_strag, d_strag_n, d_ctr); \
+                            name = "p2_ring_roles_kernel<uint32_t," #NV ",RecordDirect," #PD ">"; } while(0)
+  if(kernel == 0 && nv == 2) { if(pd == 1) KT_P2R(2, 1); else if(pd == 2) KT_P2R(2, 2); else KT_P2R(2, 3); }
+  else if(kernel == 0) { if(pd == 1) KT_P2R(1, 1); else if(pd == 2) KT_P2R(1, 2); else KT_P2R(1, 3); }
+#undef KT_P2R
+  else {
+    hipLaunchKernelGGL((p2_ring_kernel<RecordDirect>), dim3(kG2Blocks, nbk), dim3(kPBlock), lds, t->stream, pd_, b2e, tag_bits, S, cap, d_gcur, d_gcur + n_dest,
+                       d_out, bucket0, (unsigned long long*)nullptr, d_strag, d_strag_n, d_ctr);
+    name = "p2_ring_kernel<RecordDirect>";
+  }
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL((p1_stragglers_kernel<uint32_t, RecordDirect>), dim3(t->n_cu), dim3(256), 0, t->stream, pd_, d_ctr, (const uint64_t*)d_strag, (const uint32_t*)d_strag_n,
+                     n_lists, cap, d_gcur, (unsigned long long*)nullptr, d_out, kP2StragPerBlock);
+  name += "+p1_stragglers_kernel<uint32_t,RecordDirect>";
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  HIP_TRY(hipMemcpy(out, d_out, (size_t)n_dest * cap * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(gcur, d_gcur, 2 * (size_t)n_dest * 4, hipMemcpyDeviceToHost));
+  if(rec_cap) HIP_TRY(hipMemcpy(rec, d_rec, 3 * (size_t)rec_cap * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n_rec, d_nrec, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ctr_direct, d_ctr, 8, hipMemcpyDeviceToHost));
+  if(strag_n) HIP_TRY(hipMemcpy(strag_n, d_strag_n, (size_t)n_lists * 4, hipMemcpyDeviceToHost));
+  say(launched, launched_len, name);
+  return JFGPU_OK;
+}
+
+// ---- T alone ----------------------------------------------------------------------------------------------------------
+// tile_rank_insert_kernel<ITEM, table's RETURNING, table's SLOT, tpb, kTileBlock, heavy, sample, holes> over n_units units
+// from tile `tile0` of the table, one item array: unit u is items[off[u << sh] .. off[(u << sh) + 1]).  The instantiations
+// are the host's (launch_tile_rank_variant): pairs of tiles for 4-byte items into 32-bit slots only, the hole-free one for
+// the plain and the sampling kernel on such pairs only.  grid: workgroups (0: one per unit).
+int jfkt_tile(jfgpu_table* t, int tpb, int heavy, int sample, int holes, uint32_t item_bytes, const void* items, uint64_t n_items,
+              const uint64_t* off, uint64_t n_off, uint32_t sh, uint64_t tile0, uint32_t n_units, uint32_t grid, char* launched, size_t launched_len) {
+  int rc = use(t); if(rc) return rc;
+  if(t->wide || t->nword || t->g.tile_bits != kMaxTileBits) return fail(JFGPU_E_INVALID, "jfkt_tile: one-word keys, full-size tiles");
+  if((tpb != 1 && tpb != 2) || (item_bytes != 4 && item_bytes != 8) || sh > 1 || !n_units) return fail(JFGPU_E_INVALID, "jfkt_tile: bad arguments");
+  if(tpb == 2 && !(item_bytes == 4 && t->g.slot32)) return fail(JFGPU_E_INVALID, "jfkt_tile: pairs of tiles take 4-byte items into 32-bit slots");
+  if(heavy && sample) return fail(JFGPU_E_INVALID, "jfkt_tile: the sampling kernel is the plain one");
+  if(!holes && !(tpb == 2 && !heavy)) return fail(JFGPU_E_INVALID, "jfkt_tile: the hole-free instantiation is the plain kernel's on pairs of tiles");
+  if(tile0 + (uint64_t)tpb * n_units > n_tiles_of(t)) return fail(JFGPU_E_INVALID, "jfkt_tile: units beyond the table");
+  if(n_off < (((uint64_t)n_units - 1) << sh) + 2) return fail(JFGPU_E_INVALID, "jfkt_tile: offsets do not cover the units");
+  for(uint32_t u = 0; u < n_units; ++u) {
+    const uint64_t a = off[(size_t)u << sh], b = off[((size_t)u << sh) + 1];
+    if(a > b || b > n_items) return fail(JFGPU_E_INVALID, "jfkt_tile: a unit's range lies outside the items");
+  }
+  DevBufs D;
+  uint8_t* d_items; uint64_t* d_off;
+  KT_TRY(D.put(&d_items, (const uint8_t*)items, (size_t)n_items * item_bytes, 16));
+  KT_TRY(D.put(&d_off, off, (size_t)n_off));
+  SegList S; memset(&S, 0, sizeof S);
+  S.n = 1; S.items[0] = d_items; S.off[0] = d_off; S.sh[0] = sh; S.dense[0] = holes ? 0 : 1;
+  const dim3 g(grid ? std::min(grid, n_units) : n_units), block(kTileBlock);
+  const size_t lds = tile_rank_lds(t->g.slot32 ? 4 : 8, t->g.tile_bits, tpb);
+  const bool rt = t->returning;
+  std::string name;
+#define KT_T(I, SL, P, H, M, HL) do { \
+    if(rt) hipLaunchKernelGGL((tile_rank_insert_kernel<I, true, SL, P, kTileBlock, H, M, HL>), g, block, lds, t->stream, t->dt, S, tile0, n_units); \
+    else   hipLaunchKernelGGL((tile_rank_insert_kernel<I, false, SL, P, kTileBlock, H, M, HL>), g, block, lds, t->stream, t->dt, S, tile0, n_units); \
+    name = std::string("tile_rank_insert_kernel<" #I ",") + (rt ? "true" : "false") + "," #SL "," #P ",kTileBlock," #H "," #M "," #HL ">"; } while(0)
+#define KT_TV(I, SL, P) do { if(heavy) KT_T(I, SL, P, true, false, true); else if(sample) KT_T(I, SL, P, false, true, true); else KT_T(I, SL, P, false, false, true); } while(0)
+  if(!holes) { if(sample) KT_T(uint32_t, unsigned int, 2, false, true, false); else KT_T(uint32_t, unsigned int, 2, false, false, false); }
+  else if(item_bytes == 4 && t->g.slot32 && tpb == 2) KT_TV(uint32_t, unsigned int, 2);
+  else if(item_bytes == 4 && t->g.slot32) KT_TV(uint32_t, unsigned int, 1);
+  else if(item_bytes == 4) KT_TV(uint32_t, unsigned long long, 1);
+  else if(t->g.slot32) KT_TV(uint64_t, unsigned int, 1);
+  else KT_TV(uint64_t, unsigned long long, 1);
+#undef KT_TV
+#undef KT_T
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  t->pristine = false;
+  say(launched, launched_len, name);
+  return JFGPU_OK;
+}
+
+// ---- P1 alone ---------------------------------------------------------------------------------------------------------
+// p1_ring_kernel<uint32_t, false, NB, CANON, RecordDirect> over bases[lo, hi) (a contract buffer: its base 16-byte
+// aligned) on the table's descriptor with 2^b1 buckets (PartGeom set here: rest_shift = lsize_l - b1), `grid` workgroups.
+// variant: 0 the run-time byte-table hash (NB = 0, CANON = 2); 1 six key bytes compiled in (NB = 6, CANON the table's);
+// 2 the xor-shift matrix in registers (NB = kHashXSLow, CANON = 2; the table's matrix must be that one).
+// Neither p1_stragglers_kernel nor granule_finish_kernel runs: the lists come back as the kernel left them.
+// out: (2^b1 + 1) * cap items in and out (one region behind the last bucket's: a guard); gcur: 2 * 2^b1 words out; tot: 2^b1 out; strag: grid * kStragPerBlock entries out,
+// strag_n: grid; rec / n_rec as in jfkt_p2; ctr[2]: what the kernel added to the table's k-mer counter and to its direct counter.
+int jfkt_p1(jfgpu_table* t, int variant, uint32_t b1, const uint8_t* bases, uint64_t n_bases, int64_t lo, int64_t hi, uint32_t cap, uint32_t grid,
+            uint32_t* out, uint32_t* gcur, uint64_t* tot, uint64_t* strag, uint32_t* strag_n, uint64_t* rec, uint64_t rec_cap, uint64_t* n_rec,
+            uint64_t* ctr, char* launched, size_t launched_len) {
+  int rc = use(t); if(rc) return rc;
+  if(t->wide || t->nword) return fail(JFGPU_E_INVALID, "jfkt_p1: one-word keys");
+  if(b1 < 1 || b1 > 10 || b1 > t->g.lsize_l || !grid || grid > 64) return fail(JFGPU_E_INVALID, "jfkt_p1: 1 <= b1 <= 10, 1 <= grid <= 64");
+  if(lo < 0 || hi < lo || (uint64_t)hi > n_bases) return fail(JFGPU_E_INVALID, "jfkt_p1: [lo, hi) outside the buffer");
+  if(cap % kGran || !cap) return fail(JFGPU_E_INVALID, "jfkt_p1: regions are whole reservations");
+  PartGeom P;
+  P.b1 = b1; P.b2 = t->g.lsize_l - t->g.tile_bits > b1 ? t->g.lsize_l - t->g.tile_bits - b1 : 0;
+  P.rest_shift = t->g.lsize_l - b1; P.item_bits = P.rest_shift + t->g.rem_bits;
+  if(P.item_bits > 32) return fail(JFGPU_E_INVALID, "jfkt_p1: the geometry's items do not fit 32 bits");
+  if(variant == 1 && t->g.nbytes != 6) return fail(JFGPU_E_INVALID, "jfkt_p1: NB = 6 needs keys of six bytes");
+  if(variant == 2 && !t->g.hash_xs) return fail(JFGPU_E_INVALID, "jfkt_p1: the table's matrix is not the xor-shift one");
+  if(variant == 2 && t->g.lsize_g > 32) return fail(JFGPU_E_INVALID, "jfkt_p1: kHashXSLow is for positions of at most 32 bits");
+  KT_TRY(kt_ring_attrs());
+  const uint32_t nb = 1u << b1;
+  DevBufs D;
+  uint8_t* d_bases; uint32_t *d_out, *d_strag_n; unsigned int* d_gcur; unsigned long long *d_tot, *d_nrec; uint64_t *d_strag, *d_rec;
+  KT_TRY(D.put(&d_bases, bases, (size_t)n_bases, 32));
+  KT_TRY(D.put(&d_out, out, ((size_t)nb + 1) * cap));
+  KT_TRY(D.get(&d_gcur, 2 * (size_t)nb, 0));
+  KT_TRY(D.get(&d_tot, nb, 0));
+  KT_TRY(D.get(&d_strag, (size_t)grid * kStragPerBlock, 0));
+  KT_TRY(D.get(&d_strag_n, grid, 0));
+  KT_TRY(D.get(&d_rec, 3 * (size_t)rec_cap, 0));
+  KT_TRY(D.get(&d_nrec, 1, 0));
+  uint64_t c0[CTR_COUNT], c1[CTR_COUNT];
+  KT_TRY(read_counters(t, c0));
+  const RecordDirect od{d_rec, d_nrec, rec_cap};
+  const size_t lds = (size_t)nb * 128 + 128;                                      // (part_ingest)
+  std::string name;
+#define KT_P1(N, CN) do { hipLaunchKernelGGL((p1_ring_kernel<uint32_t, false, N, CN, RecordDirect>), dim3(grid), dim3(kPBlock), lds, t->stream, t->dt, od, P, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, d_strag, d_strag_n); \
+                          name = "p1_ring_kernel<uint32_t,false," #N "," #CN ",RecordDirect>"; } while(0)
+  if(variant == 0) KT_P1(0, 2);
+  else if(variant == 1) { if(t->g.canonical) KT_P1(6, 1); else KT_P1(6, 0); }
+  else KT_P1(kHashXSLow, 2);
+#undef KT_P1
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  KT_TRY(read_counters(t, c1));
+  HIP_TRY(hipMemcpy(out, d_out, ((size_t)nb + 1) * cap * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(gcur, d_gcur, 2 * (size_t)nb * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tot, d_tot, (size_t)nb * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(strag, d_strag, (size_t)grid * kStragPerBlock * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(strag_n, d_strag_n, (size_t)grid * 4, hipMemcpyDeviceToHost));
+  if(rec_cap) HIP_TRY(hipMemcpy(rec, d_rec, 3 * (size_t)rec_cap * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n_rec, d_nrec, 8, hipMemcpyDeviceToHost));
+  if(ctr) { ctr[0] = c1[CTR_MERS] - c0[CTR_MERS]; ctr[1] = c1[CTR_DIRECT] - c0[CTR_DIRECT]; }
+  say(launched, launched_len, name);
+  return JFGPU_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,123 @@
+"""Python side of tests/kernels/stage_harness.hip: the library that is the engine plus entry points launching ONE stage
+of the partitioned insert path (P1, P2, T) with the caller's arguments.  Test infrastructure, used by
+tests/test_gpu_stage_*.py only.
+
+The library is a superset of the engine, so it gets a ctypes binding of its own: a private copy of jellyfish_amd.capi bound
+to it (`Harness.capi`).  A table made there is what the stage launches take and what lookup / dump_records / stats /
+digest read back.  A handle of one library never goes to the other.
+
+JFKT_LIB names a library built elsewhere (tests/test_stage_kernels_emu.py: the host emulation); without it the device
+build is made, or found up to date, by `make kernel-harness`."""
+import ctypes as C
+import importlib.util
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_P = C.c_void_p
+HOLE = 0xFFFFFFFF
+
+CONSTS = ["kPBlock", "kP2StragPerBlock", "kStragPerBlock", "kGran", "kRingSlots", "kRingUnit", "kTileBlock", "kTileRound4",
+          "kTileRound8", "kMaxTileBits", "kBucketBits", "kPTilePos", "kG2Blocks", "kTileQueueBytes"]
+GEOM = ["lsize_l", "tile_bits", "rem_bits", "tag_bits", "cnt_bits", "slot32", "hash_xs", "nbytes", "returning", "part_ok", "b1", "b2",
+        "rest_shift", "item32", "lsize_g", "canonical"]
+
+_SIGNATURES = {
+    "jfkt_const": (C.c_uint64, [C.c_int]),
+    "jfkt_geom": (C.c_int, [_P, _P, C.c_uint32]),
+    "jfkt_p2": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
+                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint64, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "jfkt_tile": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, C.c_uint64,
+                            C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "jfkt_p1": (C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_uint64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P,
+                          C.c_uint64, _P, _P, C.c_char_p, C.c_size_t]),
+}
+
+
+class Harness:
+    def __init__(self, path):
+        from jellyfish_amd import capi as product
+        spec = importlib.util.spec_from_file_location("jellyfish_amd_capi_stage_harness", product.__file__)
+        self.capi = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(self.capi)
+        self.capi.LIB_PATH = path
+        self.lib = self.capi.load()
+        for name, (res, args) in _SIGNATURES.items():
+            fn = getattr(self.lib, name)
+            fn.restype, fn.argtypes = res, args
+        self.const = {n: int(self.lib.jfkt_const(i)) for i, n in enumerate(CONSTS)}
+
+    def geom(self, table):
+        out = np.zeros(len(GEOM), dtype=np.uint64)
+        self.capi._check(self.lib.jfkt_geom(table._h, out.ctypes.data, len(GEOM)))
+        return {n: int(v) for n, v in zip(GEOM, out)}
+
+    def p2(self, table, kernel, nv, pd, b2e, tag_bits, segs, cap, bucket0, nbk, out, rec_cap=1 << 16):
+        """segs: [(items uint32[], off uint64[], sh)]; out: uint32[n_dest * cap], pre-filled by the caller (not modified: the
+        result is a copy).  kernel: 'roles' or 'shared'."""
+        keep = [(np.ascontiguousarray(i, dtype=np.uint32), np.ascontiguousarray(o, dtype=np.uint64), int(s)) for i, o, s in segs]
+        n = len(keep)
+        items = (_P * n)(*[i.ctypes.data for i, _, _ in keep])
+        offs = (_P * n)(*[o.ctypes.data for _, o, _ in keep])
+        n_items = np.array([len(i) for i, _, _ in keep], dtype=np.uint64)
+        n_off = np.array([len(o) for _, o, _ in keep], dtype=np.uint64)
+        sh = np.array([s for _, _, s in keep], dtype=np.uint32)
+        assert len(out) % cap == 0
+        n_dest = len(out) // cap
+        res = np.array(out, dtype=np.uint32, copy=True)
+        shared = kernel == "shared"
+        gcur = np.zeros(2 * n_dest, dtype=np.uint32)
+        rec = np.zeros((rec_cap, 3), dtype=np.uint64)
+        n_rec, ctr = C.c_uint64(0), C.c_uint64(0)
+        strag_n = np.zeros((self.const["kG2Blocks"] if shared else 1) * nbk, dtype=np.uint32)
+        name = C.create_string_buffer(256)
+        self.capi._check(self.lib.jfkt_p2(table._h, int(shared), nv, pd, b2e, tag_bits, n, items, n_items.ctypes.data, offs, n_off.ctypes.data,
+                                          sh.ctypes.data, cap, bucket0, nbk, n_dest, res.ctypes.data, gcur.ctypes.data, rec.ctypes.data, rec_cap,
+                                          C.byref(n_rec), C.byref(ctr), strag_n.ctypes.data, name, len(name)))
+        return dict(out=res.reshape(n_dest, cap), gcur=gcur[:n_dest], gshort=gcur[n_dest:], rec=rec[:min(n_rec.value, rec_cap)], n_rec=n_rec.value,
+                    ctr_direct=ctr.value, strag_n=strag_n, launched=name.value.decode())
+
+    def tile(self, table, items, off, sh, n_units, tpb, heavy=False, sample=False, holes=True, tile0=0, grid=0):
+        items = np.ascontiguousarray(items)
+        assert items.dtype in (np.uint32, np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        name = C.create_string_buffer(256)
+        self.capi._check(self.lib.jfkt_tile(table._h, tpb, int(heavy), int(sample), int(holes), items.dtype.itemsize, items.ctypes.data, len(items),
+                                            off.ctypes.data, len(off), sh, tile0, n_units, grid, name, len(name)))
+        return name.value.decode()
+
+    def p1(self, table, variant, b1, bases, lo, hi, cap, grid, sentinel, rec_cap=1 << 16):
+        """bases: bytes of the contract buffer (its start is the 16-byte aligned base); the k-mers of [lo, hi) are taken."""
+        buf = np.frombuffer(bytes(bases), dtype=np.uint8)
+        nb = 1 << b1
+        out = np.full((nb + 1) * cap, sentinel, dtype=np.uint32)
+        gcur = np.zeros(2 * nb, dtype=np.uint32)
+        tot = np.zeros(nb, dtype=np.uint64)
+        strag = np.zeros((grid, self.const["kStragPerBlock"]), dtype=np.uint64)
+        strag_n = np.zeros(grid, dtype=np.uint32)
+        rec = np.zeros((rec_cap, 3), dtype=np.uint64)
+        n_rec, ctr = C.c_uint64(0), np.zeros(2, dtype=np.uint64)
+        name = C.create_string_buffer(256)
+        self.capi._check(self.lib.jfkt_p1(table._h, variant, b1, buf.ctypes.data, len(buf), lo, hi, cap, grid, out.ctypes.data, gcur.ctypes.data,
+                                          tot.ctypes.data, strag.ctypes.data, strag_n.ctypes.data, rec.ctypes.data, rec_cap, C.byref(n_rec),
+                                          ctr.ctypes.data, name, len(name)))
+        return dict(out=out.reshape(nb + 1, cap), gcur=gcur[:nb], gshort=gcur[nb:], tot=tot, strag=strag, strag_n=strag_n,
+                    rec=rec[:min(n_rec.value, rec_cap)], n_rec=n_rec.value, mers=int(ctr[0]), ctr_direct=int(ctr[1]), launched=name.value.decode())
+
+
+_harness = None
+
+
+def load():
+    """The harness library, built (or found up to date) by the Makefile unless JFKT_LIB names one.  One per process."""
+    global _harness
+    if _harness is None:
+        path = os.environ.get("JFKT_LIB")
+        if not path:
+            subprocess.check_call(["make", "-s", "kernel-harness"], cwd=ROOT)
+            path = os.path.join(ROOT, "tests", "kernels", "_build", "libjfgpu_kt.so")
+        assert os.path.exists(path), path + " is missing"
+        _harness = Harness(path)
+    return _harness

@@ -160,10 +160,15 @@ int  jfgpu_lookup(jfgpu_table* t, const uint64_t* keys, size_t n, uint64_t* vals
 
 /* ---- multi-GPU: hash-prefix partition --------------------- */
 /* Encode + canonicalise + hash one contract buffer and bucket the k-mers by owning
- * shard instead of inserting them.  d_keys_out has room for `capacity` keys; shard
- * s's keys are written contiguously at d_keys_out + offsets[s] ... in arbitrary
- * order, with counts[s] of them; offsets are the exclusive prefix sum of counts
- * (so the buffer is densely packed and ready for an all-to-all-v).
+ * shard instead of inserting them, for every mer length.  A key is key_words =
+ * ceil(2k / 64) little-endian 64-bit words, the layout jfgpu_add_keys takes;
+ * d_keys_out has room for `capacity` keys (capacity * key_words words).  Shard s's
+ * keys are written contiguously from key offsets[s] on, in arbitrary order, with
+ * counts[s] of them; offsets are the exclusive prefix sum of counts (so the buffer is
+ * densely packed and ready for an all-to-all-v); capacity, counts and offsets are in
+ * k-mers.  A Bloom counter attached to the table (count --bc) is asked first: what it
+ * does not admit is neither counted nor written.  A one-pass filter (count --bf-size)
+ * changes as it is asked and the two passes ask twice: JFGPU_E_UNSUPPORTED.
  * counts_out: host array [1 << shard_bits].  Synchronous. */
 int  jfgpu_partition_ascii_dev(jfgpu_table* t, const char* d_bases, size_t n,
                                uint64_t* d_keys_out, size_t capacity, uint64_t* counts_out);

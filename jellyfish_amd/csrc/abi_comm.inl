@@ -447,8 +447,8 @@ void comm_free_retired(jfgpu_comm* c, int turn, bool closing = false) {
   c->send_retired[turn].clear();
 }
 
-// Route one contract buffer of rank R into send[cur], grouped by owner; fills scount / soff.  The host waits for the
-// per-owner counts (one small copy) -- they place the groups and size the messages.
+// Route one contract buffer of rank R into send[cur], grouped by owner (route_buffer, jfgpu.hip); fills scount / soff from
+// the per-owner counts -- they size the messages.
 int comm_route(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_bases, size_t n) {
   jfgpu_table* t = R.t;
   const int cur = R.turn, W = c->world;
@@ -461,36 +461,11 @@ int comm_route(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_bases, size_t n
   if(n < t->g.k) return JFGPU_OK;
   int rc = comm_reserve_send(c, R, cur, n * kw, t->stream); if(rc) return rc;
   if(!R.used[cur ^ 1]) { rc = comm_reserve_send(c, R, cur ^ 1, n * kw, t->stream); if(rc) return rc; }   // (both buffers of the pair at once)
-  const uint8_t* base; int64_t lo, hi;
-  align_buffer(d_bases, n, base, lo, hi);
-  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
-  const int grid = grid_for(t, (uint64_t)n_tiles);
-  HIP_TRY(hipMemsetAsync(R.d_cnt, 0, sizeof(unsigned long long) * W, t->stream));
-  {
-    ProfScope ps(t, 2, n);
-    if(t->nword) hipLaunchKernelGGL(partition_count_nword_kernel, dim3(grid), dim3(kBlock), nword_route_lds(t->g.nbytes), t->stream, t->nt, base, lo, hi, R.d_cnt);
-    else if(t->wide && t->wt.bloom.data) hipLaunchKernelGGL(partition_count_wide_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, R.d_cnt);
-    else if(t->wide) hipLaunchKernelGGL(partition_count_wide_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, R.d_cnt);
-    else if(t->dt.bloom.data) hipLaunchKernelGGL(partition_count_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, R.d_cnt);
-    else hipLaunchKernelGGL(partition_count_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, R.d_cnt);
-  }
-  std::vector<unsigned long long> h(W);
-  HIP_TRY(hipMemcpyAsync(h.data(), R.d_cnt, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
+  std::vector<uint64_t> h(W);
+  rc = route_buffer(t, d_bases, n, R.d_cnt, R.send[cur], n, h.data()); if(rc) return rc;
   uint64_t total = 0;
-  for(int p = 0; p < W; ++p) { R.scount[cur][p] = h[p] * kw; R.soff[cur][p] = total * kw; const uint64_t first = total; total += h[p]; h[p] = first; }      // (cursors in k-mers, messages in words)
+  for(int p = 0; p < W; ++p) { R.scount[cur][p] = h[p] * kw; R.soff[cur][p] = total * kw; total += h[p]; }      // (counts in k-mers, messages in words)
   R.soff[cur][W] = total * kw;
-  HIP_TRY(hipMemcpyAsync(R.d_cnt, h.data(), sizeof(unsigned long long) * W, hipMemcpyHostToDevice, t->stream));   // cursors = offsets
-  {
-    ProfScope ps(t, 2, 0);
-    if(t->nword) hipLaunchKernelGGL(partition_scatter_nword_kernel, dim3(grid), dim3(kBlock), nword_route_lds(t->g.nbytes), t->stream, t->nt, base, lo, hi, R.d_cnt, R.send[cur], t->key_words);
-    else if(t->wide && t->wt.bloom.data) hipLaunchKernelGGL(partition_scatter_wide_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, R.d_cnt, R.send[cur]);
-    else if(t->wide) hipLaunchKernelGGL(partition_scatter_wide_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, R.d_cnt, R.send[cur]);
-    else if(t->dt.bloom.data) hipLaunchKernelGGL(partition_scatter_kernel<true>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, R.d_cnt, R.send[cur]);
-    else hipLaunchKernelGGL(partition_scatter_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, R.d_cnt, R.send[cur]);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(t->stream));       // the host vector h is read by the copy above
   R.sent += total;
   return JFGPU_OK;
 }

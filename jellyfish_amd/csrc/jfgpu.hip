@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/jfgpu.h"
@@ -222,6 +223,7 @@ int part_ingest(jfgpu_table* t, const uint8_t* base, int64_t lo, int64_t hi, boo
 int part_flush(jfgpu_table* t);
 int table_grow(jfgpu_table* t);
 int measure_occupancy(jfgpu_table* t);
+int comm_filter_ok(const jfgpu_table* t);   // abi_comm.inl
 
 // Splits a device buffer pointer into a 16-byte aligned base and [lo, hi).
 void align_buffer(const char* d, size_t n, const uint8_t*& base, int64_t& lo, int64_t& hi) {
@@ -447,6 +449,45 @@ void launch_dump(jfgpu_table* t, const Table& T, uint64_t t0, uint64_t ntile, ui
   const size_t lds = ((size_t)(8 * KeyOps<Table>::kSlotWords) << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits);     // 16 or 32 bytes of slot, 2 of index
   hipLaunchKernelGGL(dump_tiles_words_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), lds, t->stream, T, t->dump_lower, t->dump_upper,
                      t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump, key_bytes, t->out_counter_len);
+}
+
+// The sender's two passes over one contract buffer (route_count_kernel, route_scatter_kernel): the buffer's k-mers into `out`,
+// grouped by owner, key_words words each.  d_cnt: one device counter per shard; counts[p]: the k-mers of owner p, whose
+// region starts at counts[0] + .. + counts[p - 1] k-mers.  `capacity` is what `out` holds, in k-mers.  The host waits for the
+// counts (one small copy) -- they place the regions -- and for the scatter.
+int route_buffer(jfgpu_table* t, const char* d_bases, size_t n, unsigned long long* d_cnt, uint64_t* out, size_t capacity, uint64_t* counts) {
+  const uint32_t W = 1u << t->g.shard_bits;
+  const uint8_t* base; int64_t lo, hi;
+  align_buffer(d_bases, n, base, lo, hi);
+  const int grid = grid_for(t, (uint64_t)((hi + kTilePos - 1) / kTilePos));
+  auto launch = [&](bool scatter) {
+    ProfScope ps(t, 2, scatter ? 0 : n);
+    with_view(t, [&](const auto& T) {
+      typedef std::decay_t<decltype(T)> Table;
+      typedef KeyOps<Table> K;
+      const size_t lds = K::kFwdLdsWords ? 0 : route_lds_bytes(t->g.nbytes, K::kHaloWords);
+      auto go = [&](auto bloom) {
+        if(scatter) hipLaunchKernelGGL((route_scatter_kernel<Table, decltype(bloom)::value>), dim3(grid), dim3(kBlock), lds, t->stream, T, base, lo, hi, d_cnt, out, t->key_words);
+        else hipLaunchKernelGGL((route_count_kernel<Table, decltype(bloom)::value>), dim3(grid), dim3(kBlock), lds, t->stream, T, base, lo, hi, d_cnt);
+      };
+      if constexpr(std::is_same_v<Table, NTable>) go(std::false_type());      // (takes no filter)
+      else if(T.bloom.data) go(std::true_type());
+      else go(std::false_type());
+    });
+  };
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * W, t->stream));
+  launch(false);
+  std::vector<unsigned long long> h(W);
+  HIP_TRY(hipMemcpyAsync(h.data(), d_cnt, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  uint64_t total = 0;
+  for(uint32_t p = 0; p < W; ++p) { counts[p] = h[p]; h[p] = total; total += counts[p]; }
+  if(total > capacity) return fail(JFGPU_E_INVALID, "partition buffer too small: need " + std::to_string(total) + " keys");
+  HIP_TRY(hipMemcpyAsync(d_cnt, h.data(), sizeof(unsigned long long) * W, hipMemcpyHostToDevice, t->stream));   // cursors = offsets
+  launch(true);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(t->stream));       // (the host vector h is read by the copy above)
+  return JFGPU_OK;
 }
 
 // One scan into n 64-bit counters of its own (4, or a histogram's buckets), copied to `out` when it is complete.
@@ -738,10 +779,10 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
     t->part_ok = false; t->mode = MODE_DIRECT;
     const int nl = (int)(((size_t)32 << kNTileBits) + ((size_t)2 << kNTileBits));
     HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_words_kernel<NTable>, hipFuncAttributeMaxDynamicSharedMemorySize, nl));
-    {                                                                          // the routing passes of a shard, world 1 included (abi_comm.inl)
-      const int rl = (int)nword_route_lds(t->g.nbytes);
-      HIP_TRY(hipFuncSetAttribute((const void*)partition_count_nword_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-      HIP_TRY(hipFuncSetAttribute((const void*)partition_scatter_nword_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
+    {                                                                          // the routing passes of a shard, world 1 included (route_buffer)
+      const int rl = (int)route_lds_bytes(t->g.nbytes, KeyOps<NTable>::kHaloWords);
+      HIP_TRY(hipFuncSetAttribute((const void*)route_count_kernel<NTable, false>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
+      HIP_TRY(hipFuncSetAttribute((const void*)route_scatter_kernel<NTable, false>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
     }
   } else if(wide) {
     WideTable& w = t->wt;
@@ -1067,40 +1108,16 @@ int jfgpu_partition_ascii_dev(jfgpu_table* t, const char* d_bases, size_t n, uin
                               uint64_t* counts_out) {
   int rc = use(t); if(rc) return rc;
   if(!counts_out) return fail(JFGPU_E_INVALID, "null counts_out");
-  if(t->wide || t->nword) return fail(JFGPU_E_UNSUPPORTED, "hash-prefix partition with mer length > 32 is not built yet");
+  rc = comm_filter_ok(t); if(rc) return rc;     // a one-pass filter changes as it is asked, and the two passes ask twice
   const uint32_t n_shards = 1u << t->g.shard_bits;
   for(uint32_t i = 0; i < n_shards; ++i) counts_out[i] = 0;
   if(n < t->g.k) return JFGPU_OK;
   if(!d_bases || !d_keys_out) return fail(JFGPU_E_INVALID, "null buffer");
   unsigned long long* d_cnt = nullptr;
   HIP_TRY(hipMalloc((void**)&d_cnt, sizeof(unsigned long long) * n_shards));
-  HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * n_shards, t->stream));
-  const uint8_t* base; int64_t lo, hi;
-  align_buffer(d_bases, n, base, lo, hi);
-  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
-  const int grid = grid_for(t, (uint64_t)n_tiles);
-  {
-    ProfScope ps(t, 2, n);
-    hipLaunchKernelGGL(partition_count_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, d_cnt);
-  }
-  std::vector<unsigned long long> h(n_shards);
-  hipError_t e = hipMemcpyAsync(h.data(), d_cnt, sizeof(unsigned long long) * n_shards, hipMemcpyDeviceToHost, t->stream);
-  if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  if(e != hipSuccess) { hipFree(d_cnt); return fail(JFGPU_E_HIP, hipGetErrorString(e)); }
-  uint64_t total = 0;
-  std::vector<unsigned long long> offs(n_shards);
-  for(uint32_t i = 0; i < n_shards; ++i) { offs[i] = total; total += h[i]; counts_out[i] = h[i]; }
-  if(total > capacity) { hipFree(d_cnt); return fail(JFGPU_E_INVALID, "partition buffer too small: need " + std::to_string(total) + " keys"); }
-  e = hipMemcpyAsync(d_cnt, offs.data(), sizeof(unsigned long long) * n_shards, hipMemcpyHostToDevice, t->stream);
-  if(e == hipSuccess) {
-    ProfScope ps(t, 2, 0);
-    hipLaunchKernelGGL(partition_scatter_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, d_cnt, d_keys_out);
-    e = hipGetLastError();
-  }
-  if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  rc = route_buffer(t, d_bases, n, d_cnt, d_keys_out, capacity, counts_out);
   hipFree(d_cnt);
-  if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
-  return JFGPU_OK;
+  return rc;
 }
 
 int jfgpu_stats_compute(jfgpu_table* t, uint64_t lower, uint64_t upper, jfgpu_stats* out) {

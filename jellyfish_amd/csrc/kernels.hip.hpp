@@ -8,7 +8,7 @@
 //                        (large_hash_array.hpp:291-295,509-597,741-752)
 //   add_keys_kernel      hash_counter::add on encoded mers (hash_counter.hpp:91-126)
 //   lookup_kernel        array_base::get_val_for_key (large_hash_array.hpp:354-372)
-//   partition_*_kernel   new: hash-prefix routing of k-mers to their owning GPU
+//   route_*_kernel       new: hash-prefix routing of k-mers to their owning GPU
 //   stats/histo/dump     region iterators + sorted_dumper + binary_writer
 //                        (large_hash_iterator.hpp, sorted_dumper.hpp:57-101,
 //                        binary_dumper.hpp:36-40)
@@ -306,6 +306,22 @@ __device__ inline bool table_add_val(const DevTable& T, const uint64_t* fwd_lds,
 //   store_key / load_key             a key as kw little-endian 64-bit words; load_key masks with the table's key mask when asked
 //   digest(T, key, c)                (the multi-word views) an entry's digest hash
 //   kSlotWords, slot_of(w), key_byte (the multi-word views, for the dump) words per slot, a slot from a copy of its words, byte b of a key
+// and, for the kernels that read sequence from a contract buffer (route_count_kernel and route_scatter_kernel below):
+//   Lane, kHaloWords                 a lane's 16 bases with the k-mer state before them, and the code words of halo a tile is
+//                                    staged with (k - 1 bases: 2, 4 or 8)
+//   stage_tile(T, base, tile_start, lo, hi, s_codes, s_inv)   the tile's codes and invalid masks through LDS (kBlock +
+//                                    kHaloWords words each) into a Lane; ends in a barrier
+//   for_each_kmer(T, L, f)           f(j, key, valid) for the (canonical) k-mer ending at position j of the lane.  The one- and
+//                                    two-word views call f for the valid windows only; NTable calls it on every lane at every
+//                                    position (wave-uniform), because its route_rank ballots
+//   route_rank(valid, owner, s_hist) the rank of this lane's k-mer among the workgroup's k-mers of its owner, counted in
+//                                    s_hist.  One LDS atomic per k-mer for one and two words, one per wave and owner (by
+//                                    ballot) for NTable: each width keeps the ranking it was written and measured with, and
+//                                    moving the narrow widths to the ballot would be a change of speed, not of structure
+//   admit_mask(T, L), admits(T, mask, j, key)   count --bc, only in a BLOOM kernel: what the view's Bloom counter admits.  One
+//                                    word asks for the lane's 16 windows at once and tests a bit, two words ask key by key
+//                                    (the mask is all ones); NTable takes no filter and has neither
+//   kKeyWords                        64-bit words a routed key is stored as by store_key (0: the caller's kw, 3 or 4)
 template <class Table> struct KeyOps;
 
 __device__ inline void load_tables_lds(uint64_t* dst, const uint64_t* src, uint32_t nbytes) {
@@ -319,11 +335,15 @@ __device__ inline const uint64_t* stage_tables_lds(const uint64_t* src, uint32_t
   return s_tbl;
 }
 
+__device__ inline LaneWords stage_tile(const uint8_t* __restrict__ base, int64_t tile_start, int64_t lo, int64_t hi, uint32_t* s_codes, uint32_t* s_inv);   // below
+
 template <> struct KeyOps<DevTable> {
   typedef uint64_t Key;
   struct Slot { uint64_t w; };
   static constexpr uint32_t kFwdLdsWords = 8 * 256;
   static constexpr bool kUpdateReturns = false;
+  typedef LaneWords Lane;
+  static constexpr uint32_t kHaloWords = 2, kKeyWords = 1;
   __device__ static const TableGeom& geom(const DevTable& T) { return T.g; }
   __device__ static bool load(const DevTable& T, uint64_t i, Slot& s) { s.w = slot_ld(T, i); return s.w != 0; }
   __device__ static uint64_t count(const DevTable& T, const Slot& s, uint64_t i, int have_ovf) { return full_count(T, s.w, i, have_ovf); }
@@ -340,6 +360,14 @@ template <> struct KeyOps<DevTable> {
   __device__ static uint32_t owner(const DevTable& T, const uint64_t* H, Key key) { return (uint32_t)(hash_tables(H, key, T.g.nbytes) >> T.g.lsize_l); }
   __device__ static void store_key(uint64_t* dst, Key key, uint32_t) { dst[0] = key; }
   __device__ static Key load_key(const DevTable& T, const uint64_t* keys, uint64_t i, uint32_t, bool masked) { return masked ? keys[i] & T.g.key_mask : keys[i]; }
+  __device__ static Lane stage_tile(const DevTable&, const uint8_t* __restrict__ base, int64_t tile_start, int64_t lo, int64_t hi, uint32_t* s_codes, uint32_t* s_inv) {
+    return jfgpu::stage_tile(base, tile_start, lo, hi, s_codes, s_inv);
+  }
+  template <typename F>
+  __device__ static void for_each_kmer(const DevTable& T, const Lane& L, F&& f) { jfgpu::for_each_kmer(T.g, L, [&](int j, uint64_t key) { f(j, key, true); }); }
+  __device__ static uint32_t route_rank(bool valid, uint32_t owner, uint32_t* s_hist) { return valid ? atomicAdd(&s_hist[owner], 1u) : 0u; }
+  __device__ static uint32_t admit_mask(const DevTable& T, const Lane& L) { return bloom_admit_mask(T.bloom, T.g, L); }
+  __device__ static bool admits(const DevTable&, uint32_t mask, int j, Key) { return (mask >> j) & 1u; }
 };
 
 __device__ inline LaneWords stage_tile(const uint8_t* __restrict__ base, int64_t tile_start, int64_t lo, int64_t hi,
@@ -460,76 +488,6 @@ __global__ __launch_bounds__(kBlock) void add_keys_one_kernel(DevTable T, const 
     table_add<RETURNING>(T, s_fwd, keys[i] & T.g.key_mask, 1);
 }
 
-// ---- multi-GPU routing: count per shard, then scatter ----------------------------
-// Pass A: how many k-mers of this buffer belong to each shard.
-// BLOOM: count --bc with --gpus -- the sender asks its copy of the Bloom counter, what it does not admit never travels.
-template <bool BLOOM = false>
-__global__ __launch_bounds__(kBlock) void partition_count_kernel(DevTable T, const uint8_t* __restrict__ base,
-                                                                 int64_t lo, int64_t hi,
-                                                                 unsigned long long* __restrict__ shard_counts) {
-  __shared__ uint64_t s_fwd[8 * 256];
-  __shared__ uint32_t s_codes[kBlock + 2];
-  __shared__ uint32_t s_inv[kBlock + 2];
-  __shared__ uint32_t s_hist[256];
-  load_tables_lds(s_fwd, T.fwd_tbl, T.g.nbytes);
-  const uint32_t n_shards = 1u << T.g.shard_bits;
-  for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x) s_hist[i] = 0;
-  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
-  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    __syncthreads();
-    const LaneWords L = stage_tile(base, tile * kTilePos, lo, hi, s_codes, s_inv);
-    const uint32_t adm = BLOOM ? bloom_admit_mask(T.bloom, T.g, L) : 0xFFFFu;
-    for_each_kmer(T.g, L, [&](int j, uint64_t key) {
-      if(BLOOM && !((adm >> j) & 1u)) return;
-      const uint64_t pos = hash_tables(s_fwd, key, T.g.nbytes);
-      atomicAdd(&s_hist[(uint32_t)(pos >> T.g.lsize_l)], 1u);
-    });
-  }
-  __syncthreads();
-  for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x)
-    if(s_hist[i]) atomicAdd(&shard_counts[i], (unsigned long long)s_hist[i]);
-}
-
-// Pass B: write each k-mer into its shard's region.  cursors[s] starts at the
-// region's offset; a block reserves its share with one atomic per (tile, shard).
-template <bool BLOOM = false>
-__global__ __launch_bounds__(kBlock) void partition_scatter_kernel(DevTable T, const uint8_t* __restrict__ base,
-                                                                   int64_t lo, int64_t hi,
-                                                                   unsigned long long* __restrict__ cursors,
-                                                                   uint64_t* __restrict__ out) {
-  __shared__ uint64_t s_fwd[8 * 256];
-  __shared__ uint32_t s_codes[kBlock + 2];
-  __shared__ uint32_t s_inv[kBlock + 2];
-  __shared__ uint32_t s_hist[256];
-  __shared__ unsigned long long s_base[256];
-  load_tables_lds(s_fwd, T.fwd_tbl, T.g.nbytes);
-  const uint32_t n_shards = 1u << T.g.shard_bits;
-  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
-  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    __syncthreads();
-    for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x) s_hist[i] = 0;
-    const LaneWords L = stage_tile(base, tile * kTilePos, lo, hi, s_codes, s_inv);  // contains a barrier
-    // indexed by the unrolled position j (compile-time after unrolling) so these stay in VGPRs
-    uint64_t keys[kPerThread]; uint32_t shard[kPerThread]; uint32_t rank[kPerThread]; uint32_t vmask = 0;
-    const uint32_t adm = BLOOM ? bloom_admit_mask(T.bloom, T.g, L) : 0xFFFFu;      // (the same answers as the count pass: the counter is read-only here)
-    for_each_kmer(T.g, L, [&](int j, uint64_t key) {
-      if(BLOOM && !((adm >> j) & 1u)) return;
-      const uint64_t pos = hash_tables(s_fwd, key, T.g.nbytes);
-      const uint32_t s = (uint32_t)(pos >> T.g.lsize_l);
-      keys[j] = key; shard[j] = s;
-      rank[j] = atomicAdd(&s_hist[s], 1u);
-      vmask |= 1u << j;
-    });
-    __syncthreads();
-    for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x)
-      s_base[i] = s_hist[i] ? atomicAdd(&cursors[i], (unsigned long long)s_hist[i]) : 0ull;
-    __syncthreads();
-#pragma unroll
-    for(int j = 0; j < kPerThread; ++j)
-      if((vmask >> j) & 1u) out[s_base[shard[j]] + rank[j]] = keys[j];
-  }
-}
-
 // ---- cooperative size doubling (hash_counter::double_size, hash_counter.hpp:200-238) -------------
 // Every entry of the old table is re-derived (slot -> key by the inverse tables) and inserted with its
 // full count into the new, twice as large table (one more matrix row).  Hash tables are read through
@@ -580,6 +538,114 @@ __global__ __launch_bounds__(kBlock) void lookup_kernel(Table T, const uint64_t*
     const uint64_t s = K::find(T, H, K::load_key(T, keys, i, kw, true));
     vals[i] = s == ~0ull ? 0 : K::count_at(T, s, have_ovf);
     if(found) found[i] = s != ~0ull;
+  }
+}
+
+// ---- multi-GPU routing: a contract buffer's k-mers grouped by owner, every key width (KeyOps) -------------------------
+// The sender's two passes (route_buffer in jfgpu.hip: the key path of abi_comm.inl, jfgpu_partition_ascii_dev).  The owner of a
+// k-mer is pos >> lsize_l under the shard's global matrix.  Pass A counts the k-mers per owner; the host turns the counts into
+// cursors (the regions' offsets); pass B writes every k-mer into its owner's region as kw little-endian words, the layout of
+// jfgpu_add_keys.  Counts and cursors are in k-mers.  A workgroup counts in LDS and sends one global atomic per owner: per
+// buffer in pass A, per tile in pass B, where it reserves the tile's share of each region.
+// BLOOM: count --bc with --gpus -- the sender asks its copy of the Bloom counter, what it does not admit never travels.  The
+// counter is read-only here, so both passes get the same answers.
+// LDS: the forward tables, s_base (pass B), s_hist, and the tile's codes and invalid masks.  Static where the view stages its
+// tables statically; NTable's 64 KiB of tables make it dynamic, route_lds_bytes() for both of its kernels.
+struct RouteLds { uint64_t* fwd; unsigned long long* base; uint32_t *hist, *codes, *inv; };
+constexpr uint32_t kRouteOwners = 256;                     // s_hist / s_base: shard_bits <= 8
+inline size_t route_lds_bytes(uint32_t nbytes, uint32_t halo_words) { return (size_t)nbytes * 256 * 8 + kRouteOwners * (8 + 4) + 2 * (kBlock + halo_words) * 4; }
+template <class Table, bool SCATTER>
+__device__ inline RouteLds route_lds(uint32_t nbytes) {
+  typedef KeyOps<Table> K;
+  constexpr uint32_t kStage = kBlock + K::kHaloWords;
+  static_assert(16 * K::kHaloWords >= 4 * sizeof(typename K::Key) - 1, "the halo holds the k - 1 bases before a tile, for the view's longest k");
+  RouteLds S;
+  if constexpr(K::kFwdLdsWords != 0) {
+    __shared__ uint64_t s_fwd[K::kFwdLdsWords];
+    __shared__ uint32_t s_codes[kStage];
+    __shared__ uint32_t s_inv[kStage];
+    __shared__ uint32_t s_hist[kRouteOwners];
+    S.fwd = s_fwd; S.codes = s_codes; S.inv = s_inv; S.hist = s_hist; S.base = nullptr;
+    if constexpr(SCATTER) { __shared__ unsigned long long s_base[kRouteOwners]; S.base = s_base; }
+  } else {
+    JF_DYN_LDS(s_raw);
+    S.fwd = reinterpret_cast<uint64_t*>(s_raw);
+    S.base = reinterpret_cast<unsigned long long*>(S.fwd + (size_t)nbytes * 256);
+    S.hist = reinterpret_cast<uint32_t*>(S.base + kRouteOwners);
+    S.codes = S.hist + kRouteOwners;
+    S.inv = S.codes + kStage;
+  }
+  return S;
+}
+
+// Pass A: how many k-mers of this buffer belong to each shard.
+// (A BLOOM kernel leaves f at a k-mer its counter does not admit: the views that take a filter call f for the valid windows
+// only and rank without a ballot, so no lane is missed by one.)
+template <class Table, bool BLOOM>
+__global__ __launch_bounds__(kBlock) void route_count_kernel(Table T, const uint8_t* __restrict__ base, int64_t lo, int64_t hi,
+                                                             unsigned long long* __restrict__ shard_counts) {
+  typedef KeyOps<Table> K;
+  const TableGeom& g = K::geom(T);
+  const RouteLds S = route_lds<Table, false>(g.nbytes);
+  load_tables_lds(S.fwd, T.fwd_tbl, g.nbytes);
+  const uint32_t n_shards = 1u << g.shard_bits;
+  for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x) S.hist[i] = 0;
+  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
+  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    __syncthreads();
+    const typename K::Lane L = K::stage_tile(T, base, tile * kTilePos, lo, hi, S.codes, S.inv);
+    uint32_t adm = 0;
+    if constexpr(BLOOM) adm = K::admit_mask(T, L);
+    K::for_each_kmer(T, L, [&](int j, const typename K::Key& key, bool valid) {
+      if constexpr(BLOOM) if(!K::admits(T, adm, j, key)) return;
+      K::route_rank(valid, valid ? K::owner(T, S.fwd, key) : 0u, S.hist);
+    });
+  }
+  __syncthreads();
+  for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x)
+    if(S.hist[i]) atomicAdd(&shard_counts[i], (unsigned long long)S.hist[i]);
+}
+
+// Pass B: write each k-mer into its shard's region.  cursors[s] starts at the region's offset; a block reserves its share
+// with one atomic per (tile, shard).  Two sweeps over the lane's windows, ranks and then stores.  Keys of one word are kept in
+// registers between the sweeps; wider ones are rolled again (the re-rolled form costs the one-word kernel a wave per SIMD,
+// the kept form the wider ones their registers: profiles/route_kernel_resources.txt).
+template <class Table, bool BLOOM>
+__global__ __launch_bounds__(kBlock) void route_scatter_kernel(Table T, const uint8_t* __restrict__ base, int64_t lo, int64_t hi,
+                                                               unsigned long long* __restrict__ cursors, uint64_t* __restrict__ out, uint32_t kw) {
+  typedef KeyOps<Table> K;
+  typedef typename K::Key Key;
+  constexpr bool kKeepKeys = sizeof(Key) == 8;
+  const TableGeom& g = K::geom(T);
+  const RouteLds S = route_lds<Table, true>(g.nbytes);
+  load_tables_lds(S.fwd, T.fwd_tbl, g.nbytes);
+  const uint32_t n_shards = 1u << g.shard_bits;
+  const uint32_t stride = K::kKeyWords ? K::kKeyWords : kw;
+  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
+  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    __syncthreads();
+    for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x) S.hist[i] = 0;
+    const typename K::Lane L = K::stage_tile(T, base, tile * kTilePos, lo, hi, S.codes, S.inv);     // contains a barrier
+    // indexed by the unrolled position j (compile-time after unrolling) so these stay in VGPRs
+    Key keys[kKeepKeys ? kPerThread : 1]; uint32_t sh[kPerThread], rank[kPerThread], routed = 0;
+    uint32_t adm = 0;
+    if constexpr(BLOOM) adm = K::admit_mask(T, L);
+    K::for_each_kmer(T, L, [&](int j, const Key& key, bool valid) {
+      if constexpr(BLOOM) if(!K::admits(T, adm, j, key)) return;
+      if constexpr(kKeepKeys) keys[j] = key;
+      sh[j] = valid ? K::owner(T, S.fwd, key) : 0u;
+      rank[j] = K::route_rank(valid, sh[j], S.hist);
+      routed |= (uint32_t)valid << j;
+    });
+    __syncthreads();
+    for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x)
+      S.base[i] = S.hist[i] ? atomicAdd(&cursors[i], (unsigned long long)S.hist[i]) : 0ull;
+    __syncthreads();
+    auto store = [&](int j, const Key& key, bool routes) { if(routes) K::store_key(out + (uint64_t)stride * (S.base[sh[j]] + rank[j]), key, kw); };
+    if constexpr(kKeepKeys) {
+#pragma unroll
+      for(int j = 0; j < kPerThread; ++j) store(j, keys[j], (routed >> j) & 1u);
+    } else K::for_each_kmer(T, L, [&](int j, const Key& key, bool valid) { store(j, key, BLOOM ? (routed >> j) & 1u : valid); });
   }
 }
 

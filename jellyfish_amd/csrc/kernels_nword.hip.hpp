@@ -331,70 +331,13 @@ __device__ inline K256 load_key4(const uint64_t* keys, uint64_t i, uint32_t kw, 
   return k256_and(r, mask);
 }
 
-// Slot access for the kernels written once for every key width (KeyOps, kernels.hip.hpp).  A slot is looked at where it lies (in
-// the table, or in the dump's copy of it); only a complete one -- every word set -- holds a key, whatever the kernel.
-template <> struct KeyOps<NTable> {
-  typedef K256 Key;
-  struct Slot { const uint64_t* sp; };
-  static constexpr int kSlotWords = kNWords;
-  static constexpr uint32_t kFwdLdsWords = 0;            // up to 32 x 256 words = 64 KiB: read through the caches
-  static constexpr bool kUpdateReturns = true;
-  __device__ static const TableGeom& geom(const NTable& T) { return T.N.g; }
-  __device__ static bool load(const NTable& T, uint64_t i, Slot& s) { s.sp = &T.slots[4 * i]; return nword_complete(s.sp); }
-  __device__ static bool occupied(const NTable& T, uint64_t i, Slot& s) { return load(T, i, s); }
-  __device__ static Slot slot_of(const uint64_t* w) { Slot s; s.sp = w; return s; }
-  __device__ static uint64_t count(const NTable& T, const Slot& s, uint64_t i, int have_ovf) { return nword_count_at(T, ovf_view(T), i, s.sp[3], have_ovf); }
-  __device__ static Key key(const NTable& T, const Slot& s, uint64_t tile_base) { return nword_slot_key(T, T.inv_tbl, s.sp, tile_base); }
-  __device__ static uint64_t count_at(const NTable& T, uint64_t i, int have_ovf) { return nword_count_at(T, ovf_view(T), i, T.slots[4 * i + 3], have_ovf); }
-  __device__ static const uint64_t* stage_fwd(const NTable& T) { return T.fwd_tbl; }
-  __device__ static bool add_val(const NTable& T, const uint64_t* H, const Key& key, uint64_t val) { return nword_add_val(T, H, key, val); }
-  template <bool RETURNING>
-  __device__ static bool update_add(const NTable& T, const uint64_t* H, const Key& key, uint64_t cnt) { static_assert(RETURNING, "kUpdateReturns"); return nword_update_add(T, H, key, cnt); }
-  __device__ static uint64_t find(const NTable& T, const uint64_t* H, const Key& key) { return nword_find(T, H, key); }
-  __device__ static uint32_t owner(const NTable& T, const uint64_t* H, const Key& key) { return slot_addr(T.N.g, hash_tables_n256(H, key, T.N.g.nbytes)).shard; }
-  __device__ static void store_key(uint64_t* dst, const Key& key, uint32_t kw) { for(uint32_t q = 0; q < kw; ++q) dst[q] = key.w[q]; }
-  __device__ static Key load_key(const NTable& T, const uint64_t* keys, uint64_t i, uint32_t kw, bool) { return load_key4(keys, i, kw, T.N.key_mask); }   // (masked either way)
-  __device__ static uint64_t digest(const NTable& T, const Key& key, uint64_t c) {
-    uint64_t h = kDigestSeed;
-    for(uint32_t q = 0; q < (T.N.g.k + 31) / 32; ++q) h = digest_mix(h ^ key.w[q]);
-    return digest_mix(h ^ c);
-  }
-  __device__ static uint8_t key_byte(const Key& key, uint32_t b) { return (uint8_t)(key.w[b >> 3] >> (8 * (b & 7))); }
-};
-
-// ---- multi-GPU: a contract buffer's k-mers grouped by owner (abi_comm.inl, key path) ---------------------------------
-// The two passes of partition_count / scatter_wide_kernel for 256-bit keys, reading the buffer like count_ascii_nword_kernel
-// (halo of 8 code words, `filled` validity, canonical form).  The owner is pos >> lsize_l under the shard's global matrix,
-// whose byte tables (up to 32 x 256 words, 64 KiB) sit in dynamic LDS: a k-mer's 32 gathers go to LDS, not to L2.
-// Per-owner counts never become a global atomic per k-mer: the lanes of a wave that route to the same owner are grouped
-// by ballot (one LDS atomic per wave and owner, and consecutive ranks in lane order), a workgroup's LDS counts go out with
-// one global atomic per owner.  Pass 1 writes kw (3 for k <= 96, 4 above) little-endian words per k-mer at its owner's
-// cursor, the layout of jfgpu_add_keys; a wave's k-mers for one owner land in neighbouring records.
-inline size_t nword_route_lds(uint32_t nbytes) { return (size_t)nbytes * 256 * 8 + 256 * 8 + 256 * 4 + 2 * (kBlock + 8) * 4; }
-
+// ---- sequence -> 256-bit k-mers for the routing kernels (route_count / route_scatter_kernel, kernels.hip.hpp) --------------
+// The buffer is read like count_ascii_nword_kernel reads it (halo of 8 code words, `filled` validity, canonical form).  The
+// matrix's byte tables (up to 32 x 256 words, 64 KiB) sit in dynamic LDS there: a k-mer's 32 gathers go to LDS, not to L2.
+// Per-owner counts never become an atomic per k-mer: the lanes of a wave that route to the same owner are grouped by ballot
+// (one LDS atomic per wave and owner, and consecutive ranks in lane order), so a wave's k-mers for one owner land in
+// neighbouring records.
 struct NLane { uint32_t c, v, filled; K256 fw, rc; };     // a lane's 16 bases and the k-mer state just before them
-
-__device__ inline NLane nword_stage_tile(const NGeom& N, const uint8_t* __restrict__ base, int64_t tile_start, int64_t lo, int64_t hi,
-                                         uint32_t* s_codes, uint32_t* s_inv) {
-  const int tid = threadIdx.x;
-  NLane L;
-  load_pack16(base, tile_start + 16 * tid, lo, hi, L.c, L.v);
-  s_codes[tid + 8] = L.c; s_inv[tid + 8] = L.v;
-  if(tid < 8) { uint32_t hc, hv; load_pack16(base, tile_start - 128 + 16 * tid, lo, hi, hc, hv); s_codes[tid] = hc; s_inv[tid] = hv; }
-  __syncthreads();
-  for(int i = 0; i < 4; ++i) L.fw.w[i] = ((uint64_t)s_codes[tid + 7 - 2 * i - 1] << 32) | s_codes[tid + 7 - 2 * i];
-  L.fw = k256_and(L.fw, N.key_mask);
-  L.rc = revcomp256(L.fw, N.g.k);
-  L.filled = 0;
-  for(int q = 7; q >= 0; --q) {                            // nearest halo word first
-    const uint32_t iv = s_inv[tid + q] & 0xFFFFu;
-    if(iv == 0) { L.filled += 16; continue; }
-    L.filled += (uint32_t)__ffs((int)iv) - 1;
-    break;
-  }
-  if(L.filled > N.g.k) L.filled = N.g.k;
-  return L;
-}
 
 // f(j, key, valid) for the lane's 16 positions, called by every lane at every position (wave-uniform: f may ballot)
 template <typename F>
@@ -431,64 +374,63 @@ __device__ inline uint32_t nword_wave_rank(bool valid, uint32_t s, uint32_t* s_h
   return rank;
 }
 
-__global__ __launch_bounds__(kBlock) void partition_count_nword_kernel(NTable T, const uint8_t* __restrict__ base, int64_t lo, int64_t hi,
-                                                                       unsigned long long* __restrict__ shard_counts) {
-  JF_DYN_LDS(s_raw);
-  const NGeom& N = T.N;
-  uint64_t* s_fwd = reinterpret_cast<uint64_t*>(s_raw);
-  uint32_t* s_hist = reinterpret_cast<uint32_t*>(s_fwd + (size_t)N.g.nbytes * 256 + 256);
-  uint32_t* s_codes = s_hist + 256;
-  uint32_t* s_inv = s_codes + kBlock + 8;
-  load_tables_lds(s_fwd, T.fwd_tbl, N.g.nbytes);
-  const uint32_t n_shards = 1u << N.g.shard_bits;
-  for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x) s_hist[i] = 0;
-  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
-  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    __syncthreads();
-    const NLane L = nword_stage_tile(N, base, tile * kTilePos, lo, hi, s_codes, s_inv);
-    for_each_kmer_nword(N, L, [&](int, const K256& key, bool valid) {
-      const uint32_t s = valid ? (uint32_t)(hash_tables_n256(s_fwd, key, N.g.nbytes) >> N.g.lsize_l) : 0u;
-      nword_wave_rank(valid, s, s_hist);
-    });
+// Slot access for the kernels written once for every key width (KeyOps, kernels.hip.hpp).  A slot is looked at where it lies (in
+// the table, or in the dump's copy of it); only a complete one -- every word set -- holds a key, whatever the kernel.
+template <> struct KeyOps<NTable> {
+  typedef K256 Key;
+  struct Slot { const uint64_t* sp; };
+  static constexpr int kSlotWords = kNWords;
+  static constexpr uint32_t kFwdLdsWords = 0;            // up to 32 x 256 words = 64 KiB: read through the caches
+  static constexpr bool kUpdateReturns = true;
+  typedef NLane Lane;
+  static constexpr uint32_t kHaloWords = 8, kKeyWords = 0;   // (3 or 4 words a key: the caller's kw)
+  __device__ static const TableGeom& geom(const NTable& T) { return T.N.g; }
+  __device__ static bool load(const NTable& T, uint64_t i, Slot& s) { s.sp = &T.slots[4 * i]; return nword_complete(s.sp); }
+  __device__ static bool occupied(const NTable& T, uint64_t i, Slot& s) { return load(T, i, s); }
+  __device__ static Slot slot_of(const uint64_t* w) { Slot s; s.sp = w; return s; }
+  __device__ static uint64_t count(const NTable& T, const Slot& s, uint64_t i, int have_ovf) { return nword_count_at(T, ovf_view(T), i, s.sp[3], have_ovf); }
+  __device__ static Key key(const NTable& T, const Slot& s, uint64_t tile_base) { return nword_slot_key(T, T.inv_tbl, s.sp, tile_base); }
+  __device__ static uint64_t count_at(const NTable& T, uint64_t i, int have_ovf) { return nword_count_at(T, ovf_view(T), i, T.slots[4 * i + 3], have_ovf); }
+  __device__ static const uint64_t* stage_fwd(const NTable& T) { return T.fwd_tbl; }
+  __device__ static bool add_val(const NTable& T, const uint64_t* H, const Key& key, uint64_t val) { return nword_add_val(T, H, key, val); }
+  template <bool RETURNING>
+  __device__ static bool update_add(const NTable& T, const uint64_t* H, const Key& key, uint64_t cnt) { static_assert(RETURNING, "kUpdateReturns"); return nword_update_add(T, H, key, cnt); }
+  __device__ static uint64_t find(const NTable& T, const uint64_t* H, const Key& key) { return nword_find(T, H, key); }
+  __device__ static uint32_t owner(const NTable& T, const uint64_t* H, const Key& key) { return slot_addr(T.N.g, hash_tables_n256(H, key, T.N.g.nbytes)).shard; }
+  __device__ static void store_key(uint64_t* dst, const Key& key, uint32_t kw) { for(uint32_t q = 0; q < kw; ++q) dst[q] = key.w[q]; }
+  __device__ static Key load_key(const NTable& T, const uint64_t* keys, uint64_t i, uint32_t kw, bool) { return load_key4(keys, i, kw, T.N.key_mask); }   // (masked either way)
+  __device__ static uint64_t digest(const NTable& T, const Key& key, uint64_t c) {
+    uint64_t h = kDigestSeed;
+    for(uint32_t q = 0; q < (T.N.g.k + 31) / 32; ++q) h = digest_mix(h ^ key.w[q]);
+    return digest_mix(h ^ c);
   }
-  __syncthreads();
-  for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x)
-    if(s_hist[i]) atomicAdd(&shard_counts[i], (unsigned long long)s_hist[i]);
-}
-
-__global__ __launch_bounds__(kBlock) void partition_scatter_nword_kernel(NTable T, const uint8_t* __restrict__ base, int64_t lo, int64_t hi,
-                                                                         unsigned long long* __restrict__ cursors, uint64_t* __restrict__ out, uint32_t kw) {
-  JF_DYN_LDS(s_raw);
-  const NGeom& N = T.N;
-  uint64_t* s_fwd = reinterpret_cast<uint64_t*>(s_raw);
-  unsigned long long* s_base = reinterpret_cast<unsigned long long*>(s_fwd + (size_t)N.g.nbytes * 256);
-  uint32_t* s_hist = reinterpret_cast<uint32_t*>(s_base + 256);
-  uint32_t* s_codes = s_hist + 256;
-  uint32_t* s_inv = s_codes + kBlock + 8;
-  load_tables_lds(s_fwd, T.fwd_tbl, N.g.nbytes);
-  const uint32_t n_shards = 1u << N.g.shard_bits;
-  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
-  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+  __device__ static uint8_t key_byte(const Key& key, uint32_t b) { return (uint8_t)(key.w[b >> 3] >> (8 * (b & 7))); }
+  // (the staging itself and not a call of it: the Lane handed back through one more function costs route_count_kernel two
+  // VGPRs, profiles/route_kernel_resources.txt)
+  __device__ static Lane stage_tile(const NTable& T, const uint8_t* __restrict__ base, int64_t tile_start, int64_t lo, int64_t hi, uint32_t* s_codes, uint32_t* s_inv) {
+    const NGeom& N = T.N;
+    const int tid = threadIdx.x;
+    NLane L;
+    load_pack16(base, tile_start + 16 * tid, lo, hi, L.c, L.v);
+    s_codes[tid + 8] = L.c; s_inv[tid + 8] = L.v;
+    if(tid < 8) { uint32_t hc, hv; load_pack16(base, tile_start - 128 + 16 * tid, lo, hi, hc, hv); s_codes[tid] = hc; s_inv[tid] = hv; }
     __syncthreads();
-    for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x) s_hist[i] = 0;
-    const NLane L = nword_stage_tile(N, base, tile * kTilePos, lo, hi, s_codes, s_inv);     // contains a barrier
-    // two sweeps over the lane's windows (the keys are 32 bytes: they are rolled again rather than kept): ranks, then stores
-    uint32_t rank[kPerLane], sh[kPerLane];
-    for_each_kmer_nword(N, L, [&](int j, const K256& key, bool valid) {
-      sh[j] = valid ? (uint32_t)(hash_tables_n256(s_fwd, key, N.g.nbytes) >> N.g.lsize_l) : 0u;
-      rank[j] = nword_wave_rank(valid, sh[j], s_hist);
-    });
-    __syncthreads();
-    for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x)
-      s_base[i] = s_hist[i] ? atomicAdd(&cursors[i], (unsigned long long)s_hist[i]) : 0ull;
-    __syncthreads();
-    for_each_kmer_nword(N, L, [&](int j, const K256& key, bool valid) {
-      if(!valid) return;
-      uint64_t* dst = out + (uint64_t)kw * (s_base[sh[j]] + rank[j]);
-#pragma unroll
-      for(uint32_t q = 0; q < 4; ++q) if(q < kw) dst[q] = key.w[q];
-    });
+    for(int i = 0; i < 4; ++i) L.fw.w[i] = ((uint64_t)s_codes[tid + 7 - 2 * i - 1] << 32) | s_codes[tid + 7 - 2 * i];
+    L.fw = k256_and(L.fw, N.key_mask);
+    L.rc = revcomp256(L.fw, N.g.k);
+    L.filled = 0;
+    for(int q = 7; q >= 0; --q) {                            // nearest halo word first
+      const uint32_t iv = s_inv[tid + q] & 0xFFFFu;
+      if(iv == 0) { L.filled += 16; continue; }
+      L.filled += (uint32_t)__ffs((int)iv) - 1;
+      break;
+    }
+    if(L.filled > N.g.k) L.filled = N.g.k;
+    return L;
   }
-}
+  template <typename F>
+  __device__ static void for_each_kmer(const NTable& T, const Lane& L, F&& f) { for_each_kmer_nword(T.N, L, f); }
+  __device__ static uint32_t route_rank(bool valid, uint32_t owner, uint32_t* s_hist) { return nword_wave_rank(valid, owner, s_hist); }
+};
 
 }  // namespace jfgpu

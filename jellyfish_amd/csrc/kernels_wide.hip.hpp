@@ -331,13 +331,16 @@ __device__ inline u128 load_key2(const uint64_t* keys, uint64_t i, u128 mask) {
 }
 
 // Slot access for the kernels written once for every key width (KeyOps, kernels.hip.hpp): hash_counter::double_size, the
-// scans, the sorted dump, the redistribution between shards, and add, update_add and look-up of a list of keys.
+// scans, the sorted dump, the redistribution between shards, add, update_add and look-up of a list of keys, and the routing
+// of a contract buffer's k-mers to their owners.
 template <> struct KeyOps<WideTable> {
   typedef u128 Key;
   struct Slot { uint64_t lo, hi; };
   static constexpr int kSlotWords = 2;
   static constexpr uint32_t kFwdLdsWords = 16 * 256;
   static constexpr bool kUpdateReturns = false;
+  typedef LaneWordsW Lane;
+  static constexpr uint32_t kHaloWords = 4, kKeyWords = 2;
   __device__ static const TableGeom& geom(const WideTable& T) { return T.W.g; }
   // stats / histo / tile counts / dump: only the hi word (count + occupancy) matters, the lo word is never touched
   __device__ static bool occupied(const WideTable& T, uint64_t i, Slot& s) { s.lo = 0; s.hi = T.slots[2 * i + 1]; return s.hi != 0; }
@@ -366,69 +369,14 @@ template <> struct KeyOps<WideTable> {
     return digest_mix(digest_mix(digest_mix(kDigestSeed ^ (uint64_t)key) ^ (uint64_t)(key >> 64)) ^ c);
   }
   __device__ static uint8_t key_byte(Key key, uint32_t b) { return (uint8_t)(key >> (8 * b)); }
+  __device__ static Lane stage_tile(const WideTable&, const uint8_t* __restrict__ base, int64_t tile_start, int64_t lo, int64_t hi, uint32_t* s_codes, uint32_t* s_inv) {
+    return stage_tile_wide(base, tile_start, lo, hi, s_codes, s_inv);
+  }
+  template <typename F>
+  __device__ static void for_each_kmer(const WideTable& T, const Lane& L, F&& f) { for_each_kmer_wide(T.W, L, [&](int j, u128 key) { f(j, key, true); }); }
+  __device__ static uint32_t route_rank(bool valid, uint32_t owner, uint32_t* s_hist) { return valid ? atomicAdd(&s_hist[owner], 1u) : 0u; }
+  __device__ static uint32_t admit_mask(const WideTable&, const Lane&) { return ~0u; }
+  __device__ static bool admits(const WideTable& T, uint32_t, int, Key key) { return bloom_admits_wide(T.bloom, key); }
 };
-
-// ---- multi-GPU: a contract buffer's two-word k-mers grouped by owner (abi_comm.inl, key path) -------------------------
-// The two passes of kernels.hip.hpp's partition_count / partition_scatter kernels for 128-bit keys: out receives two
-// 64-bit words per k-mer (low word first: what add_keys takes), counts and cursors are in k-mers.
-// BLOOM: count --bc with --gpus -- the sender asks its copy of the (read-only) Bloom counter, what it does not admit never travels
-template <bool BLOOM = false>
-__global__ __launch_bounds__(kBlock) void partition_count_wide_kernel(WideTable T, const uint8_t* __restrict__ base, int64_t lo, int64_t hi,
-                                                                      unsigned long long* __restrict__ shard_counts) {
-  __shared__ uint64_t s_fwd[16 * 256];
-  __shared__ uint32_t s_codes[kBlock + 4];
-  __shared__ uint32_t s_inv[kBlock + 4];
-  __shared__ uint32_t s_hist[256];
-  load_tables_lds(s_fwd, T.fwd_tbl, T.W.g.nbytes);
-  const uint32_t n_shards = 1u << T.W.g.shard_bits;
-  for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x) s_hist[i] = 0;
-  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
-  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    __syncthreads();
-    const LaneWordsW L = stage_tile_wide(base, tile * kTilePos, lo, hi, s_codes, s_inv);
-    for_each_kmer_wide(T.W, L, [&](int, u128 key) {
-      if(BLOOM && !bloom_admits_wide(T.bloom, key)) return;
-      const uint64_t pos = hash_tables_wide(s_fwd, key, T.W.g.nbytes);
-      atomicAdd(&s_hist[(uint32_t)(pos >> T.W.g.lsize_l)], 1u);
-    });
-  }
-  __syncthreads();
-  for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x)
-    if(s_hist[i]) atomicAdd(&shard_counts[i], (unsigned long long)s_hist[i]);
-}
-
-template <bool BLOOM = false>
-__global__ __launch_bounds__(kBlock) void partition_scatter_wide_kernel(WideTable T, const uint8_t* __restrict__ base, int64_t lo, int64_t hi,
-                                                                        unsigned long long* __restrict__ cursors, uint64_t* __restrict__ out) {
-  __shared__ uint64_t s_fwd[16 * 256];
-  __shared__ uint32_t s_codes[kBlock + 4];
-  __shared__ uint32_t s_inv[kBlock + 4];
-  __shared__ uint32_t s_hist[256];
-  __shared__ unsigned long long s_base[256];
-  load_tables_lds(s_fwd, T.fwd_tbl, T.W.g.nbytes);
-  const uint32_t n_shards = 1u << T.W.g.shard_bits;
-  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
-  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    __syncthreads();
-    for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x) s_hist[i] = 0;
-    const LaneWordsW L = stage_tile_wide(base, tile * kTilePos, lo, hi, s_codes, s_inv);     // contains a barrier
-    // two sweeps over the lane's windows (the keys are wide: they are not kept, they are rolled again): ranks, then stores
-    uint32_t rank[kPerLane]; uint32_t vmask = 0, sh[kPerLane];
-    for_each_kmer_wide(T.W, L, [&](int j, u128 key) {
-      if(BLOOM && !bloom_admits_wide(T.bloom, key)) return;      // (the same answers as the count pass: the counter is read-only here)
-      const uint32_t s = (uint32_t)(hash_tables_wide(s_fwd, key, T.W.g.nbytes) >> T.W.g.lsize_l);
-      sh[j] = s; rank[j] = atomicAdd(&s_hist[s], 1u); vmask |= 1u << j;
-    });
-    __syncthreads();
-    for(uint32_t i = threadIdx.x; i < n_shards; i += blockDim.x)
-      s_base[i] = s_hist[i] ? atomicAdd(&cursors[i], (unsigned long long)s_hist[i]) : 0ull;
-    __syncthreads();
-    for_each_kmer_wide(T.W, L, [&](int j, u128 key) {
-      if(!((vmask >> j) & 1u)) return;
-      const unsigned long long at = s_base[sh[j]] + rank[j];
-      out[2 * at] = (uint64_t)key; out[2 * at + 1] = (uint64_t)(key >> 64);
-    });
-  }
-}
 
 }  // namespace jfgpu

@@ -849,7 +849,7 @@ def test_count_gpus_n_with_a_bloom_counter_file(cli, tmp_path, k):
     """`count --bc file --gpus 2` (count_main.cc:109-119, 191-206 with hash-prefix shards; round-3 review, missing #1): every
     rank process loads the counter file and asks it before routing; the file the ranks write equals the single-process
     `count --bc` file.  k = 21 takes the item path, k = 31 the key path, k = 40 (round 6) the key path of two-word keys:
-    partition_count / scatter_wide_kernel<BLOOM> ask the counter on the sending side."""
+    route_count / route_scatter_kernel<WideTable, BLOOM> ask the counter on the sending side."""
     import random
     rng = random.Random(101 + k)
     twice = ["".join(rng.choice("ACGT") for _ in range(150)) for _ in range(1500)]

@@ -47,6 +47,7 @@ SELECTION = [
     "tests/test_gpu_wide.py::test_add_keys_is_new_and_lookup_at_every_key_width[21]",
     "tests/test_gpu_wide.py::test_add_keys_is_new_and_lookup_at_every_key_width[40]",
     "tests/test_gpu_wide.py::test_add_keys_is_new_and_lookup_at_every_key_width[100]",
+    "tests/test_gpu_route.py",
 ]
 
 

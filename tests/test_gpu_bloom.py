@@ -351,7 +351,7 @@ def test_one_pass_bloom_filter(gpu, monkeypatch, k, mode):
 def test_sharded_count_with_a_bloom_counter_equals_the_single_table(gpu, monkeypatch, k, world, items):
     """`count --bc` over hash-prefix shards (count_main.cc:109-119 with --gpus; round-3 review, missing #1): every rank
     holds the whole read-only Bloom counter and asks it on the SENDING side -- in the routing kernels of the item path
-    (k = 21: p1_ring_kernel<.., BLOOM, RouteListDirect>) and of the key path (partition_count / scatter_kernel<BLOOM>) --
+    (k = 21: p1_ring_kernel<.., BLOOM, RouteListDirect>) and of the key path (route_count / route_scatter_kernel<.., BLOOM>) --
     so what the filter does not admit never travels.  The shards together hold exactly what one table with the same
     counter attached holds."""
     monkeypatch.setenv("JFGPU_COMM_ITEMS", items)

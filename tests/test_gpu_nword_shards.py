@@ -1,6 +1,6 @@
 """Hash-prefix shards of tables of keys of three and four words, 65 <= k <= 128 (-m gpu).
 
-Every rank routes the 256-bit k-mers of its input by owner (partition_count / scatter_nword_kernel), a message carries
+Every rank routes the 256-bit k-mers of its input by owner (route_count / route_scatter_kernel<NTable>), a message carries
 ceil(2k / 64) words per k-mer (3 for k <= 96, 4 above), receivers insert with the four-word claim (add_keys_kernel<NTable>)
 or, in the UPDATE pass of `count --if`, count what is present (update_keys_kernel<NTable, true>).  Shards grow together
 (reshard_kernel<NTable>, add_pairs_kernel<NTable>), and a step is cut into pieces whose send buffers stay under a byte budget

@@ -368,7 +368,7 @@ def test_flush_in_groups_sharing_one_p2_buffer(gpu, monkeypatch):
 @pytest.mark.parametrize("k,world,max_msg", [(40, 2, None), (48, 4, "997"), (33, 1, None), (63, 2, None)])
 def test_sharded_two_word_keys_equal_single_table(gpu, monkeypatch, k, world, max_msg):
     """Hash-prefix shards of a table of two-word keys (round 4; round 3 refused k > 32 with shard_bits): every rank routes
-    the 128-bit k-mers of its input by owner (partition_count / scatter_wide_kernel), the messages carry two words per
+    the 128-bit k-mers of its input by owner (route_count / route_scatter_kernel<WideTable>), the messages carry two words per
     k-mer, receivers insert with the two-word claim.  The shards' dumps concatenated in rank order are byte-identical to the
     dump of one table of the global size under the same matrix, and nothing is lost or duplicated."""
     if max_msg:

@@ -41,7 +41,7 @@ enum {
   JFGPU_E_ALLOC = 3,      /* large_hash::array::ErrorAllocation, large_hash_array.hpp:55,169-172 */
   JFGPU_E_FULL = 4,       /* std::runtime_error("Hash full"), hash_counter.hpp:194-195 */
   JFGPU_E_HIP = 5,        /* HIP runtime error */
-  JFGPU_E_UNSUPPORTED = 6,/* combination not built (e.g. k > 128, a Bloom counter for k > 64, a one-pass filter over shards) */
+  JFGPU_E_UNSUPPORTED = 6,/* combination not built (e.g. k > 128, a one-pass filter over shards, a filter on a shard of keys of more than two words) */
   JFGPU_E_FORMAT = 7,     /* device parser: chunk is not in the strict layout it handles; give it to the host parser */
   JFGPU_E_CORRUPT = 8     /* compressed input (BGZF / BAM) is malformed or fails its CRC32 / ISIZE check: there is no
                              host path for it, the input is bad (htslib's "bgzf_read" / "truncated file" errors) */
@@ -225,7 +225,12 @@ int  jfgpu_dump_begin(jfgpu_table* t, uint64_t lower, uint64_t upper, uint64_t* 
 int  jfgpu_dump_next(jfgpu_table* t, void* out, uint64_t capacity_records, uint64_t* n_read);
 int  jfgpu_dump_end(jfgpu_table* t);
 
-/* ---- Bloom counter: `jellyfish bc` and `count --bc` (BASELINE config 3) ------------------- */
+/* ---- Bloom counter: `jellyfish bc` and `count --bc` (BASELINE config 3) -------------------
+ * Mer lengths 1 to 128, like the reference's mer_dna_bloom_counter (two 64 x 2k matrices over mer_dna): every entry point
+ * below -- jfgpu_bc_create, jfgpu_bf_create, the inserts, jfgpu_bc_keys, jfgpu_attach_bloom -- takes them all on one GPU.
+ * Above 64 bases (keys of three and four words) the insert is the direct one (jfgpu_bc_set_mode(2) is refused), and a
+ * table with a filter attached is refused by the routing and sharded entry points (jfgpu_partition_ascii_dev, the
+ * jfgpu_comm_* steps) with JFGPU_E_UNSUPPORTED. */
 typedef struct jfgpu_bloom jfgpu_bloom;   /* opaque: ceil(m/5) bytes of base-3 cells in HBM */
 typedef struct jfgpu_bloom_params {
   uint32_t k, canonical;
@@ -252,7 +257,9 @@ int  jfgpu_bc_get_info(const jfgpu_bloom* b, uint64_t* m, uint32_t* nb_hashes, u
 /* write_bits / the istream ctor: the raw ceil(m/5) bytes of a "bloomcounter" file body */
 int  jfgpu_bc_read(jfgpu_bloom* b, uint8_t* out);
 int  jfgpu_bc_load(jfgpu_bloom* b, const uint8_t* data);
-/* bloom_base::check / insert on encoded k-mers (query_main.cc Bloom branch); out[i] = 0, 1 or 2 */
+/* bloom_base::check / insert on encoded k-mers (query_main.cc Bloom branch); out[i] = 0, 1 or 2 (insert: the minimum before
+ * it).  keys: ceil(2k / 64) little-endian words per k-mer, mer_dna::data()'s layout, key after key -- one word for
+ * k <= 32, two for k <= 64, three for k <= 96, four for k <= 128; bits beyond 2k are ignored. */
 int  jfgpu_bc_keys(jfgpu_bloom* b, const uint64_t* keys, size_t n, uint8_t* out, int do_insert);
 /* count --bf-size N --bf-fp F (count_main.cc:121-131,321-323; bloom_filter.hpp:44-68): a Bloom filter of m = opt_m(F, N)
  * BITS with opt_k(F) hashes, filled by the count itself -- attached with jfgpu_attach_bloom, every k-mer sets its bits
@@ -271,7 +278,8 @@ int  jfgpu_bc_profile_enable(jfgpu_bloom* b, int on);
 int  jfgpu_bc_profile_get(jfgpu_bloom* b, int which, double* ms, uint64_t* launches, uint64_t* units);
 int  jfgpu_bc_profile_reset(jfgpu_bloom* b);
 /* count --bc: from now on jfgpu_count_* admits a k-mer only if check(m) > 1 (count_main.cc:115-118).
- * b == NULL detaches.  The Bloom counter must outlive its use. */
+ * b == NULL detaches.  The Bloom counter must outlive its use.  Any mer length up to 128 (the counter's must be the
+ * table's); the attachment stays when the table doubles. */
 int  jfgpu_attach_bloom(jfgpu_table* t, jfgpu_bloom* b);
 /* `jellyfish bc` with the input split between the GPUs (sub_commands/bc_main.cc:84-161, mer_bloom_counter::start :67-71 per
  * rank): every rank creates the same counter (jfgpu_bc_create with the same parameters: same size, same matrices), inserts

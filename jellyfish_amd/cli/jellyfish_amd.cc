@@ -471,7 +471,7 @@ int count_main(int argc, char* argv[]) {
   if(gpus_given) {
     if(gpus < 1 || (gpus & (gpus - 1)) || gpus > 256) die("--gpus must be a power of two");
     if(mer_len > 64 && (bf_size_given || !bc_path.empty()))
-      die("--gpus: --bc and --bf-size are not built for mer length " + std::to_string(mer_len) + " (Bloom counters hold keys of at most 64 bases)");
+      die("--gpus: --bc and --bf-size are not built for mer length " + std::to_string(mer_len) + " (Bloom counters of keys of more than 64 bases run on one GPU)");
     if(bf_size_given || disk)
       die("--gpus cannot be combined with --bf-size (a one-pass filter cannot be sharded by input) or --disk yet");
     // (--if and --bc over shards: every rank loads the whole counter and asks it before routing -- --bc for keys of one and
@@ -724,12 +724,14 @@ int bc_main(int argc, char* argv[]) {
   if(!mer_len) die("Error: mandatory switch missing: -m, --mer-len");
   if(!size_given) die("Error: mandatory switch missing: -s, --size");
   if(files.empty() && generator.empty()) die("Error: at least 1 file argument is required");
-  if(mer_len > 64) die("jellyfish-amd: Bloom counters for mer length > 64 are not built");
+  if(mer_len > 128) die("jellyfish-amd: mer length > 128 (more than four key words) is not built");
   // --gpus N (like count --gpus N: this process starts the ranks, or is one): every rank inserts its part of every file into
   // its own counter, the counters are merged on the devices (jfgpu_comm_bc_merge) and rank 0 writes the file
   rank_env renv;
   if(gpus_given) {
     if(gpus < 1 || (gpus & (gpus - 1)) || gpus > 256) die("--gpus must be a power of two");
+    if(mer_len > 64)
+      die("--gpus: bc is not built for mer length " + std::to_string(mer_len) + " (Bloom counters of keys of more than 64 bases run on one GPU)");
     if(host_parse || !generator.empty()) die("--gpus cannot be combined with --host-parse or -g yet");
     renv = read_rank_env();
     if(!renv.is_rank) return spawn_ranks(gpus, argv);

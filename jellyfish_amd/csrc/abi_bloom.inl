@@ -6,6 +6,7 @@ struct jfgpu_bloom {
   hipStream_t stream = nullptr;
   TableGeom g{};                 // only k / key_mask / canonical / nbytes are used (encode side)
   bool wide = false; WideGeom wg{};   // 33 <= k <= 64: two-word keys
+  bool nword = false; NGeom ng{};     // 65 <= k <= 128: keys of three and four words (kernels_nword.hip.hpp), direct path only
   uint64_t m = 0; uint32_t nh = 0;
   Gf2Matrix m1, m2;
   uint64_t *d_t1 = nullptr, *d_t2 = nullptr;
@@ -64,7 +65,7 @@ static int bloom_create(const jfgpu_bloom_params* p, jfgpu_bloom** out, uint32_t
   if(!p || !out) return fail(JFGPU_E_INVALID, "null argument");
   *out = nullptr;
   if(p->k < 1) return fail(JFGPU_E_INVALID, "mer length must be >= 1");
-  if(p->k > 64) return fail(JFGPU_E_UNSUPPORTED, "mer length > 64 (more than two key words) is not built yet");
+  if(p->k > 128) return fail(JFGPU_E_UNSUPPORTED, "mer length > 128 (more than four key words) is not built");
   if(p->m < 1 || p->nb_hashes < 1 || p->nb_hashes > 64) return fail(JFGPU_E_INVALID, "bad Bloom counter size / number of hashes");
   int ndev = 0;
   if(hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(JFGPU_E_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
@@ -74,7 +75,11 @@ static int bloom_create(const jfgpu_bloom_params* p, jfgpu_bloom** out, uint32_t
   HIP_TRY(hipSetDevice(dev));
   std::unique_ptr<jfgpu_bloom> b(new jfgpu_bloom);
   b->device = dev; b->m = p->m; b->nh = p->nb_hashes; b->kind = kind;
-  if(p->k > 32) {
+  if(p->k > 64) {
+    b->nword = true;
+    if(!nword_geom_init(b->ng, p->k, std::max<uint32_t>(kNTileBits, nword_min_lsize(p->k)), p->canonical ? 1 : 0)) return fail(JFGPU_E_INVALID, "bad mer length");
+    b->g = b->ng.g;
+  } else if(p->k > 32) {
     b->wide = true;
     if(!wide_geom_init(b->wg, p->k, std::max<uint32_t>(kMaxTileBits, wide_min_lsize(p->k)), p->canonical ? 1 : 0)) return fail(JFGPU_E_INVALID, "bad mer length");
     b->g = b->wg.g;
@@ -245,13 +250,14 @@ int jfgpu_bc_keys(jfgpu_bloom* b, const uint64_t* keys, size_t n, uint8_t* out, 
   rc = bloom_flush(b); if(rc) return rc;
   if(!n) return JFGPU_OK;
   uint64_t* d_k = nullptr; uint8_t* d_o = nullptr;
-  const size_t kw = b->wide ? 2 : 1;                       // words per key (little-endian words, like jfgpu_add_keys)
+  const size_t kw = b->nword ? (2 * b->g.k + 63) / 64 : b->wide ? 2 : 1;      // words per key (little-endian words, like jfgpu_add_keys)
   HIP_TRY(hipMalloc((void**)&d_k, n * 8 * kw));
   if(hipMalloc((void**)&d_o, n) != hipSuccess) { hipFree(d_k); return fail(JFGPU_E_ALLOC, "hipMalloc"); }
   hipError_t e = hipMemcpyAsync(d_k, keys, n * 8 * kw, hipMemcpyHostToDevice, b->stream);
   if(e == hipSuccess) {
     const int grid = (int)std::max<size_t>(1, std::min<size_t>((n + kBlock - 1) / kBlock, (size_t)b->n_cu * 8));
-    if(b->wide) hipLaunchKernelGGL(bloom_keys_wide_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->wg.key_mask, (const uint64_t*)d_k, (uint64_t)n, d_o, do_insert);
+    if(b->nword) hipLaunchKernelGGL(bloom_keys_nword_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->ng.key_mask, (uint32_t)kw, (const uint64_t*)d_k, (uint64_t)n, d_o, do_insert);
+    else if(b->wide) hipLaunchKernelGGL(bloom_keys_wide_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->wg.key_mask, (const uint64_t*)d_k, (uint64_t)n, d_o, do_insert);
     else
     hipLaunchKernelGGL(bloom_keys_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), (const uint64_t*)d_k, (uint64_t)n, d_o, do_insert);
     e = hipGetLastError();
@@ -318,7 +324,6 @@ int jfgpu_attach_bloom(jfgpu_table* t, jfgpu_bloom* b) {   // count --bc (count_
     if(b->g.k != t->g.k) return fail(JFGPU_E_INVALID, "Invalid mer length in bloom filter");
     // a shard: the counter is asked on the sending side of the exchange (abi_comm.inl: comm_filter_ok), never on arrival
     if(t->g.shard_bits && b->kind != 0) return fail(JFGPU_E_UNSUPPORTED, "sharded tables take a Bloom counter (count --bc), not a one-pass filter (--bf-size)");
-    if(t->nword) return fail(JFGPU_E_UNSUPPORTED, "Bloom filters for mer length > 64 are not built");
   }
   // the cache of admitted k-mers belongs to one attachment: its answers are this counter's
   if(t->d_bcache) {
@@ -327,12 +332,12 @@ int jfgpu_attach_bloom(jfgpu_table* t, jfgpu_bloom* b) {   // count --bc (count_
     hipFree(t->d_bcache); t->d_bcache = nullptr;
   }
   t->bcache_state = 0;
-  if(!b) { memset(&t->dt.bloom, 0, sizeof t->dt.bloom); memset(&t->wt.bloom, 0, sizeof t->wt.bloom); return JFGPU_OK; }
+  if(!b) { memset(&t->dt.bloom, 0, sizeof t->dt.bloom); memset(&t->wt.bloom, 0, sizeof t->wt.bloom); memset(&t->nt.bloom, 0, sizeof t->nt.bloom); return JFGPU_OK; }
   rc = bloom_flush(b); if(rc) return rc;
   HIP_TRY(hipStreamSynchronize(b->stream));
-  if(t->wide) t->wt.bloom = b->view(); else t->dt.bloom = b->view();
+  if(t->nword) t->nt.bloom = b->view(); else if(t->wide) t->wt.bloom = b->view(); else t->dt.bloom = b->view();
   { uint64_t c[CTR_COUNT]; rc = read_counters(t, c); if(rc) return rc; t->mers_seen = c[CTR_MERS]; }
-  if(b->kind != 0 || t->wide || t->tun.bloom_cache == 0) t->bcache_state = -1;      // (a one-pass filter changes as it is asked: nothing to remember)
+  if(b->kind != 0 || t->wide || t->nword || t->tun.bloom_cache == 0) t->bcache_state = -1;      // (a one-pass filter changes as it is asked: nothing to remember)
   else if(t->tun.bloom_cache == 1) { rc = bloom_cache_enable(t); if(rc) return rc; }
   return JFGPU_OK;
 }

@@ -212,7 +212,11 @@ __global__ __launch_bounds__(1024) void comm_claims_kernel(const unsigned long l
 
 // A Bloom counter attached to a shard (count --bc) is asked on the SENDING side, every rank holding the whole read-only
 // counter.  A one-pass filter (--bf-size) changes as it is asked and would see only its rank's reads; two-word keys: not built.
+// Keys of three and four words: the routing kernels take no filter at all (KeyOps<NTable> has no admits), so a table with one
+// attached is refused here rather than routed unfiltered.
 int comm_filter_ok(const jfgpu_table* t) {
+  if(t->nword && t->nt.bloom.data)
+    return fail(JFGPU_E_UNSUPPORTED, "--bc and --bf-size over shards are not built for mer length " + std::to_string(t->g.k) + " (the routing kernels of keys of more than two words take no filter)");
   if(t->wide && t->wt.bloom.data && t->wt.bloom.kind != 0) return fail(JFGPU_E_UNSUPPORTED, "--bf-size with --gpus: a one-pass filter cannot be sharded by input");
   if(!t->wide && t->dt.bloom.data && t->dt.bloom.kind != 0) return fail(JFGPU_E_UNSUPPORTED, "--bf-size with --gpus: a one-pass filter cannot be sharded by input");
   return JFGPU_OK;

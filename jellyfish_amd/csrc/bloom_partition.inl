@@ -23,11 +23,11 @@ void bloom_prof_collect(jfgpu_bloom* b) {
   b->spans.clear();
 }
 
-// Segments, bucket bits.  part_ok == false: the direct kernel is the only path (tiny or > 128 GiB filters, two-word keys).
+// Segments, bucket bits.  part_ok == false: the direct kernel is the only path (tiny or > 128 GiB filters, keys of two to four words).
 void bloom_part_init(jfgpu_bloom* b) {
   b->part_ok = false;
   const uint64_t n_seg = (b->data_bytes + ((1ull << kBloomSegBits) - 1)) >> kBloomSegBits;
-  if(b->wide || n_seg == 0 || n_seg > (1ull << 21)) return;
+  if(b->wide || b->nword || n_seg == 0 || n_seg > (1ull << 21)) return;
   uint32_t sb = 0;
   while((1ull << sb) < n_seg) ++sb;
   uint32_t b1, b2;
@@ -87,7 +87,8 @@ int bloom_launch_direct(jfgpu_bloom* b, const uint8_t* base, int64_t lo, int64_t
   const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_tiles, (int64_t)b->n_cu * 8));
   BloomProf ps(b, BS_DIRECT, (uint64_t)(hi - lo));
-  if(b->wide) hipLaunchKernelGGL(bloom_insert_ascii_wide_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->wg, base, lo, hi, b->d_mers);
+  if(b->nword) hipLaunchKernelGGL(bloom_insert_ascii_nword_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->ng, base, lo, hi, b->d_mers);
+  else if(b->wide) hipLaunchKernelGGL(bloom_insert_ascii_wide_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->wg, base, lo, hi, b->d_mers);
   else hipLaunchKernelGGL(bloom_insert_ascii_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->g, base, lo, hi, b->d_mers);
   HIP_TRY(hipGetLastError());
   return JFGPU_OK;

@@ -297,8 +297,10 @@ int launch_count_chunk(jfgpu_table* t, const char* d_bases, size_t n) {
     t->pristine = false;
     const int64_t nt = (hi + kTilePos - 1) / kTilePos;
     ProfScope ps(t, 0, n);
-    if(t->returning) hipLaunchKernelGGL(count_ascii_nword_kernel<true>, dim3(grid_for(t, (uint64_t)nt)), dim3(kBlock), 0, t->stream, t->nt, base, lo, hi, t->operation);
-    else             hipLaunchKernelGGL(count_ascii_nword_kernel<false>, dim3(grid_for(t, (uint64_t)nt)), dim3(kBlock), 0, t->stream, t->nt, base, lo, hi, t->operation);
+    const bool bl = t->nt.bloom.data != nullptr;
+#define CN(RT, BL) hipLaunchKernelGGL((count_ascii_nword_kernel<RT, BL>), dim3(grid_for(t, (uint64_t)nt)), dim3(kBlock), 0, t->stream, t->nt, base, lo, hi, t->operation)
+    if(t->returning) { if(bl) CN(true, true); else CN(true, false); } else { if(bl) CN(false, true); else CN(false, false); }
+#undef CN
     HIP_TRY(hipGetLastError());
     return JFGPU_OK;
   }

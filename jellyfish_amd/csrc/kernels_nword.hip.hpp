@@ -13,6 +13,7 @@
 // dump sorts in LDS).  Insert path: global atomics only (this range is a correctness feature, not a benchmark).
 #pragma once
 #include "kernels.hip.hpp"
+#include "kernels_bloom.hip.hpp"
 
 namespace jfgpu {
 
@@ -123,6 +124,7 @@ struct NTable {
   uint64_t* ovf_key; uint64_t* ovf_cnt; uint64_t ovf_mask;
   uint64_t* counters;
   uint32_t max_probe;
+  DevBloom bloom;             // count --bc / --bf-size filter (data == nullptr: none)
 };
 
 __device__ inline DevTable ovf_view(const NTable& T) {
@@ -136,6 +138,13 @@ __device__ inline uint64_t hash_tables_n256(const uint64_t* tbl, const K256& key
   uint64_t pos = 0;
   for(uint32_t b = 0; b < nbytes; ++b) pos ^= tbl[b * 256 + ((key.w[b >> 3] >> (8 * (b & 7))) & 0xFF)];
   return pos;
+}
+
+// Bloom counter on keys of three and four words: h0 = M1 * key, h1 = M2 * key with 64 x 2k matrices
+// (mer_dna_bloom_counter.hpp:19-34); the byte tables (up to 32 x 256 entries each) are read through the caches.
+__device__ inline bool bloom_admits_nword(const DevBloom& B, const K256& key) {
+  const uint64_t h0 = hash_tables_n256(B.tbl1, key, B.nbytes), h1 = hash_tables_n256(B.tbl2, key, B.nbytes);
+  return B.kind == 1 ? bloom_filter_insert(B, h0, h1) : bloom_all_two(B, h0, h1);
 }
 
 struct NSlot { uint64_t lo[3]; uint64_t hi_low; };
@@ -264,7 +273,9 @@ __device__ inline bool nword_complete(const uint64_t* sp) { return sp[3] != 0 &&
 // ---- sequence -> 256-bit k-mers -----------------------------------------------------------------------------
 // Halo: k - 1 <= 127 bases = 8 code words before the lane's own 16.  Validity is tracked the way mer_iterator does
 // (`filled`): the number of consecutive valid bases ending at the current position, capped at k.
-template <bool RETURNING>
+// FILTERED: count --bc / --bf-size (count_main.cc:115-131) -- T.bloom is asked for every valid sighting, before the run
+// merge (a one-pass filter changes as it is asked: once per run would undercount); CTR_MERS counts every window either way.
+template <bool RETURNING, bool FILTERED>
 __global__ __launch_bounds__(kBlock) void count_ascii_nword_kernel(NTable T, const uint8_t* __restrict__ base, int64_t lo, int64_t hi, int op) {
   __shared__ uint32_t s_codes[kBlock + 8];
   __shared__ uint32_t s_inv[kBlock + 8];
@@ -313,6 +324,7 @@ __global__ __launch_bounds__(kBlock) void count_ascii_nword_kernel(NTable T, con
       if(filled < k) continue;
       ++my_mers;
       const K256 key = (N.g.canonical && k256_less(rc, fw)) ? rc : fw;
+      if constexpr(FILTERED) { if(!bloom_admits_nword(T.bloom, key)) continue; }
       if(run && k256_eq(key, prev)) { ++run; continue; }
       if(run) apply(prev, run);
       prev = key; run = 1;
@@ -432,5 +444,41 @@ template <> struct KeyOps<NTable> {
   __device__ static void for_each_kmer(const NTable& T, const Lane& L, F&& f) { for_each_kmer_nword(T.N, L, f); }
   __device__ static uint32_t route_rank(bool valid, uint32_t owner, uint32_t* s_hist) { return nword_wave_rank(valid, owner, s_hist); }
 };
+
+// ---- Bloom counter over keys of three and four words (jellyfish bc, 65 <= k <= 128) ---------------------------------------
+// Every valid window is one bloom_insert (no run merge: a k-mer seen twice in a row must read 2).  The two byte tables
+// (2 x ceil(2k / 8) x 2 KiB: 100 KiB at k = 100, 128 KiB at k = 128) are read through the caches, as the two-word kernel
+// reads its 64 KiB and count_ascii_nword_kernel its own (DESIGN.md 3.5 on staging them in LDS instead).
+__global__ __launch_bounds__(kBlock) void bloom_insert_ascii_nword_kernel(DevBloom B, NGeom N, const uint8_t* __restrict__ base,
+                                                                          int64_t lo, int64_t hi, unsigned long long* __restrict__ mers) {
+  __shared__ uint32_t s_codes[kBlock + 8];
+  __shared__ uint32_t s_inv[kBlock + 8];
+  NTable T; T.N = N;                                       // (stage_tile and for_each_kmer look at the geometry only)
+  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
+  uint32_t my = 0;
+  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    __syncthreads();
+    const NLane L = KeyOps<NTable>::stage_tile(T, base, tile * kTilePos, lo, hi, s_codes, s_inv);
+    for_each_kmer_nword(N, L, [&](int, const K256& key, bool valid) {
+      if(!valid) return;
+      ++my;
+      bloom_insert(B, hash_tables_n256(B.tbl1, key, B.nbytes), hash_tables_n256(B.tbl2, key, B.nbytes));
+    });
+  }
+  uint64_t w = my;
+  for(int o = 32; o > 0; o >>= 1) w += __shfl_down(w, o, 64);
+  if((threadIdx.x & 63) == 0 && w) atomicAdd(mers, (unsigned long long)w);
+}
+
+// check() / insert() on encoded keys of kw = ceil(2k / 64) words each (mer_dna::data() layout)
+__global__ __launch_bounds__(kBlock) void bloom_keys_nword_kernel(DevBloom B, K256 key_mask, uint32_t kw, const uint64_t* __restrict__ keys, uint64_t n,
+                                                                  uint8_t* __restrict__ out, int do_insert) {
+  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const K256 key = load_key4(keys, i, kw, key_mask);
+    const uint64_t h0 = hash_tables_n256(B.tbl1, key, B.nbytes), h1 = hash_tables_n256(B.tbl2, key, B.nbytes);
+    const uint32_t r = do_insert ? bloom_insert(B, h0, h1) : bloom_check(B, h0, h1);
+    if(out) out[i] = (uint8_t)r;
+  }
+}
 
 }  // namespace jfgpu

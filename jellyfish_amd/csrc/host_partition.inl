@@ -534,7 +534,11 @@ int part_flush_t(jfgpu_table* t) {
     constexpr uint32_t kG2Single = 4;                       // blocks per P1 bucket
     constexpr bool kSingleItems = sizeof(ITEM) == 4 || sizeof(ITEM) == 8 || sizeof(ITEM) == 16;
     uint32_t cap2 = 0, single_groups = 1; unsigned int* d_gcur2 = nullptr; uint64_t* d_off2 = nullptr; ITEM* out2 = nullptr; bool own2 = false;
-    const bool single_ok = kSingleItems && t->tun.p2_single && (sizeof(ITEM) >= 8 || pair) && t->tun.flush_groups <= 1;      // (4-byte items: pairs only; 8- and 16-byte items: single tiles)
+    // (4-byte items: pairs only; 8- and 16-byte items: single tiles.  The single-pass kernel places one destination per thread
+    // (GranuleLds: kGranMaxB = 1024); from 2^34 slots on b2 is 11, and what is not routed to pairs takes the exact scheme,
+    // whose kernels go to kMaxBuckets = 2048 destinations)
+    const bool single_ok = kSingleItems && t->tun.p2_single && (sizeof(ITEM) >= 8 || pair) && t->tun.flush_groups <= 1 &&
+                           (1u << (t->pg.b2 - (pair ? 1 : 0))) <= (uint32_t)kGranMaxB;
     const uint64_t n_dest = pair ? n_tiles >> 1 : n_tiles;
     // The ring kernels of P2 read every all-ones item as a hole and load 16 bytes at a time: right for granule batches (fixed
     // regions, holes marked so), wrong for an exact two-pass batch, which stores every item -- the all-ones one too when

@@ -1,6 +1,9 @@
 // tests/kernels/stage_harness.hip -- TEST INFRASTRUCTURE: the engine's translation unit plus entry points (jfkt_*) that
 // launch ONE stage of the partitioned insert path -- P1 (p1_ring_kernel), P2 (p2_ring_roles_kernel / p2_ring_kernel, each
 // followed by p1_stragglers_kernel), T (tile_rank_insert_kernel) -- with the caller's arguments and copy its outputs back.
+// Likewise the sort-based P2 at 4-, 8- and 16-byte items (jfkt_p2_sort: p2_granule_kernel + granule_finish[_range]_kernel;
+// p2_kernel + scan_matrix_kernel + p2_scatter_sorted_kernel) and the two-word path's own stages (jfkt_p1_wide:
+// p1_wide_granule_kernel; jfkt_tile_wide: tile_insert_wide_kernel, tile_insert_wide_pipe_kernel, items_direct_wide_kernel).
 //
 // The engine is one translation unit, so including it here gives the harness the anonymous namespace, jfgpu_table, the
 // descriptors and the kernels.  The library built from this file is a superset of the engine: a table made by ITS
@@ -25,6 +28,22 @@ struct RecordDirect {
     const unsigned long long at = atomicAdd(n, 1ull);
     if(at < cap) { rec[3 * at] = dest; rec[3 * at + 1] = item; rec[3 * at + 2] = cnt; }
   }
+};
+
+// DIRECT of p2_granule_kernel (called with the P1 bucket and the item): destination, low word, high word; the kernel adds
+// its count of such calls to direct_counter(), which is the harness's own
+template <typename ITEM>
+struct RecordDirectT {
+  uint64_t* rec; unsigned long long* n; uint64_t cap; unsigned long long* ctr; uint32_t b2e, tag_bits;
+  __device__ void operator()(uint32_t bucket, ITEM item) const {
+    const unsigned long long at = atomicAdd(n, 1ull);
+    if(at < cap) {
+      rec[3 * at] = ((uint64_t)bucket << b2e) | ((uint64_t)(item >> tag_bits) & ((1ull << b2e) - 1));
+      rec[3 * at + 1] = (uint64_t)item;
+      if constexpr(sizeof(ITEM) == 16) rec[3 * at + 2] = (uint64_t)(item >> 64); else rec[3 * at + 2] = 0;
+    }
+  }
+  __device__ unsigned long long* direct_counter() const { return ctr; }
 };
 
 // device buffers of one call, freed when it returns
@@ -95,12 +114,13 @@ uint64_t jfkt_const(int which) {
 
 // The table's geometry as the kernels see it (TableGeom), for tests that restate make_item:
 // 0 lsize_l 1 tile_bits 2 rem_bits 3 tag_bits 4 cnt_bits 5 slot32 6 hash_xs 7 nbytes 8 returning 9 part_ok 10 b1 11 b2
-// 12 rest_shift 13 item32 14 lsize_g 15 canonical
+// 12 rest_shift 13 item32 14 lsize_g 15 canonical 16 tag_full (two-word keys: tile_bits + rem_bits) 17 key_bits (2k)
 int jfkt_geom(jfgpu_table* t, uint64_t* out, uint32_t n) {
   if(!t || !out) return fail(JFGPU_E_INVALID, "null argument");
-  const uint64_t v[16] = {t->g.lsize_l, t->g.tile_bits, t->g.rem_bits, t->g.tag_bits, t->g.cnt_bits, t->g.slot32, t->g.hash_xs, t->g.nbytes,
-                          (uint64_t)t->returning, (uint64_t)t->part_ok, t->pg.b1, t->pg.b2, t->pg.rest_shift, (uint64_t)t->item32, t->g.lsize_g, t->g.canonical};
-  for(uint32_t i = 0; i < n && i < 16; ++i) out[i] = v[i];
+  const uint64_t v[18] = {t->g.lsize_l, t->g.tile_bits, t->g.rem_bits, t->g.tag_bits, t->g.cnt_bits, t->g.slot32, t->g.hash_xs, t->g.nbytes,
+                          (uint64_t)t->returning, (uint64_t)t->part_ok, t->pg.b1, t->pg.b2, t->pg.rest_shift, (uint64_t)t->item32, t->g.lsize_g, t->g.canonical,
+                          t->wide ? t->wt.W.tag_full : t->g.tile_bits + t->g.rem_bits, t->wide ? t->wt.W.g.key_bits : t->g.key_bits};
+  for(uint32_t i = 0; i < n && i < 18; ++i) out[i] = v[i];
   return JFGPU_OK;
 }
 
@@ -288,6 +308,230 @@ int jfkt_p1(jfgpu_table* t, int variant, uint32_t b1, const uint8_t* bases, uint
   if(rec_cap) HIP_TRY(hipMemcpy(rec, d_rec, 3 * (size_t)rec_cap * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(n_rec, d_nrec, 8, hipMemcpyDeviceToHost));
   if(ctr) { ctr[0] = c1[CTR_MERS] - c0[CTR_MERS]; ctr[1] = c1[CTR_DIRECT] - c0[CTR_DIRECT]; }
+  say(launched, launched_len, name);
+  return JFGPU_OK;
+}
+
+// ---- the sort-based P2 alone ------------------------------------------------------------------------------------------
+// scheme 0 (single pass): p2_granule_kernel<ITEM, RecordDirectT<ITEM>, PER> with (ITEM, PER) = (uint32_t, kP2PairPer),
+// (uint64_t, kP2MidPer), (u128, kP2WidePer), grid (4, nbk), then granule_finish_kernel over all n_dest destinations -- or,
+// with fr_nd > 0, granule_finish_range_kernel over destinations [fr_d0, fr_d0 + fr_nd).
+// scheme 1 (exact): p2_kernel<ITEM, false>, scan_matrix_kernel, p2_scatter_sorted_kernel<ITEM, PER> with the host's PER
+// (28 for pairs of tiles, else 16 / 14 / 7), 32 workgroups a bucket; base[q]: where bucket q's items start in out.
+// Items of 16 bytes are pairs of 64-bit words, low word first.  Segments as in jfkt_p2.
+// out: n_out items in and out (scheme 0: n_out = n_dest * cap).  gcur: 2 * n_dest words out (scheme 0).  off2: 2 * n_dest
+// words in and out (scheme 0).  goff: n_dest + 1 words in and out (scheme 1).  rec: 3 * rec_cap words (destination, low, high).
+int jfkt_p2_sort(jfgpu_table* t, int scheme, uint32_t item_bytes, int pair, uint32_t b2e, uint32_t tag_bits, uint32_t n_seg,
+                 const void* const* seg_items, const uint64_t* n_items, const uint64_t* const* seg_off, const uint64_t* n_off, const uint32_t* sh,
+                 uint32_t cap, uint32_t bucket0, uint32_t nbk, uint32_t n_dest, void* out, uint64_t n_out, uint32_t* gcur, uint64_t* off2,
+                 uint32_t fr_d0, uint32_t fr_nd, const uint64_t* base, uint64_t* goff,
+                 uint64_t* rec, uint64_t rec_cap, uint64_t* n_rec, uint64_t* ctr_direct, char* launched, size_t launched_len) {
+  int rc = use(t); if(rc) return rc;
+  if(scheme < 0 || scheme > 1 || (item_bytes != 4 && item_bytes != 8 && item_bytes != 16)) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: scheme 0 or 1, items of 4, 8 or 16 bytes");
+  if(!n_seg || n_seg > (uint32_t)kMaxSeg || !nbk) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: bad segment or bucket count");
+  if(b2e > (scheme == 0 ? 10u : 11u)) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: the single-pass kernel places one destination per thread (at most 1024), the exact ones take 2048");
+  if(tag_bits + b2e > 8 * item_bytes || tag_bits >= 8 * item_bytes) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: the sub-bucket lies outside the item");
+  if(pair && item_bytes != 4) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: pairs of tiles take 4-byte items");
+  if(((uint64_t)(bucket0 + nbk) << b2e) > n_dest) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: launched destinations beyond n_dest");
+  if(scheme == 0 && (!cap || cap % kGran || (uint64_t)n_dest * cap != n_out)) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: regions are whole reservations, out is n_dest regions");
+  if(scheme == 0 && fr_nd && (uint64_t)fr_d0 + fr_nd > n_dest) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: the finish range lies outside the destinations");
+  for(uint32_t s = 0; s < n_seg; ++s) {
+    const uint64_t need = ((uint64_t)(bucket0 + nbk - 1) << sh[s]) + 2;
+    if(sh[s] > 1 || n_off[s] < need) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: offsets do not cover the launched buckets");
+    for(uint32_t j = bucket0; j < bucket0 + nbk; ++j) {
+      const uint64_t a = seg_off[s][(size_t)j << sh[s]], b = seg_off[s][((size_t)j << sh[s]) + 1];
+      if(a > b || b > n_items[s]) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: a bucket's range lies outside its segment");
+    }
+  }
+  if(scheme == 1) {      // every launched bucket's items inside out
+    if(!base) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: the exact scheme needs base");
+    for(uint32_t j = bucket0; j < bucket0 + nbk; ++j) {
+      uint64_t n = 0;
+      for(uint32_t s = 0; s < n_seg; ++s) {                 // (what the kernels store: every entry, but for a granule segment's holes)
+        const uint64_t a = seg_off[s][(size_t)j << sh[s]], b = seg_off[s][((size_t)j << sh[s]) + 1];
+        n += b - a;
+        const uint8_t* e = (const uint8_t*)seg_items[s];
+        for(uint64_t i = a; sh[s] && i < b; ++i) {
+          bool hole = true;
+          for(uint32_t c = 0; c < item_bytes; ++c) hole = hole && e[i * item_bytes + c] == 0xFF;
+          n -= hole;
+        }
+      }
+      if(n >> 32 || base[j] + n > n_out) return fail(JFGPU_E_INVALID, "jfkt_p2_sort: a bucket's items do not fit out behind base");
+    }
+  }
+  DevBufs D;
+  SegList S; memset(&S, 0, sizeof S);
+  S.n = n_seg;
+  for(uint32_t s = 0; s < n_seg; ++s) {
+    uint8_t* di; uint64_t* doff;
+    KT_TRY(D.put(&di, (const uint8_t*)seg_items[s], (size_t)n_items[s] * item_bytes, 16));
+    KT_TRY(D.put(&doff, seg_off[s], (size_t)n_off[s]));
+    S.items[s] = di; S.off[s] = doff; S.sh[s] = sh[s];
+  }
+  uint8_t* d_out; uint64_t* d_rec; unsigned long long *d_nrec, *d_ctr;
+  KT_TRY(D.put(&d_out, (const uint8_t*)out, (size_t)n_out * item_bytes));
+  KT_TRY(D.get(&d_rec, 3 * (size_t)rec_cap, 0));
+  KT_TRY(D.get(&d_nrec, 1, 0));
+  KT_TRY(D.get(&d_ctr, 1, 0));
+  const dim3 block(kPBlock);
+  std::string name;
+  if(scheme == 0) {
+    unsigned int* d_gcur; uint64_t* d_off2;
+    KT_TRY(D.get(&d_gcur, 2 * (size_t)n_dest, 0));
+    KT_TRY(D.put(&d_off2, off2, 2 * (size_t)n_dest));
+    const dim3 g1p(4, nbk);
+#define KT_G(I, PER) do { \
+      const RecordDirectT<I> rd{d_rec, d_nrec, rec_cap, d_ctr, b2e, tag_bits}; \
+      const size_t lds = (size_t)kPBlock * PER * sizeof(I); \
+      HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<I, RecordDirectT<I>, PER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+      hipLaunchKernelGGL((p2_granule_kernel<I, RecordDirectT<I>, PER>), g1p, block, lds, t->stream, rd, b2e, tag_bits, S, cap, d_gcur, d_gcur + n_dest, (I*)d_out, bucket0); \
+      name = "p2_granule_kernel<" #I ",RecordDirectT<" #I ">," #PER ">"; } while(0)
+    if(item_bytes == 4) KT_G(uint32_t, kP2PairPer); else if(item_bytes == 8) KT_G(uint64_t, kP2MidPer); else KT_G(u128, kP2WidePer);
+#undef KT_G
+    HIP_TRY(hipGetLastError());
+    if(fr_nd) { hipLaunchKernelGGL(granule_finish_range_kernel, dim3(256), dim3(256), 0, t->stream, d_gcur, cap, n_dest, d_off2, fr_d0, fr_nd); name += "+granule_finish_range_kernel"; }
+    else { hipLaunchKernelGGL(granule_finish_kernel, dim3(1024), dim3(256), 0, t->stream, d_gcur, cap, n_dest, d_off2); name += "+granule_finish_kernel"; }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    HIP_TRY(hipMemcpy(gcur, d_gcur, 2 * (size_t)n_dest * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(off2, d_off2, 2 * (size_t)n_dest * 8, hipMemcpyDeviceToHost));
+  } else {
+    const int g2 = 32;
+    const uint32_t nb1 = bucket0 + nbk, nb2e = 1u << b2e;
+    uint32_t* d_M2; uint64_t *d_goff, *d_base;
+    KT_TRY(D.get(&d_M2, (size_t)nb1 * g2 * nb2e, 0));
+    KT_TRY(D.put(&d_goff, goff, (size_t)n_dest + 1));
+    KT_TRY(D.put(&d_base, base, nb1));
+    PartGeom pg2; memset(&pg2, 0, sizeof pg2);
+    pg2.b2 = b2e;
+    const dim3 grid(g2, nbk);
+#define KT_X(I, PER) do { \
+      hipLaunchKernelGGL((p2_kernel<I, false>), grid, block, 0, t->stream, pg2, tag_bits, S, d_M2, (const uint64_t*)d_goff, (I*)d_out, bucket0); \
+      hipLaunchKernelGGL(scan_matrix_kernel, dim3(nbk), dim3(1024), 0, t->stream, d_M2, (uint32_t)g2, nb2e, (const uint64_t*)d_base, d_goff, bucket0); \
+      hipLaunchKernelGGL((p2_scatter_sorted_kernel<I, PER>), grid, block, (size_t)kPBlock * PER * sizeof(I), t->stream, pg2, tag_bits, S, (const uint32_t*)d_M2, (const uint64_t*)d_goff, (I*)d_out, bucket0); \
+      name = "p2_kernel<" #I ",false>+scan_matrix_kernel+p2_scatter_sorted_kernel<" #I "," #PER ">"; } while(0)
+    if(item_bytes == 4 && pair) KT_X(uint32_t, kP2PairPer); else if(item_bytes == 4) KT_X(uint32_t, 16); else if(item_bytes == 8) KT_X(uint64_t, 14); else KT_X(u128, 7);
+#undef KT_X
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    HIP_TRY(hipMemcpy(goff, d_goff, ((size_t)n_dest + 1) * 8, hipMemcpyDeviceToHost));
+  }
+  HIP_TRY(hipMemcpy(out, d_out, (size_t)n_out * item_bytes, hipMemcpyDeviceToHost));
+  if(rec_cap) HIP_TRY(hipMemcpy(rec, d_rec, 3 * (size_t)rec_cap * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n_rec, d_nrec, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ctr_direct, d_ctr, 8, hipMemcpyDeviceToHost));
+  say(launched, launched_len, name);
+  return JFGPU_OK;
+}
+
+// ---- P1w alone --------------------------------------------------------------------------------------------------------
+// p1_wide_granule_kernel<table's RETURNING, false, XS> (XS: the table's matrix is the xor-shift one) over bases[lo, hi) with
+// 2^b1 buckets, `grid` workgroups.  PartGeom as in jfkt_p1, b2 = what is left of the tile index.  This kernel's overflow
+// is not a template argument: what a region cannot take is claimed in the table itself (wide_item_direct), which needs
+// the buckets to be groups of whole tiles -- so b1 beyond the table's tile-index bits is taken only with regions that
+// cannot overflow (cap >= hi - lo + grid * kGran).
+// out: (2^b1 + 1) * cap items of two words in and out (the last region is a guard); gcur: 2 * 2^b1 words out; tot: 2^b1 out;
+// ctr[2]: what the kernel added to the table's k-mer counter and to its direct counter.
+int jfkt_p1_wide(jfgpu_table* t, uint32_t b1, const uint8_t* bases, uint64_t n_bases, int64_t lo, int64_t hi, uint32_t cap, uint32_t grid,
+                 uint64_t* out, uint32_t* gcur, uint64_t* tot, uint64_t* ctr, char* launched, size_t launched_len) {
+  int rc = use(t); if(rc) return rc;
+  if(!t->wide || !t->item128 || t->wt.bloom.data) return fail(JFGPU_E_INVALID, "jfkt_p1_wide: two-word keys with the partitioned geometry, no filter");
+  if(b1 > 10 || b1 > t->g.lsize_l || !grid || grid > 64) return fail(JFGPU_E_INVALID, "jfkt_p1_wide: 0 <= b1 <= 10, 1 <= grid <= 64");
+  if(lo < 0 || hi < lo || (uint64_t)hi > n_bases) return fail(JFGPU_E_INVALID, "jfkt_p1_wide: [lo, hi) outside the buffer");
+  if(cap % kGran || !cap) return fail(JFGPU_E_INVALID, "jfkt_p1_wide: regions are whole reservations");
+  const uint32_t tbits = t->g.lsize_l - t->g.tile_bits;
+  if(b1 > tbits && (uint64_t)cap < (uint64_t)(hi - lo) + (uint64_t)grid * kGran) return fail(JFGPU_E_INVALID, "jfkt_p1_wide: buckets smaller than a tile need regions that cannot overflow");
+  PartGeom P;
+  P.b1 = b1; P.b2 = tbits > b1 ? tbits - b1 : 0;
+  P.rest_shift = t->g.lsize_l - b1; P.item_bits = P.rest_shift + t->g.rem_bits;
+  if(P.item_bits > 128) return fail(JFGPU_E_INVALID, "jfkt_p1_wide: the geometry's items do not fit 128 bits");
+  const uint32_t nb = 1u << b1;
+  DevBufs D;
+  uint8_t* d_bases; uint64_t* d_out; unsigned int* d_gcur; unsigned long long* d_tot;
+  KT_TRY(D.put(&d_bases, bases, (size_t)n_bases, 32));
+  KT_TRY(D.put(&d_out, out, ((size_t)nb + 1) * cap * 2));
+  KT_TRY(D.get(&d_gcur, 2 * (size_t)nb, 0));
+  KT_TRY(D.get(&d_tot, nb, 0));
+  uint64_t c0[CTR_COUNT], c1[CTR_COUNT];
+  KT_TRY(read_counters(t, c0));
+  const size_t wlds = (size_t)kWideChunk * 18 + (size_t)t->g.nbytes * 2048;         // (part_ingest)
+  const bool xs = t->g.hash_xs != 0;
+  std::string name;
+#define KT_PW(RT, X) do { hipLaunchKernelGGL((p1_wide_granule_kernel<RT, false, X>), dim3(grid), dim3(kPBlock), wlds, t->stream, t->wt, P, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, (u128*)d_out); \
+                          name = "p1_wide_granule_kernel<" #RT ",false," #X ">"; } while(0)
+  if(xs) { if(t->returning) KT_PW(true, true); else KT_PW(false, true); }
+  else { if(t->returning) KT_PW(true, false); else KT_PW(false, false); }
+#undef KT_PW
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  t->pristine = false;
+  KT_TRY(read_counters(t, c1));
+  HIP_TRY(hipMemcpy(out, d_out, ((size_t)nb + 1) * cap * 16, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(gcur, d_gcur, 2 * (size_t)nb * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tot, d_tot, (size_t)nb * 8, hipMemcpyDeviceToHost));
+  if(ctr) { ctr[0] = c1[CTR_MERS] - c0[CTR_MERS]; ctr[1] = c1[CTR_DIRECT] - c0[CTR_DIRECT]; }
+  say(launched, launched_len, name);
+  return JFGPU_OK;
+}
+
+// ---- Tw alone ---------------------------------------------------------------------------------------------------------
+// kernel 0: tile_insert_wide_kernel<table's RETURNING> over n_units tiles from tile0, 1 to 3 segments;
+// kernel 1: tile_insert_wide_pipe_kernel<table's RETURNING>, exactly one segment;
+// kernel 2: items_direct_wide_kernel<table's RETURNING> over one granule batch of the table's own P1 geometry: segment 0
+//           holds 2^b1 regions of `cap` items and their (begin, end) pairs.
+// Unit u of segment s is items[off[u << sh] .. off[(u << sh) + 1]) as in jfkt_tile; items are pairs of words, low first.
+int jfkt_tile_wide(jfgpu_table* t, int kernel, uint32_t n_seg, const void* const* seg_items, const uint64_t* n_items, const uint64_t* const* seg_off,
+                   const uint64_t* n_off, const uint32_t* sh, uint64_t tile0, uint32_t n_units, uint32_t grid, uint64_t cap, char* launched, size_t launched_len) {
+  int rc = use(t); if(rc) return rc;
+  if(!t->wide || !t->item128 || t->g.tile_bits != kMaxTileBits || !t->wt.dirty) return fail(JFGPU_E_INVALID, "jfkt_tile_wide: two-word keys, full-size tiles");
+  if(kernel < 0 || kernel > 2 || !n_seg || n_seg > 3 || (kernel != 0 && n_seg != 1) || !grid) return fail(JFGPU_E_INVALID, "jfkt_tile_wide: bad kernel, segment count or grid");
+  if(kernel == 2) {
+    const uint64_t nb = 1ull << t->pg.b1;
+    if(!cap || sh[0] != 1 || n_items[0] != nb * cap || n_off[0] < 2 * nb) return fail(JFGPU_E_INVALID, "jfkt_tile_wide: a granule batch is 2^b1 regions of cap items");
+    for(uint64_t b = 0; b < nb; ++b) if(seg_off[0][2 * b + 1] > (b + 1) * cap) return fail(JFGPU_E_INVALID, "jfkt_tile_wide: a region ends beyond itself");
+  } else {
+    if(!n_units || tile0 + n_units > n_tiles_of(t)) return fail(JFGPU_E_INVALID, "jfkt_tile_wide: units beyond the table");
+    for(uint32_t s = 0; s < n_seg; ++s) {
+      if(sh[s] > 1 || n_off[s] < (((uint64_t)n_units - 1) << sh[s]) + 2) return fail(JFGPU_E_INVALID, "jfkt_tile_wide: offsets do not cover the units");
+      for(uint32_t u = 0; u < n_units; ++u) {
+        const uint64_t a = seg_off[s][(size_t)u << sh[s]], b = seg_off[s][((size_t)u << sh[s]) + 1];
+        if(a > b || b > n_items[s]) return fail(JFGPU_E_INVALID, "jfkt_tile_wide: a unit's range lies outside the items");
+      }
+    }
+  }
+  DevBufs D;
+  SegList S; memset(&S, 0, sizeof S);
+  S.n = n_seg;
+  for(uint32_t s = 0; s < n_seg; ++s) {
+    uint64_t *di, *doff;
+    KT_TRY(D.put(&di, (const uint64_t*)seg_items[s], (size_t)n_items[s] * 2, 2));
+    KT_TRY(D.put(&doff, seg_off[s], (size_t)n_off[s]));
+    S.items[s] = di; S.off[s] = doff; S.sh[s] = sh[s];
+  }
+  const size_t tile_lds = (size_t)16 << t->g.tile_bits;                             // (part_flush_t)
+  const bool rt = t->returning;
+  const char* r = rt ? "true" : "false";
+  std::string name;
+  if(kernel == 0) {
+    const dim3 g(std::min(grid, n_units)), block(kPBlock);
+    if(rt) hipLaunchKernelGGL(tile_insert_wide_kernel<true>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units);
+    else   hipLaunchKernelGGL(tile_insert_wide_kernel<false>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units);
+    name = std::string("tile_insert_wide_kernel<") + r + ">";
+  } else if(kernel == 1) {
+    const dim3 g(std::min(grid, n_units)), block(kPBlock);
+    if(rt) hipLaunchKernelGGL(tile_insert_wide_pipe_kernel<true>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units);
+    else   hipLaunchKernelGGL(tile_insert_wide_pipe_kernel<false>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units);
+    name = std::string("tile_insert_wide_pipe_kernel<") + r + ">";
+  } else {
+    const dim3 g(grid), block(kBlock);
+    if(rt) hipLaunchKernelGGL(items_direct_wide_kernel<true>, g, block, 0, t->stream, t->wt, t->pg, (const u128*)S.items[0], S.off[0], cap);
+    else   hipLaunchKernelGGL(items_direct_wide_kernel<false>, g, block, 0, t->stream, t->wt, t->pg, (const u128*)S.items[0], S.off[0], cap);
+    name = std::string("items_direct_wide_kernel<") + r + ">";
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  t->pristine = false;
   say(launched, launched_len, name);
   return JFGPU_OK;
 }

@@ -1,6 +1,7 @@
 """Python side of tests/kernels/stage_harness.hip: the library that is the engine plus entry points launching ONE stage
-of the partitioned insert path (P1, P2, T) with the caller's arguments.  Test infrastructure, used by
-tests/test_gpu_stage_*.py only.
+of the partitioned insert path (P1, P2, T; the sort-based P2 and the two-word path's P1w and Tw) with the caller's
+arguments.  Test infrastructure, used by tests/test_gpu_stage_*.py only.  Items of 16 bytes are Python ints here and pairs
+of 64-bit words, low word first, at the C boundary (to_words / from_words).
 
 The library is a superset of the engine, so it gets a ctypes binding of its own: a private copy of jellyfish_amd.capi bound
 to it (`Harness.capi`).  A table made there is what the stage launches take and what lookup / dump_records / stats /
@@ -22,7 +23,9 @@ HOLE = 0xFFFFFFFF
 CONSTS = ["kPBlock", "kP2StragPerBlock", "kStragPerBlock", "kGran", "kRingSlots", "kRingUnit", "kTileBlock", "kTileRound4",
           "kTileRound8", "kMaxTileBits", "kBucketBits", "kPTilePos", "kG2Blocks", "kTileQueueBytes"]
 GEOM = ["lsize_l", "tile_bits", "rem_bits", "tag_bits", "cnt_bits", "slot32", "hash_xs", "nbytes", "returning", "part_ok", "b1", "b2",
-        "rest_shift", "item32", "lsize_g", "canonical"]
+        "rest_shift", "item32", "lsize_g", "canonical", "tag_full", "key_bits"]
+HOLE128 = (1 << 128) - 1
+M64 = (1 << 64) - 1
 
 _SIGNATURES = {
     "jfkt_const": (C.c_uint64, [C.c_int]),
@@ -33,7 +36,33 @@ _SIGNATURES = {
                             C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]),
     "jfkt_p1": (C.c_int, [_P, C.c_int, C.c_uint32, _P, C.c_uint64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P,
                           C.c_uint64, _P, _P, C.c_char_p, C.c_size_t]),
+    "jfkt_p2_sort": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
+                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_uint32, _P, _P,
+                               _P, C.c_uint64, _P, _P, C.c_char_p, C.c_size_t]),
+    "jfkt_p1_wide": (C.c_int, [_P, C.c_uint32, _P, C.c_uint64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "jfkt_tile_wide": (C.c_int, [_P, C.c_int, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_size_t]),
 }
+
+
+def to_words(items, item_bytes):
+    """items (Python ints or an array) as the array that crosses the C boundary: uint32 / uint64, or (n, 2) uint64 low word first"""
+    if item_bytes == 16 and isinstance(items, np.ndarray) and items.ndim == 2:
+        return np.ascontiguousarray(items, dtype=np.uint64)
+    if item_bytes == 16:
+        a = np.empty((len(items), 2), dtype=np.uint64)
+        if len(items):
+            a[:, 0] = [int(x) & M64 for x in items]
+            a[:, 1] = [int(x) >> 64 for x in items]
+        return a
+    return np.ascontiguousarray(items, dtype=np.uint32 if item_bytes == 4 else np.uint64)
+
+
+def from_words(a, item_bytes):
+    """the inverse: a list of Python ints"""
+    if item_bytes == 16:
+        a = np.asarray(a, dtype=np.uint64).reshape(-1, 2)
+        return [(int(h) << 64) | int(l) for l, h in zip(a[:, 0].tolist(), a[:, 1].tolist())]
+    return np.asarray(a).tolist()
 
 
 class Harness:
@@ -105,6 +134,69 @@ class Harness:
                                           ctr.ctypes.data, name, len(name)))
         return dict(out=out.reshape(nb + 1, cap), gcur=gcur[:nb], gshort=gcur[nb:], tot=tot, strag=strag, strag_n=strag_n,
                     rec=rec[:min(n_rec.value, rec_cap)], n_rec=n_rec.value, mers=int(ctr[0]), ctr_direct=int(ctr[1]), launched=name.value.decode())
+
+    def _segs(self, segs, item_bytes):
+        keep = [(to_words(i, item_bytes), np.ascontiguousarray(o, dtype=np.uint64), int(s)) for i, o, s in segs]
+        n = len(keep)
+        items = (_P * n)(*[i.ctypes.data for i, _, _ in keep])
+        offs = (_P * n)(*[o.ctypes.data for _, o, _ in keep])
+        n_items = np.array([len(i) for i, _, _ in keep], dtype=np.uint64)
+        n_off = np.array([len(o) for _, o, _ in keep], dtype=np.uint64)
+        sh = np.array([s for _, _, s in keep], dtype=np.uint32)
+        return keep, n, items, offs, n_items, n_off, sh
+
+    def p2_sort(self, table, scheme, item_bytes, b2e, tag_bits, segs, bucket0, nbk, n_dest, sentinel, cap=0, pair=False, base=None, n_out=0,
+                finish_range=None, rec_cap=1 << 17):
+        """segs: [(items, off uint64[], sh)], items Python ints (16 bytes) or arrays.  scheme 0: n_dest regions of cap items, filled
+        with `sentinel` before the launch; finish_range (d0, nd): granule_finish_range_kernel over it instead of
+        granule_finish_kernel.  scheme 1: base[q] where bucket q starts in an output of n_out items.  Items come back as arrays
+        (4, 8 bytes) or (n, 2) word arrays (16 bytes: from_words)."""
+        keep, n, items, offs, n_items, n_off, sh = self._segs(segs, item_bytes)
+        if scheme == 0:
+            n_out = n_dest * cap
+        if item_bytes == 16:
+            out = np.empty((n_out, 2), dtype=np.uint64)
+            out[:, 0], out[:, 1] = sentinel & M64, sentinel >> 64
+        else:
+            out = np.full(n_out, sentinel, dtype=np.uint32 if item_bytes == 4 else np.uint64)
+        gcur = np.zeros(2 * n_dest, dtype=np.uint32)
+        off2 = np.full(2 * n_dest, M64, dtype=np.uint64)
+        goff = np.full(n_dest + 1, M64, dtype=np.uint64)
+        base_a = np.ascontiguousarray(base if base is not None else [], dtype=np.uint64)
+        rec = np.zeros((rec_cap, 3), dtype=np.uint64)
+        n_rec, ctr = C.c_uint64(0), C.c_uint64(0)
+        fr = finish_range or (0, 0)
+        name = C.create_string_buffer(256)
+        self.capi._check(self.lib.jfkt_p2_sort(table._h, scheme, item_bytes, int(pair), b2e, tag_bits, n, items, n_items.ctypes.data, offs, n_off.ctypes.data,
+                                               sh.ctypes.data, cap, bucket0, nbk, n_dest, out.ctypes.data, n_out, gcur.ctypes.data, off2.ctypes.data,
+                                               fr[0], fr[1], base_a.ctypes.data if len(base_a) else None, goff.ctypes.data,
+                                               rec.ctypes.data, rec_cap, C.byref(n_rec), C.byref(ctr), name, len(name)))
+        return dict(out=out, gcur=gcur[:n_dest], gshort=gcur[n_dest:], off2=off2.reshape(n_dest, 2), goff=goff, rec=rec[:min(n_rec.value, rec_cap)],
+                    n_rec=n_rec.value, ctr_direct=ctr.value, launched=name.value.decode())
+
+    def p1_wide(self, table, b1, bases, lo, hi, cap, grid, sentinel):
+        """p1_wide_granule_kernel over bases[lo, hi); out: (2^b1 + 1, cap, 2) words, the last region a guard"""
+        buf = np.frombuffer(bytes(bases), dtype=np.uint8)
+        nb = 1 << b1
+        out = np.empty(((nb + 1) * cap, 2), dtype=np.uint64)
+        out[:, 0], out[:, 1] = sentinel & M64, sentinel >> 64
+        gcur = np.zeros(2 * nb, dtype=np.uint32)
+        tot = np.zeros(nb, dtype=np.uint64)
+        ctr = np.zeros(2, dtype=np.uint64)
+        name = C.create_string_buffer(256)
+        self.capi._check(self.lib.jfkt_p1_wide(table._h, b1, buf.ctypes.data, len(buf), lo, hi, cap, grid, out.ctypes.data, gcur.ctypes.data,
+                                               tot.ctypes.data, ctr.ctypes.data, name, len(name)))
+        return dict(out=out.reshape(nb + 1, cap, 2), gcur=gcur[:nb], gshort=gcur[nb:], tot=tot, mers=int(ctr[0]), ctr_direct=int(ctr[1]),
+                    launched=name.value.decode())
+
+    def tile_wide(self, table, kernel, segs, tile0=0, n_units=0, grid=1, cap=0):
+        """kernel: 'plain' (tile_insert_wide_kernel), 'pipe' (tile_insert_wide_pipe_kernel) or 'direct' (items_direct_wide_kernel:
+        one granule batch of 2^b1 regions of cap items); segs: [(items as Python ints, off, sh)]"""
+        keep, n, items, offs, n_items, n_off, sh = self._segs(segs, 16)
+        name = C.create_string_buffer(256)
+        self.capi._check(self.lib.jfkt_tile_wide(table._h, {"plain": 0, "pipe": 1, "direct": 2}[kernel], n, items, n_items.ctypes.data, offs,
+                                                 n_off.ctypes.data, sh.ctypes.data, tile0, n_units, grid, cap, name, len(name)))
+        return name.value.decode()
 
 
 _harness = None

@@ -375,8 +375,9 @@ __global__ __launch_bounds__(kPBlock) void bloom_segment_kernel(DevBloom B, SegL
   }
 }
 
-// Too few updates to be worth streaming the filter: apply pending items with global CAS.  Same item layouts as
-// items_direct_kernel (cap == 0: packed, bucket by binary search; cap > 0: granule regions with holes).
+// Too few updates to be worth streaming the filter: apply pending items with global CAS.  One granule batch: 2^b1 regions
+// of cap > 0 entries, region b filled up to off[2 b + 1], all-ones entries are holes.  (There is no packed form: P1b only
+// ever leaves granule batches.)
 __global__ __launch_bounds__(kBlock) void bloom_items_direct_kernel(DevBloom B, BloomPart BP, const uint32_t* __restrict__ items,
                                                                     const uint64_t* __restrict__ off, uint64_t cap) {
   const uint32_t nb = 1u << BP.b1;

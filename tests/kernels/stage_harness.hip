@@ -4,6 +4,8 @@
 // Likewise the sort-based P2 at 4-, 8- and 16-byte items (jfkt_p2_sort: p2_granule_kernel + granule_finish[_range]_kernel;
 // p2_kernel + scan_matrix_kernel + p2_scatter_sorted_kernel) and the two-word path's own stages (jfkt_p1_wide:
 // p1_wide_granule_kernel; jfkt_tile_wide: tile_insert_wide_kernel, tile_insert_wide_pipe_kernel, items_direct_wide_kernel).
+// And the partitioned Bloom insert (jfkt_bloom_p1: the three P1b families; jfkt_bloom_seg: bloom_segment_kernel;
+// jfkt_bloom_items_direct; jfkt_bloom_p2: the P2 kernels with the Bloom functors), on a Bloom counter of this library.
 //
 // The engine is one translation unit, so including it here gives the harness the anonymous namespace, jfgpu_table, the
 // descriptors and the kernels.  The library built from this file is a superset of the engine: a table made by ITS
@@ -532,6 +534,284 @@ int jfkt_tile_wide(jfgpu_table* t, int kernel, uint32_t n_seg, const void* const
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(t->stream));
   t->pristine = false;
+  say(launched, launched_len, name);
+  return JFGPU_OK;
+}
+
+}  // extern "C"
+
+// ---- the partitioned Bloom insert (kernels_bloom_part.hip.hpp) ----------------------------------------------------------
+// Every entry point takes a counter made by THIS library's jfgpu_bc_create: kind 0, part_ok (whole segments are allocated,
+// so Tb may load and store them), left in mode 1 so that the engine itself launches nothing partitioned, nothing pending.
+// The BloomPart is the caller's: n_seg must be the filter's own and 2^(b1 + b2) buckets x sub-buckets must cover it.  The
+// filter's bytes go in and come out through jfgpu_bc_load / jfgpu_bc_read.  The functors are the product's own (BloomDirect,
+// BloomRingDirect, BloomP1RingDirect): what they do IS the output here, a side effect on the filter.
+namespace {
+
+int kt_bloom_attrs() {                                          // (the engine's own values: bloom_create)
+  static bool done = false;
+  if(done) return JFGPU_OK;
+  const int pl = (int)((size_t)kBloomChunk * 6 + (size_t)2 * 8 * 2048), pl2 = (int)((size_t)kPBlock * 5 * 6 + (size_t)8 * 512);
+  const int plr = (int)((size_t)512 * kBloomRingBytes + kBloomRingBytes + (size_t)8 * 512), rl = (int)(kGranMaxB * 128 + 128);
+#define KT_A(F, N) HIP_TRY(hipFuncSetAttribute((const void*)F, hipFuncAttributeMaxDynamicSharedMemorySize, N))
+  KT_A(p1_bloom_granule_kernel<0>, pl); KT_A(p1_bloom_granule_kernel<6>, pl); KT_A(p1_bloom_granule_kernel<8>, pl);
+  KT_A(p1_bloom_granule2_kernel<0>, pl2); KT_A(p1_bloom_granule2_kernel<6>, pl2); KT_A(p1_bloom_granule2_kernel<8>, pl2);
+  KT_A((p1_bloom_ring_kernel<0, 10>), plr); KT_A((p1_bloom_ring_kernel<6, 10>), plr); KT_A((p1_bloom_ring_kernel<8, 10>), plr);
+  KT_A((p1_bloom_ring_kernel<0, 5>), plr); KT_A((p1_bloom_ring_kernel<8, 5>), plr);
+  KT_A(bloom_segment_kernel, 1 << kBloomSegBits);
+  KT_A((p2_granule_kernel<uint32_t, BloomDirect, kP2PairPer>), kPBlock * kP2PairPer * 4);
+  KT_A(p2_ring_kernel<BloomRingDirect>, rl);
+  KT_A((p2_ring_roles_kernel<uint32_t, 2, BloomRingDirect, 3>), rl);
+#undef KT_A
+  done = true;
+  return JFGPU_OK;
+}
+
+int kt_bloom_use(jfgpu_bloom* b, const BloomPart& BP, const char* who) {
+  int rc = use_b(b); if(rc) return rc;
+  if(b->kind != 0 || !b->part_ok || b->mode != 1 || !b->pending.empty() || b->wide || b->nword)
+    return fail(JFGPU_E_INVALID, std::string(who) + ": a Bloom counter of one-word keys with whole segments, in mode 1, nothing pending");
+  if(BP.n_seg != b->bp.n_seg || BP.b1 > 10 || BP.b2 > 11 || ((uint64_t)1 << (BP.b1 + BP.b2)) < BP.n_seg)
+    return fail(JFGPU_E_INVALID, std::string(who) + ": n_seg is the filter's own, b1 <= 10, b2 <= 11, n_seg <= 2^(b1 + b2)");
+  return kt_bloom_attrs();
+}
+
+// a cell update the kernels may be given: digit below five, (with `bucket`) a segment of the filter
+bool kt_bloom_item_ok(const BloomPart& BP, uint32_t bucket, uint32_t item) {
+  const uint64_t sub = item >> kBloomItemLow;
+  return (item & 7u) <= 4u && sub < ((uint64_t)1 << BP.b2) && (((uint64_t)bucket << BP.b2) | sub) < BP.n_seg;
+}
+
+}  // namespace
+
+extern "C" {
+
+// 0 kBloomSegBits  1 kBloomItemLow  2 kBloomPer  3 kBloomRingBytes  4 kP2PairPer  5 kGranMaxB
+uint64_t jfkt_bloom_const(int which) {
+  switch(which) {
+    case 0: return kBloomSegBits;
+    case 1: return kBloomItemLow;
+    case 2: return kBloomPer;
+    case 3: return kBloomRingBytes;
+    case 4: return kP2PairPer;
+    case 5: return kGranMaxB;
+  }
+  return 0;
+}
+
+// ---- P1b alone --------------------------------------------------------------------------------------------------------
+// family 0: p1_bloom_granule_kernel<NB> (per = 10); 1: p1_bloom_granule2_kernel<NB> (per = 5); 2: p1_bloom_ring_kernel<NB, per>
+// with (NB, per) in {0, 6, 8} x {10} and {0, 8} x {5}, at most 512 buckets -- the instantiations bloom_ingest launches, with
+// its dynamic-LDS sizes -- over bases[lo, hi) (a contract buffer, its base 16-byte aligned), `grid` workgroups.
+// run_stragglers (ring family): p1_stragglers_kernel<uint32_t, BloomP1RingDirect> over the lists afterwards, as bloom_ingest does.
+// out: (2^b1 + 1) * cap items in and out (the last region is a guard); gcur: 2 * 2^b1 words out (cursors, overflow notes);
+// tot: 2^b1; strag: grid * kStragPerBlock entries and strag_n: grid, as the P1b kernel left them (ring family; else zero);
+// mers: what the launch added to the counter's k-mer count.
+int jfkt_bloom_p1(jfgpu_bloom* b, int family, int nbt, int per, uint32_t b1, uint32_t b2, uint32_t n_seg, const uint8_t* bases, uint64_t n_bases,
+                  int64_t lo, int64_t hi, uint32_t cap, uint32_t grid, int run_stragglers, uint32_t* out, uint32_t* gcur, uint64_t* tot,
+                  uint64_t* strag, uint32_t* strag_n, uint64_t* mers, char* launched, size_t launched_len) {
+  const BloomPart BP{b1, b2, n_seg, 0};
+  int rc = kt_bloom_use(b, BP, "jfkt_bloom_p1"); if(rc) return rc;
+  if(family < 0 || family > 2 || !grid || grid > 64) return fail(JFGPU_E_INVALID, "jfkt_bloom_p1: family 0, 1 or 2, 1 <= grid <= 64");
+  if(lo < 0 || hi < lo || (uint64_t)hi > n_bases) return fail(JFGPU_E_INVALID, "jfkt_bloom_p1: [lo, hi) outside the buffer");
+  if(cap % kGran || !cap) return fail(JFGPU_E_INVALID, "jfkt_bloom_p1: regions are whole reservations");
+  if((nbt != 0 && nbt != 6 && nbt != 8) || (nbt && (uint32_t)nbt != b->g.nbytes) || b->g.nbytes > 8) return fail(JFGPU_E_INVALID, "jfkt_bloom_p1: NB is 0 or the key's bytes (6 or 8)");
+  if((family == 0 && per != kBloomPer) || (family == 1 && per != 5)) return fail(JFGPU_E_INVALID, "jfkt_bloom_p1: the sort-based kernels take 10 (byte tables) and 5 (nibble tables) cells a round");
+  if(family == 2 && !((per == 10) || (per == 5 && nbt != 6))) return fail(JFGPU_E_INVALID, "jfkt_bloom_p1: the host launches rings with (NB, PER) in {0, 6, 8} x {10} and {0, 8} x {5}");
+  if(family == 2 && b1 > 9) return fail(JFGPU_E_INVALID, "jfkt_bloom_p1: the ring kernel takes at most 512 buckets");
+  if(run_stragglers && family != 2) return fail(JFGPU_E_INVALID, "jfkt_bloom_p1: the sort-based kernels leave no lists");
+  const uint32_t nb = 1u << b1;
+  DevBufs D;
+  uint8_t* d_bases; uint32_t *d_out, *d_strag_n; unsigned int* d_gcur; unsigned long long* d_tot; uint64_t* d_strag;
+  KT_TRY(D.put(&d_bases, bases, (size_t)n_bases, 32));
+  KT_TRY(D.put(&d_out, out, ((size_t)nb + 1) * cap));
+  KT_TRY(D.get(&d_gcur, 2 * (size_t)nb, 0));
+  KT_TRY(D.get(&d_tot, nb, 0));
+  KT_TRY(D.get(&d_strag, (size_t)grid * kStragPerBlock, 0));
+  KT_TRY(D.get(&d_strag_n, grid, 0));
+  unsigned long long m0 = 0, m1 = 0;
+  HIP_TRY(hipMemcpy(&m0, b->d_mers, 8, hipMemcpyDeviceToHost));
+  const DevBloom B = b->view();
+  const size_t nby = b->g.nbytes;
+  const size_t lds0 = (size_t)kBloomChunk * 6 + (size_t)2 * nby * 2048, lds1 = (size_t)kPBlock * 5 * 6 + nby * 512;      // (bloom_ingest)
+  const size_t lds2 = (size_t)nb * kBloomRingBytes + kBloomRingBytes + nby * 512;
+  const BloomP1RingDirect rd{B.data, b2};
+  std::string name;
+#define KT_PB(N) do { hipLaunchKernelGGL(p1_bloom_granule_kernel<N>, dim3(grid), dim3(kPBlock), lds0, b->stream, B, BP, b->g, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, b->d_mers); \
+                      name = "p1_bloom_granule_kernel<" #N ">"; } while(0)
+#define KT_PB2(N) do { hipLaunchKernelGGL(p1_bloom_granule2_kernel<N>, dim3(grid), dim3(kPBlock), lds1, b->stream, B, BP, b->g, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, b->d_mers); \
+                       name = "p1_bloom_granule2_kernel<" #N ">"; } while(0)
+#define KT_PBR(N, PER) do { hipLaunchKernelGGL((p1_bloom_ring_kernel<N, PER>), dim3(grid), dim3(kPBlock), lds2, b->stream, B, BP, b->g, rd, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, b->d_mers, d_strag, d_strag_n); \
+                            name = "p1_bloom_ring_kernel<" #N "," #PER ">"; } while(0)
+  if(family == 0) { if(nbt == 8) KT_PB(8); else if(nbt == 6) KT_PB(6); else KT_PB(0); }
+  else if(family == 1) { if(nbt == 8) KT_PB2(8); else if(nbt == 6) KT_PB2(6); else KT_PB2(0); }
+  else if(per == 10) { if(nbt == 8) KT_PBR(8, 10); else if(nbt == 6) KT_PBR(6, 10); else KT_PBR(0, 10); }
+  else { if(nbt == 8) KT_PBR(8, 5); else KT_PBR(0, 5); }
+#undef KT_PBR
+#undef KT_PB2
+#undef KT_PB
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpy(strag, d_strag, (size_t)grid * kStragPerBlock * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(strag_n, d_strag_n, (size_t)grid * 4, hipMemcpyDeviceToHost));
+  if(run_stragglers) {
+    hipLaunchKernelGGL((p1_stragglers_kernel<uint32_t, BloomP1RingDirect>), dim3(b->n_cu), dim3(256), 0, b->stream, rd, (unsigned long long*)nullptr, (const uint64_t*)d_strag,
+                       (const uint32_t*)d_strag_n, grid, cap, d_gcur, d_tot, d_out);
+    name += "+p1_stragglers_kernel<uint32_t,BloomP1RingDirect>";
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(b->stream));
+  }
+  HIP_TRY(hipMemcpy(&m1, b->d_mers, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, d_out, ((size_t)nb + 1) * cap * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(gcur, d_gcur, 2 * (size_t)nb * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tot, d_tot, (size_t)nb * 8, hipMemcpyDeviceToHost));
+  if(mers) *mers = m1 - m0;
+  say(launched, launched_len, name);
+  return JFGPU_OK;
+}
+
+// ---- Tb alone ---------------------------------------------------------------------------------------------------------
+// bloom_segment_kernel over segments [seg0, seg0 + n_seg) of the filter, `grid` workgroups; one to three item arrays: the items
+// of segment seg0 + t in array s are items[off[t << sh] .. off[(t << sh) + 1]); sh = 1: all-ones entries are holes.
+int jfkt_bloom_seg(jfgpu_bloom* b, uint32_t n_arr, const uint32_t* const* seg_items, const uint64_t* n_items, const uint64_t* const* seg_off,
+                   const uint64_t* n_off, const uint32_t* sh, uint32_t n_seg, uint32_t seg0, uint32_t grid, char* launched, size_t launched_len) {
+  int rc = kt_bloom_use(b, b ? b->bp : BloomPart{}, "jfkt_bloom_seg"); if(rc) return rc;
+  if(!n_arr || n_arr > 3 || !n_seg || !grid || grid > 1024) return fail(JFGPU_E_INVALID, "jfkt_bloom_seg: one to three arrays, 1 <= grid <= 1024");
+  if((uint64_t)seg0 + n_seg > b->bp.n_seg) return fail(JFGPU_E_INVALID, "jfkt_bloom_seg: segments beyond the filter");
+  for(uint32_t s = 0; s < n_arr; ++s) {
+    if(sh[s] > 1 || n_off[s] < (((uint64_t)n_seg - 1) << sh[s]) + 2) return fail(JFGPU_E_INVALID, "jfkt_bloom_seg: offsets do not cover the segments");
+    for(uint32_t t = 0; t < n_seg; ++t) {
+      const uint64_t a = seg_off[s][(size_t)t << sh[s]], e = seg_off[s][((size_t)t << sh[s]) + 1];
+      if(a > e || e > n_items[s]) return fail(JFGPU_E_INVALID, "jfkt_bloom_seg: a segment's range lies outside the items");
+      for(uint64_t i = a; i < e; ++i) {
+        const uint32_t x = seg_items[s][i];
+        if(!(sh[s] && x == 0xFFFFFFFFu) && (x & 7u) > 4u) return fail(JFGPU_E_INVALID, "jfkt_bloom_seg: an item's digit is five or more (a packed array holds no all-ones entry)");
+      }
+    }
+  }
+  DevBufs D;
+  SegList S; memset(&S, 0, sizeof S);
+  S.n = n_arr;
+  for(uint32_t s = 0; s < n_arr; ++s) {
+    uint32_t* di; uint64_t* doff;
+    KT_TRY(D.put(&di, seg_items[s], (size_t)n_items[s], 4));
+    KT_TRY(D.put(&doff, seg_off[s], (size_t)n_off[s]));
+    S.items[s] = di; S.off[s] = doff; S.sh[s] = sh[s];
+  }
+  hipLaunchKernelGGL(bloom_segment_kernel, dim3(grid), dim3(kPBlock), (size_t)1 << kBloomSegBits, b->stream, b->view(), S, n_seg, seg0);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  say(launched, launched_len, "bloom_segment_kernel");
+  return JFGPU_OK;
+}
+
+// ---- the direct kernel of a small flush ----------------------------------------------------------------------------------
+// bloom_items_direct_kernel over one granule batch: 2^b1 regions of cap entries, off[2 q], off[2 q + 1] the bounds of region q.
+int jfkt_bloom_items_direct(jfgpu_bloom* b, uint32_t b1, uint32_t b2, uint32_t n_seg, const uint32_t* items, uint64_t n_items, const uint64_t* off, uint64_t n_off,
+                            uint64_t cap, uint32_t grid, char* launched, size_t launched_len) {
+  const BloomPart BP{b1, b2, n_seg, 0};
+  int rc = kt_bloom_use(b, BP, "jfkt_bloom_items_direct"); if(rc) return rc;
+  const uint64_t nb = 1ull << b1;
+  if(!cap || n_items != nb * cap || n_off < 2 * nb || !grid || grid > 4096) return fail(JFGPU_E_INVALID, "jfkt_bloom_items_direct: a granule batch is 2^b1 regions of cap items");
+  for(uint64_t q = 0; q < nb; ++q) {
+    if(off[2 * q] != q * cap) return fail(JFGPU_E_INVALID, "jfkt_bloom_items_direct: a region starts at its own place");
+    for(uint64_t v = q * cap; v < (q + 1) * cap && v < off[2 * q + 1]; ++v)
+      if(items[v] != 0xFFFFFFFFu && !kt_bloom_item_ok(BP, (uint32_t)q, items[v])) return fail(JFGPU_E_INVALID, "jfkt_bloom_items_direct: an item names no cell of the filter");
+  }
+  DevBufs D;
+  uint32_t* d_items; uint64_t* d_off;
+  KT_TRY(D.put(&d_items, items, (size_t)n_items, 4));
+  KT_TRY(D.put(&d_off, off, (size_t)n_off));
+  hipLaunchKernelGGL(bloom_items_direct_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), BP, (const uint32_t*)d_items, (const uint64_t*)d_off, cap);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  say(launched, launched_len, "bloom_items_direct_kernel");
+  return JFGPU_OK;
+}
+
+// ---- P2 with the Bloom functors ---------------------------------------------------------------------------------------------
+// kernel 0: p2_granule_kernel<uint32_t, BloomDirect, kP2PairPer> on grid (4, nbk); 1: p2_ring_roles_kernel<uint32_t, 2,
+// BloomRingDirect, 3> (nbk workgroups); 2: p2_ring_kernel<BloomRingDirect> on grid (4, nbk); 1 and 2 (b2 = 10 only, as on the
+// host) are followed by p1_stragglers_kernel<uint32_t, BloomRingDirect>; all by granule_finish_range_kernel over the launched
+// buckets' segments.  tag_bits = kBloomItemLow, arguments as bloom_flush_inner passes them.  Arrays as in jfkt_p2.
+// out: 2^(b1 + b2) * cap2 items in and out; gcur: 2 * 2^(b1 + b2) words out; off2: 2 * 2^(b1 + b2) words in and out;
+// ctr_direct: the functors' counter; strag_n: nbk (kernel 1) or 4 * nbk (kernel 2) list lengths.
+int jfkt_bloom_p2(jfgpu_bloom* b, int kernel, uint32_t b1, uint32_t b2, uint32_t n_seg_f, uint32_t n_arr, const uint32_t* const* seg_items, const uint64_t* n_items,
+                  const uint64_t* const* seg_off, const uint64_t* n_off, const uint32_t* sh, uint32_t cap2, uint32_t bucket0, uint32_t nbk,
+                  uint32_t* out, uint32_t* gcur, uint64_t* off2, uint64_t* ctr_direct, uint32_t* strag_n, char* launched, size_t launched_len) {
+  const BloomPart BP{b1, b2, n_seg_f, 0};
+  int rc = kt_bloom_use(b, BP, "jfkt_bloom_p2"); if(rc) return rc;
+  if(kernel < 0 || kernel > 2 || !n_arr || n_arr > (uint32_t)kMaxSeg || !nbk || !cap2 || cap2 % kGran) return fail(JFGPU_E_INVALID, "jfkt_bloom_p2: bad kernel, array count, bucket count or capacity");
+  if(b2 > 10 || (kernel != 0 && b2 != 10)) return fail(JFGPU_E_INVALID, "jfkt_bloom_p2: at most 1024 segments a bucket; the ring kernels take exactly 1024");
+  if((uint64_t)bucket0 + nbk > (1ull << b1)) return fail(JFGPU_E_INVALID, "jfkt_bloom_p2: launched buckets beyond 2^b1");
+  if(kernel != 0 && (((uint64_t)bucket0 + nbk) << b2) > n_seg_f) return fail(JFGPU_E_INVALID, "jfkt_bloom_p2: the ring kernels take buckets whose segments all exist");
+  for(uint32_t s = 0; s < n_arr; ++s) {
+    const uint64_t need = ((uint64_t)(bucket0 + nbk - 1) << sh[s]) + 2;
+    if(sh[s] > 1 || n_off[s] < need) return fail(JFGPU_E_INVALID, "jfkt_bloom_p2: offsets do not cover the launched buckets");
+    if(kernel == 2 && sh[s] != 1) return fail(JFGPU_E_INVALID, "jfkt_bloom_p2: the shared-ring kernel takes granule arrays only");
+    for(uint32_t j = bucket0; j < bucket0 + nbk; ++j) {
+      const uint64_t a = seg_off[s][(size_t)j << sh[s]], e = seg_off[s][((size_t)j << sh[s]) + 1];
+      if(a > e || e > n_items[s]) return fail(JFGPU_E_INVALID, "jfkt_bloom_p2: a bucket's range lies outside its array");
+      if(kernel != 0 && sh[s] == 1 && (a % 4)) return fail(JFGPU_E_INVALID, "jfkt_bloom_p2: a granule region starts at a multiple of 16 bytes");
+      for(uint64_t i = a; i < e; ++i) {
+        const uint32_t x = seg_items[s][i];
+        if(!(sh[s] && x == 0xFFFFFFFFu) && !kt_bloom_item_ok(BP, j, x)) return fail(JFGPU_E_INVALID, "jfkt_bloom_p2: an item names no cell of the filter");
+      }
+    }
+  }
+  const size_t n_dest = (size_t)1 << (b1 + b2);
+  DevBufs D;
+  SegList S; memset(&S, 0, sizeof S);
+  S.n = n_arr;
+  for(uint32_t s = 0; s < n_arr; ++s) {
+    uint32_t* di; uint64_t* doff;
+    KT_TRY(D.put(&di, seg_items[s], (size_t)n_items[s], 4));
+    KT_TRY(D.put(&doff, seg_off[s], (size_t)n_off[s]));
+    S.items[s] = di; S.off[s] = doff; S.sh[s] = sh[s];
+  }
+  const uint32_t n_lists = kernel == 1 ? nbk : kG2Blocks * nbk;
+  uint32_t *d_out, *d_strag_n; unsigned int* d_gcur; uint64_t *d_strag, *d_off2; unsigned long long* d_ctr;
+  KT_TRY(D.put(&d_out, out, n_dest * cap2));
+  KT_TRY(D.get(&d_gcur, 2 * n_dest, 0));
+  KT_TRY(D.put(&d_off2, off2, 2 * n_dest));
+  KT_TRY(D.get(&d_strag, (size_t)n_lists * kP2StragPerBlock, 0));
+  KT_TRY(D.get(&d_strag_n, n_lists, 0));
+  KT_TRY(D.get(&d_ctr, 1, 0));
+  const DevBloom B = b->view();
+  const BloomDirect DD{B, BP, d_ctr};
+  const BloomRingDirect RD{B.data};
+  const dim3 block(kPBlock);
+  const size_t rl = ((size_t)1 << b2) * 128 + 128;
+  std::string name;
+  if(kernel == 0) {
+    hipLaunchKernelGGL((p2_granule_kernel<uint32_t, BloomDirect, kP2PairPer>), dim3(kG2Blocks, nbk), block, (size_t)kPBlock * kP2PairPer * sizeof(uint32_t), b->stream,
+                       DD, b2, kBloomItemLow, S, cap2, d_gcur, d_gcur + n_dest, d_out, bucket0);
+    name = "p2_granule_kernel<uint32_t,BloomDirect,kP2PairPer>";
+  } else {
+    if(kernel == 1) {
+      hipLaunchKernelGGL((p2_ring_roles_kernel<uint32_t, 2, BloomRingDirect, 3>), dim3(nbk), block, rl, b->stream, RD, b2, kBloomItemLow, S, cap2, d_gcur,
+                         d_out, bucket0, d_strag, d_strag_n, d_ctr);
+      name = "p2_ring_roles_kernel<uint32_t,2,BloomRingDirect,3>";
+    } else {
+      hipLaunchKernelGGL((p2_ring_kernel<BloomRingDirect>), dim3(kG2Blocks, nbk), block, rl, b->stream, RD, b2, kBloomItemLow, S, cap2, d_gcur, d_gcur + n_dest,
+                         d_out, bucket0, (unsigned long long*)nullptr, d_strag, d_strag_n, d_ctr);
+      name = "p2_ring_kernel<BloomRingDirect>";
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((p1_stragglers_kernel<uint32_t, BloomRingDirect>), dim3(b->n_cu), dim3(256), 0, b->stream, RD, d_ctr, (const uint64_t*)d_strag, (const uint32_t*)d_strag_n,
+                       n_lists, cap2, d_gcur, (unsigned long long*)nullptr, d_out, kP2StragPerBlock);
+    name += "+p1_stragglers_kernel<uint32_t,BloomRingDirect>";
+  }
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(granule_finish_range_kernel, dim3(256), dim3(256), 0, b->stream, d_gcur, cap2, (uint32_t)n_dest, d_off2, bucket0 << b2, nbk << b2);
+  name += "+granule_finish_range_kernel";
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpy(out, d_out, n_dest * cap2 * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(gcur, d_gcur, 2 * n_dest * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(off2, d_off2, 2 * n_dest * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ctr_direct, d_ctr, 8, hipMemcpyDeviceToHost));
+  if(strag_n) HIP_TRY(hipMemcpy(strag_n, d_strag_n, (size_t)n_lists * 4, hipMemcpyDeviceToHost));
   say(launched, launched_len, name);
   return JFGPU_OK;
 }

@@ -1,6 +1,6 @@
 """Python side of tests/kernels/stage_harness.hip: the library that is the engine plus entry points launching ONE stage
-of the partitioned insert path (P1, P2, T; the sort-based P2 and the two-word path's P1w and Tw) with the caller's
-arguments.  Test infrastructure, used by tests/test_gpu_stage_*.py only.  Items of 16 bytes are Python ints here and pairs
+of the partitioned insert path (P1, P2, T; the sort-based P2 and the two-word path's P1w and Tw; the partitioned Bloom
+insert's P1b, P2 with the Bloom functors, Tb and its direct kernel) with the caller's arguments.  Test infrastructure, used by tests/test_gpu_stage_*.py only.  Items of 16 bytes are Python ints here and pairs
 of 64-bit words, low word first, at the C boundary (to_words / from_words).
 
 The library is a superset of the engine, so it gets a ctypes binding of its own: a private copy of jellyfish_amd.capi bound
@@ -41,7 +41,15 @@ _SIGNATURES = {
                                _P, C.c_uint64, _P, _P, C.c_char_p, C.c_size_t]),
     "jfkt_p1_wide": (C.c_int, [_P, C.c_uint32, _P, C.c_uint64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "jfkt_tile_wide": (C.c_int, [_P, C.c_int, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_size_t]),
+    "jfkt_bloom_const": (C.c_uint64, [C.c_int]),
+    "jfkt_bloom_p1": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32,
+                                C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "jfkt_bloom_seg": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "jfkt_bloom_items_direct": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "jfkt_bloom_p2": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32,
+                                _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
 }
+BLOOM_CONSTS = ["kBloomSegBits", "kBloomItemLow", "kBloomPer", "kBloomRingBytes", "kP2PairPer", "kGranMaxB"]
 
 
 def to_words(items, item_bytes):
@@ -77,6 +85,7 @@ class Harness:
             fn = getattr(self.lib, name)
             fn.restype, fn.argtypes = res, args
         self.const = {n: int(self.lib.jfkt_const(i)) for i, n in enumerate(CONSTS)}
+        self.const.update({n: int(self.lib.jfkt_bloom_const(i)) for i, n in enumerate(BLOOM_CONSTS)})
 
     def geom(self, table):
         out = np.zeros(len(GEOM), dtype=np.uint64)
@@ -197,6 +206,64 @@ class Harness:
         self.capi._check(self.lib.jfkt_tile_wide(table._h, {"plain": 0, "pipe": 1, "direct": 2}[kernel], n, items, n_items.ctypes.data, offs,
                                                  n_off.ctypes.data, sh.ctypes.data, tile0, n_units, grid, cap, name, len(name)))
         return name.value.decode()
+
+    # ---- the partitioned Bloom insert: a counter made by self.bloom(), part = (b1, b2); the filter's bytes through load() / read() ----
+    def bloom(self, k, m, nh, canonical=True, seed=7):
+        """a Bloom counter of THIS library, in mode 1: the engine launches nothing partitioned by itself"""
+        b = self.capi.Bloom(k, m, nh, canonical=canonical, seed=seed)
+        b.set_mode(1)
+        b.n_seg = (b.nb_bytes + 0xFFFF) >> 16
+        return b
+
+    def bloom_p1(self, bloom, family, nbt, per, part, bases, lo, hi, cap, grid, sentinel, run_stragglers=False):
+        """family: 'granule', 'granule2' or 'ring'; out: (2^b1 + 1, cap), the last region a guard"""
+        buf = np.frombuffer(bytes(bases), dtype=np.uint8)
+        b1, b2 = part
+        nb = 1 << b1
+        out = np.full((nb + 1) * cap, sentinel, dtype=np.uint32)
+        gcur = np.zeros(2 * nb, dtype=np.uint32)
+        tot = np.zeros(nb, dtype=np.uint64)
+        strag = np.zeros((grid, self.const["kStragPerBlock"]), dtype=np.uint64)
+        strag_n = np.zeros(grid, dtype=np.uint32)
+        mers = C.c_uint64(0)
+        name = C.create_string_buffer(256)
+        self.capi._check(self.lib.jfkt_bloom_p1(bloom._h, {"granule": 0, "granule2": 1, "ring": 2}[family], nbt, per, b1, b2, bloom.n_seg, buf.ctypes.data, len(buf),
+                                                lo, hi, cap, grid, int(run_stragglers), out.ctypes.data, gcur.ctypes.data, tot.ctypes.data, strag.ctypes.data,
+                                                strag_n.ctypes.data, C.byref(mers), name, len(name)))
+        return dict(out=out.reshape(nb + 1, cap), gcur=gcur[:nb], gshort=gcur[nb:], tot=tot, strag=strag, strag_n=strag_n, mers=mers.value,
+                    launched=name.value.decode())
+
+    def bloom_seg(self, bloom, segs, n_seg, seg0=0, grid=1):
+        """bloom_segment_kernel; segs: [(items uint32[], off uint64[], sh)], one to three"""
+        keep, n, items, offs, n_items, n_off, sh = self._segs(segs, 4)
+        name = C.create_string_buffer(256)
+        self.capi._check(self.lib.jfkt_bloom_seg(bloom._h, n, items, n_items.ctypes.data, offs, n_off.ctypes.data, sh.ctypes.data, n_seg, seg0, grid, name, len(name)))
+        return name.value.decode()
+
+    def bloom_items_direct(self, bloom, part, items, off, cap, grid=2):
+        items = np.ascontiguousarray(items, dtype=np.uint32)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        name = C.create_string_buffer(256)
+        self.capi._check(self.lib.jfkt_bloom_items_direct(bloom._h, part[0], part[1], bloom.n_seg, items.ctypes.data, len(items), off.ctypes.data, len(off), cap, grid,
+                                                          name, len(name)))
+        return name.value.decode()
+
+    def bloom_p2(self, bloom, kernel, part, segs, cap2, bucket0, nbk, sentinel):
+        """kernel: 'granule', 'roles' or 'shared'; out: (2^(b1 + b2), cap2) filled with `sentinel` before the launch"""
+        keep, n, items, offs, n_items, n_off, sh = self._segs(segs, 4)
+        b1, b2 = part
+        n_dest = 1 << (b1 + b2)
+        out = np.full(n_dest * cap2, sentinel, dtype=np.uint32)
+        gcur = np.zeros(2 * n_dest, dtype=np.uint32)
+        off2 = np.full(2 * n_dest, M64, dtype=np.uint64)
+        ctr = C.c_uint64(0)
+        kern = {"granule": 0, "roles": 1, "shared": 2}[kernel]
+        strag_n = np.zeros((1 if kern == 1 else self.const["kG2Blocks"]) * nbk, dtype=np.uint32)
+        name = C.create_string_buffer(256)
+        self.capi._check(self.lib.jfkt_bloom_p2(bloom._h, kern, b1, b2, bloom.n_seg, n, items, n_items.ctypes.data, offs, n_off.ctypes.data, sh.ctypes.data, cap2,
+                                                bucket0, nbk, out.ctypes.data, gcur.ctypes.data, off2.ctypes.data, C.byref(ctr), strag_n.ctypes.data, name, len(name)))
+        return dict(out=out.reshape(n_dest, cap2), gcur=gcur[:n_dest], gshort=gcur[n_dest:], off2=off2.reshape(n_dest, 2), ctr_direct=ctr.value, strag_n=strag_n,
+                    launched=name.value.decode())
 
 
 _harness = None

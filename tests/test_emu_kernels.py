@@ -31,6 +31,7 @@ SELECTION = [
     "tests/test_gpu_parity.py::test_spill_mode_add_keys_and_tiny_pieces",
     "tests/test_gpu_parity.py::test_add_keys_batch_larger_than_the_table_grows_in_order",
     "tests/test_gpu_bloom.py::test_partitioned_insert_equals_direct_and_oracle",
+    "tests/test_gpu_bloom.py::test_one_buffer_in_pieces_with_a_flush_inside_the_call",
     "tests/test_gpu_wide.py::test_keys_of_three_and_four_words",
     "tests/test_gpu_wide.py::test_wide_partitioned_path_equals_direct_and_oracle[33-65536]",
     "tests/test_gpu_wide.py::test_wide_partitioned_path_equals_direct_and_oracle[40-1048576]",

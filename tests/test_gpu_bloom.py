@@ -521,3 +521,74 @@ def test_partitioned_insert_at_config_3_geometry(gpu, monkeypatch):
         ans = b.keys(keys)
         assert (ans == want).all()
         assert (ans[n1:] == 2).all() and int((ans[:n1] == 1).sum()) > 0.99 * n1
+
+
+# ---- bloom_ingest's own decisions: pieces of one buffer, a flush inside the call, the arena that cannot hold a piece -----------
+ARENA = 64 << 20
+
+
+def arena_geometry(n_seg, nh, arena=ARENA, slack=0.03, gran=64):
+    """bloom_part_init and bloom_ingest restated: (b1, b2), the part of the arena pending pieces may take, the regions' fixed
+    head-room (g1 = two workgroups a CU strand a reservation each, plus two) and the bases of the largest piece that fits"""
+    cus = int(os.environ.get("JFGPU_EMU_CUS", 2)) if os.environ.get("JFGPU_LIB") else 256
+    sb = max(0, (n_seg - 1).bit_length())
+    b1, b2 = (sb, 0) if sb <= 10 else (sb - min(11, (sb + 1) // 2), min(11, (sb + 1) // 2))
+    nb, g1 = 1 << b1, 2 * cus
+    room = arena - arena // 8
+    fixed = nb * (g1 * gran + 2 * gran) * 4 + nb * 48 + 4096
+    fit = int((room - fixed) / (4.0 * (1.0 + slack) * nh)) if room > fixed else 0
+    return b1, b2, room, fixed, fit
+
+
+def test_one_buffer_in_pieces_with_a_flush_inside_the_call(gpu):
+    """An arena of 64 MiB under an 84 MB two-level filter at nh = 40: a piece's regions take 4 x 1.03 x 40 bytes a base, so the
+    56 MiB that pending pieces may use hold at most 356 000 bases.  One insert_ascii of three times what fits is therefore cut
+    into pieces by bloom_ingest -- each re-reads k - 1 characters, each but the first finds the arena taken and flushes in the
+    middle of the call.  Every window is counted once across the overlaps, and the bytes are the direct kernel's."""
+    k, nh, m = 31, 40, 5 * 84_000_000
+    n_seg = (m // 5 + 0xFFFF) >> 16
+    b1, b2, room, fixed, fit = arena_geometry(n_seg, nh)
+    assert b2 > 0 and fixed < room // 2 and fit >= (1 << 16), "the arena holds no piece worth cutting: %r" % ((b1, b2, room, fixed, fit),)
+    rng = np.random.default_rng(64)
+    n = 3 * fit + 1000
+    seq = np.frombuffer(b"ACGTacgtN", dtype=np.uint8)[rng.choice(9, n, p=[0.24, 0.24, 0.24, 0.24, 0.01, 0.01, 0.01, 0.005, 0.005])].tobytes()
+    windows = len(O.extract(seq, k, True))
+    out = {}
+    for mode in (1, 2):
+        with gpu.Bloom(k, m, nh, canonical=True, seed=11) as b:
+            b.set_mode(mode)
+            if mode == 2:
+                b.reserve(ARENA)
+            b.profile_enable(True); b.profile_reset()
+            b.insert_ascii(seq)
+            if mode == 2:
+                p1, seg = b.profile_get(1)[1], b.profile_get(3)[1]
+                assert p1 > 1, "one P1b launch: the buffer was not cut into pieces"
+                assert seg > 1, "%d segment launches before sync(): no flush inside the call" % seg
+            assert b.sync() == windows, "a window counted twice or not at all across the pieces' overlaps"
+            out[mode] = b.read()
+    assert (out[1] == out[2]).all(), "%d bytes differ" % int((out[1] != out[2]).sum())
+
+
+def test_an_arena_smaller_than_the_regions_head_room_takes_the_direct_kernel(gpu):
+    """1024 single-level segments (b1 = 10, b2 = 0): the fixed head-room of 1024 regions -- two workgroups a CU may strand a
+    reservation in each -- is more than the 64 MiB arena, so bloom_ingest hands the whole buffer to the direct kernel (profile
+    slot 0) and launches no P1b (slot 1), though the counter is in mode 2"""
+    k, nh, m = 31, 10, 1024 * (5 << 16) - 3
+    b1, b2, room, fixed, fit = arena_geometry(1024, nh)
+    assert (b1, b2) == (10, 0) and fit < k, "this device's head-room fits the arena: %r" % ((room, fixed, fit),)
+    rng = np.random.default_rng(65)
+    seq = np.frombuffer(b"ACGTN", dtype=np.uint8)[rng.choice(5, 300_000, p=[0.2475] * 4 + [0.01])].tobytes()
+    out = {}
+    for mode in (1, 2):
+        with gpu.Bloom(k, m, nh, canonical=True, seed=12) as b:
+            b.set_mode(mode)
+            if mode == 2:
+                b.reserve(ARENA)
+            b.profile_enable(True); b.profile_reset()
+            b.insert_ascii(seq)
+            assert b.sync() == len(O.extract(seq, k, True))
+            used = [b.profile_get(i)[1] for i in range(4)]
+            assert used[0] >= 1 and used[1] == 0, used
+            out[mode] = b.read()
+    assert (out[1] == out[2]).all()

@@ -1,9 +1,9 @@
 """CPU run of the stage tests (not -m gpu): tests/kernels/stage_harness.hip compiled by g++ against tests/host/hip_emu, then
-tests/test_gpu_stage_*.py executed against that library in a subprocess each -- the ring, tile, sort-based and two-word
-kernels' logic checked against their stage contracts on every CPU test run, without a device.
+tests/test_gpu_stage_*.py executed against that library in a subprocess each -- the ring, tile, sort-based, two-word and
+partitioned-Bloom kernels' logic checked against their stage contracts on every CPU test run, without a device.
 
 What this is and is not: see tests/test_emu_kernels.py.  The harness library under tests/host/_build is test infrastructure,
-loaded only here (JFKT_LIB); races, memory ordering and speed are the GPU run's to judge.  Measured times of the six
+loaded only here (JFKT_LIB); races, memory ordering and speed are the GPU run's to judge.  Measured times of the eight
 modules under the emulation: profiles/stage_harness_emu_times.txt.  One case is the device's alone: the two-word tile
 kernel at k = 63 in a table of 2^29 slots (8 GB) skips itself here, as the k = 63 tests of tests/test_gpu_wide.py do."""
 import os
@@ -16,7 +16,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "tests", "host", "_build")
 MODULES = ["tests/test_gpu_stage_p2.py", "tests/test_gpu_stage_tile.py", "tests/test_gpu_stage_p1.py",
-           "tests/test_gpu_stage_p2_sort.py", "tests/test_gpu_stage_p1_wide.py", "tests/test_gpu_stage_tile_wide.py"]
+           "tests/test_gpu_stage_p2_sort.py", "tests/test_gpu_stage_p1_wide.py", "tests/test_gpu_stage_tile_wide.py",
+           "tests/test_gpu_stage_bloom_p1.py", "tests/test_gpu_stage_bloom_seg.py"]
 SKIPS = {"tests/test_gpu_stage_tile_wide.py": 1}             # (the k = 63 case at 2^29 slots)
 
 

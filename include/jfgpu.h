@@ -150,13 +150,31 @@ int  jfgpu_add_keys(jfgpu_table* t, const uint64_t* keys, size_t n, uint64_t val
 
 /* The same with a value per key: hash_counter::add(const mer_dna&, uint64_t val) over a batch (hash_counter.hpp:122-126 ->
  * large_hash_array.hpp:741-752 add_val) -- what loads the records of a binary/sorted file back into a table, so that
- * `query -s` (sub_commands/query_main.cc:44-51) answers from the device.  Host arrays; keys of one or two words. */
+ * `query -s` (sub_commands/query_main.cc:44-51) answers from the device.  Host arrays; keys of every width (k <= 128),
+ * key_words = ceil(2k / 64) words each. */
 int  jfgpu_add_key_vals(jfgpu_table* t, const uint64_t* keys, const uint64_t* vals, size_t n);
 
 /* array::get_val_for_key (large_hash_array.hpp:354-372) for a batch.  vals[i] = 0 and
  * found[i] = 0 when absent.  Keys must already be canonical if the table is. */
 int  jfgpu_lookup_dev(jfgpu_table* t, const uint64_t* d_keys, size_t n, uint64_t* d_vals, uint8_t* d_found);
 int  jfgpu_lookup(jfgpu_table* t, const uint64_t* keys, size_t n, uint64_t* vals, uint8_t* found);
+
+/* query_from_sequence (sub_commands/query_main.cc:44-51; examples/query_per_sequence/query_per_sequence.cc) over one
+ * parser-contract buffer, the contract of jfgpu_count_ascii_dev: mer_iterator (mer_iterator.hpp:53-81) -> canonical (:51)
+ * -> array::get_val_for_key (large_hash_array.hpp:354-372) for every k-mer of the buffer, in one kernel and for every mer
+ * length.  The table is only read; pending partitioned counts are applied first.  An attached Bloom counter is not asked.
+ * Both outputs have n entries, indexed by the position of the k-mer's LAST base (its first base is k - 1 before):
+ *   vals[p]   the k-mer's count; 0 where no k-mer ends at p or the k-mer is absent
+ *   flags[p]  (optional) JFGPU_Q_MER: a k-mer ends at p; JFGPU_Q_FOUND: it is in the table; JFGPU_Q_REVCOMP: the table is
+ *             canonical and the key looked up is the reverse complement of the text (never set for a palindrome)
+ * Every entry is written (no memset needed), nothing beyond n.  Not for a shard (JFGPU_E_UNSUPPORTED: the keys of the
+ * other shards are not here).  The _dev form is asynchronous on the table's stream; the host form stages the buffer in
+ * pieces that overlap by k - 1 bytes and reports every position once. */
+#define JFGPU_Q_MER     1
+#define JFGPU_Q_FOUND   2
+#define JFGPU_Q_REVCOMP 4
+int  jfgpu_query_ascii_dev(jfgpu_table* t, const char* d_bases, size_t n, uint64_t* d_vals, uint8_t* d_flags);
+int  jfgpu_query_ascii(jfgpu_table* t, const char* bases, size_t n, uint64_t* vals, uint8_t* flags);
 
 /* ---- multi-GPU: hash-prefix partition --------------------- */
 /* Encode + canonicalise + hash one contract buffer and bucket the k-mers by owning

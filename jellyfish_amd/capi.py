@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("JFGPU_LIB") or os.path.join(_HERE, "lib", "libjfgpu.s
 
 OK, E_INVALID, E_NO_DEVICE, E_ALLOC, E_FULL, E_HIP, E_UNSUPPORTED, E_FORMAT, E_CORRUPT = range(9)
 PARSE_FASTA, PARSE_FASTQ, PARSE_CONTINUE = 1, 2, 4
+Q_MER, Q_FOUND, Q_REVCOMP = 1, 2, 4                          # include/jfgpu.h: JFGPU_Q_*, the flags of query_ascii
 
 
 class JfgpuError(RuntimeError):
@@ -73,6 +74,8 @@ SIGNATURES = {
     "jfgpu_add_key_vals": (C.c_int, [_P, _P, _P, C.c_size_t]),
     "jfgpu_lookup_dev": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "jfgpu_lookup": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "jfgpu_query_ascii_dev": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "jfgpu_query_ascii": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "jfgpu_partition_ascii_dev": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P]),
     "jfgpu_comm_unique_id": (C.c_int, [_P]),
     "jfgpu_comm_create": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.POINTER(_P)]),
@@ -318,6 +321,22 @@ class Table:
         found = np.zeros(len(keys), dtype=np.uint8)
         _check(self._lib.jfgpu_lookup(self._h, keys.ctypes.data, len(keys), vals.ctypes.data, found.ctypes.data))
         return vals, found.astype(bool)
+
+    def lookup_dev(self, d_keys, n, d_vals, d_found=None):
+        _check(self._lib.jfgpu_lookup_dev(self._h, _ptr(d_keys), n, _ptr(d_vals), _ptr(d_found)))
+
+    def query_ascii(self, seq: bytes):
+        """The count of every k-mer of a contract buffer, indexed by the position of the k-mer's last base:
+        (vals uint64[n], flags uint8[n] of Q_MER | Q_FOUND | Q_REVCOMP)."""
+        buf = np.frombuffer(seq, dtype=np.uint8)
+        vals = np.zeros(len(seq), dtype=np.uint64)
+        flags = np.zeros(len(seq), dtype=np.uint8)
+        _check(self._lib.jfgpu_query_ascii(self._h, buf.ctypes.data if len(seq) else None, len(seq),
+                                           vals.ctypes.data if len(seq) else None, flags.ctypes.data if len(seq) else None))
+        return vals, flags
+
+    def query_ascii_dev(self, d_bases, n, d_vals, d_flags=None):
+        _check(self._lib.jfgpu_query_ascii_dev(self._h, _ptr(d_bases), n, _ptr(d_vals), _ptr(d_flags)))
 
     def partition_ascii_dev(self, d_bases, n, d_keys_out, capacity):
         counts = np.zeros(1 << self.info.shard_bits, dtype=np.uint64)

@@ -997,70 +997,79 @@ int query_main(int argc, char* argv[]) {
   struct { binary_query* b; bloom_query* f; uint64_t check(const mer_dna& m) const { return b ? b->check(m) : f->check(m); } } bq{bin.get(), bloom.get()};
   const bool canonical = header.canonical();
   const unsigned k = mer_dna::k();
-  // query_from_sequence (query_main.cc:44-51) answered by the device (batched GPU lookups): the file's records
-  // go back into a table under the header's own matrix (jfgpu_add_key_vals), the k-mers of the -s files are looked up in
-  // batches of a million (jfgpu_lookup: array::get_val_for_key over a batch).  Keys of one and two words, binary/sorted
-  // databases; anything else -- or JFGPU_QUERY_HOST=1, or no device -- takes the host's binary search below.
-  if(!sequences.empty() && bin && k <= 64 && !getenv("JFGPU_QUERY_HOST") && jfgpu_device_count() > 0) {
+  // query_from_sequence (query_main.cc:44-51) answered by the device: the file's records go back into a
+  // table under the header's own matrix (jfgpu_add_key_vals), and the contract buffers of the -s files are handed to
+  // jfgpu_query_ascii as they are -- the k-mers are rolled, made canonical and looked up in one kernel, for every mer
+  // length.  What comes back is a count and three flag bits per position; the k-mer's text is taken from the buffer.
+  // Binary/sorted databases; a Bloom counter, JFGPU_QUERY_HOST=1 or no device take the host's binary search below, and so
+  // does a device that fails before anything was written (no room for the table, ...).
+  // JFGPU_QUERY_TRACE: one line on stderr saying which of the two answered.
+  const bool trace = getenv("JFGPU_QUERY_TRACE") != nullptr;
+  bool on_device = false;
+  if(!sequences.empty() && bin && !getenv("JFGPU_QUERY_HOST") && jfgpu_device_count() > 0) {
     jfgpu_params p; memset(&p, 0, sizeof p);
     p.k = k; p.canonical = canonical; p.size = header.size(); p.device = -1; p.out_counter_len = 8;
     const header_matrix hm = header.matrix();
     if(!hm.identity) p.matrix_columns = hm.columns.data();
     jfgpu_table* t = nullptr;
-    if(jfgpu_create(&p, &t) != JFGPU_OK) {                   // (no room for the table on the device, ...: the host path answers)
-      if(!getenv("JFGPU_QUIET")) std::cerr << "jellyfish-amd query: device table not created (" << jfgpu_last_error() << "): answering on the host\n";
+    auto to_host = [&](const char* what) {                   // nothing has been written yet: the host path answers
+      if(!getenv("JFGPU_QUIET")) std::cerr << "jellyfish-amd query: " << what << " (" << jfgpu_last_error() << "): answering on the host\n";
+      if(t) jfgpu_destroy(t);
       t = nullptr;
+    };
+    if(jfgpu_create(&p, &t) != JFGPU_OK) { t = nullptr; to_host("device table not created"); }
+    if(t) {
+      const unsigned kw = (2 * k + 63) / 64, kb = (2 * k + 7) / 8, vb = header.counter_len();
+      const size_t rec = kb + vb, n_rec = (map.length() - header.offset()) / rec;
+      const unsigned char* body = reinterpret_cast<const unsigned char*>(map.base() + header.offset());
+      const size_t kBatch = (size_t)1 << 20;
+      std::vector<uint64_t> keys(kBatch * kw), vals(kBatch);
+      for(size_t r0 = 0; r0 < n_rec && t; r0 += kBatch) {
+        const size_t n = std::min(kBatch, n_rec - r0);
+        std::fill(keys.begin(), keys.begin() + n * kw, 0); std::fill(vals.begin(), vals.begin() + n, 0);
+        for(size_t i = 0; i < n; ++i) { memcpy(&keys[i * kw], body + (r0 + i) * rec, kb); memcpy(&vals[i], body + (r0 + i) * rec + kb, vb); }
+        if(jfgpu_add_key_vals(t, keys.data(), vals.data(), n) != JFGPU_OK) to_host("database not loaded into the device table");
+      }
     }
     if(t) {
-    const unsigned kw = (2 * k + 63) / 64, kb = (2 * k + 7) / 8, vb = header.counter_len();
-    const size_t rec = kb + vb, n_rec = (map.length() - header.offset()) / rec;
-    const unsigned char* body = reinterpret_cast<const unsigned char*>(map.base() + header.offset());
-    const size_t kBatch = (size_t)1 << 20;
-    std::vector<uint64_t> keys(kBatch * kw), vals(kBatch);
-    for(size_t r0 = 0; r0 < n_rec; r0 += kBatch) {
-      const size_t n = std::min(kBatch, n_rec - r0);
-      std::fill(keys.begin(), keys.begin() + n * kw, 0); std::fill(vals.begin(), vals.begin() + n, 0);
-      for(size_t i = 0; i < n; ++i) { memcpy(&keys[i * kw], body + (r0 + i) * rec, kb); memcpy(&vals[i], body + (r0 + i) * rec + kb, vb); }
-      if(jfgpu_add_key_vals(t, keys.data(), vals.data(), n) != JFGPU_OK) { const std::string e = jfgpu_last_error(); jfgpu_destroy(t); die("query: " + e); }
-    }
-    std::vector<uint8_t> found(kBatch);
-    size_t fill = 0;
-    std::string text;
-    auto answer = [&]() {
-      if(!fill) return;
-      if(jfgpu_lookup(t, keys.data(), fill, vals.data(), found.data()) != JFGPU_OK) { const std::string e = jfgpu_last_error(); jfgpu_destroy(t); die("query: " + e); }
-      mer_dna m(k);
-      text.clear();
-      for(size_t i = 0; i < fill; ++i) {
-        memcpy(m.data__(), &keys[i * kw], kw * sizeof(uint64_t));
-        text += m.to_str(); text += ' '; text += std::to_string(vals[i]); text += '\n';
-      }
-      out.write(text.data(), text.size());
-      fill = 0;
-    };
-    for(const auto& path : sequences) {
-      sequence_parser parser(k);
-      parser.parse_file(path.c_str(), [&](const char* buf, size_t n) {
-        mer_dna m(k), rc(k);
-        unsigned filled = 0;
-        for(size_t i = 0; i < n; ++i) {
-          const int code = mer_dna::code(buf[i]);
-          if(code < 0) { filled = 0; continue; }
-          m.shift_left(code); rc.shift_right(3 - code);
-          if(++filled >= k) {
-            filled = k;
-            const mer_dna& q = (!canonical || m < rc) ? m : rc;
-            for(unsigned w = 0; w < kw; ++w) keys[fill * kw + w] = q.word(w);
-            if(++fill == kBatch) answer();
+      std::vector<uint64_t> vals; std::vector<uint8_t> flags;
+      std::string text;
+      uint64_t positions = 0, n_mers = 0;
+      bool wrote = false;
+      for(const auto& path : sequences) {
+        if(!t) break;
+        sequence_parser parser(k, (size_t)8 << 20);
+        parser.parse_file(path.c_str(), [&](const char* buf, size_t n) {
+          if(!t || !n) return;
+          vals.resize(n); flags.resize(n);
+          if(jfgpu_query_ascii(t, buf, n, vals.data(), flags.data()) != JFGPU_OK) {
+            if(wrote) { const std::string e = jfgpu_last_error(); jfgpu_destroy(t); die("query: " + e); }
+            to_host("device query failed");
+            return;
           }
-        }
-      });
-    }
-    answer();
-    jfgpu_destroy(t);
-    sequences.clear();
+          text.clear();
+          for(size_t i = 0; i < n; ++i) {
+            if(!(flags[i] & JFGPU_Q_MER)) continue;
+            ++n_mers;
+            const char* w = buf + i + 1 - k;                  // the k-mer's text; printed in the form that was looked up (mer_dna::to_str)
+            if(flags[i] & JFGPU_Q_REVCOMP) for(unsigned j = 0; j < k; ++j) text += mer_dna::rev_code(mer_dna::complement(mer_dna::code(w[k - 1 - j])));
+            else for(unsigned j = 0; j < k; ++j) text += (char)(w[j] & 0xDF);
+            text += ' '; text += std::to_string(vals[i]); text += '\n';
+            if(text.size() >= ((size_t)1 << 20)) { out.write(text.data(), text.size()); text.clear(); }
+          }
+          out.write(text.data(), text.size());
+          positions += n; wrote = true;
+        });
+      }
+      if(t) {
+        jfgpu_destroy(t);
+        sequences.clear();
+        on_device = true;
+        if(trace) std::cerr << "query: device k=" << k << " positions=" << positions << " mers=" << n_mers << "\n";
+      }
     }
   }
+  if(trace && !on_device) std::cerr << "query: host\n";
   for(const auto& path : sequences) {
     sequence_parser parser(k);
     parser.parse_file(path.c_str(), [&](const char* buf, size_t n) {

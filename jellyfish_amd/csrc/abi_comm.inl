@@ -1600,7 +1600,6 @@ int jfgpu_add_key_vals(jfgpu_table* t, const uint64_t* keys, const uint64_t* val
   int rc = use(t); if(rc) return rc;
   if(!n) return JFGPU_OK;
   if(!keys || !vals) return fail(JFGPU_E_INVALID, "null argument");
-  if(t->nword) return fail(JFGPU_E_UNSUPPORTED, "add_key_vals: keys longer than two words are not built");
   if(t->g.shard_bits) return fail(JFGPU_E_UNSUPPORTED, "add_key_vals: not for a shard (route the keys first)");
   const size_t kw = t->key_words;
   uint64_t *d_k = nullptr, *d_v = nullptr;

@@ -48,7 +48,7 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 constexpr uint64_t kDefaultSeed = 0x6A656C6C79666973ull;  // "jellyfis"
 constexpr size_t kStageBytes = 64u << 20;                  // host->device staging chunk
-constexpr int kNumProf = 8;   // 0 count 1 add_keys 2 shard-partition 3 lookup 4 P1 5 P2 6 tile-insert 7 items-direct
+constexpr int kNumProf = 9;   // 0 count 1 add_keys 2 shard-partition 3 lookup 4 P1 5 P2 6 tile-insert 7 items-direct 8 query
 enum Mode { MODE_AUTO = 0, MODE_DIRECT = 1, MODE_PARTITIONED = 2 };
 
 // Entries of the count-overflow side table of a small table (1 MiB): counts beyond the in-slot field are rare in k-mer
@@ -786,6 +786,8 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
       HIP_TRY(hipFuncSetAttribute((const void*)route_count_kernel<NTable, false>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
       HIP_TRY(hipFuncSetAttribute((const void*)route_scatter_kernel<NTable, false>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
     }
+    HIP_TRY(hipFuncSetAttribute((const void*)query_ascii_kernel<NTable>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)query_lds_bytes(t->g.nbytes, KeyOps<NTable>::kHaloWords)));
   } else if(wide) {
     WideTable& w = t->wt;
     w.slots = d.slots; w.fwd_tbl = d.fwd_tbl; w.inv_tbl = d.inv_tbl; w.ovf_key = d.ovf_key; w.ovf_cnt = d.ovf_cnt;
@@ -1102,6 +1104,61 @@ int jfgpu_lookup(jfgpu_table* t, const uint64_t* keys, size_t n, uint64_t* vals,
   if(e == hipSuccess && !rc && found) e = hipMemcpyAsync(found, d_f, n, hipMemcpyDeviceToHost, t->stream);
   hipStreamSynchronize(t->stream);
   hipFree(d_k); hipFree(d_v); hipFree(d_f);
+  if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
+  return rc;
+}
+
+// query_from_sequence (query_main.cc:44-51) over one contract buffer: query_ascii_kernel
+int jfgpu_query_ascii_dev(jfgpu_table* t, const char* d_bases, size_t n, uint64_t* d_vals, uint8_t* d_flags) {
+  int rc = use(t); if(rc) return rc;
+  rc = part_flush(t); if(rc) return rc;
+  if(!n) return JFGPU_OK;
+  if(!d_bases || !d_vals) return fail(JFGPU_E_INVALID, "null argument");
+  if(t->g.shard_bits) return fail(JFGPU_E_UNSUPPORTED, "query_ascii: not for a shard (the keys of the other shards are not here)");
+  uint64_t c[CTR_COUNT];
+  rc = check_deferred(t, c); if(rc) return rc;
+  const uint8_t* base; int64_t lo, hi;
+  align_buffer(d_bases, n, base, lo, hi);
+  const int grid = grid_for(t, (uint64_t)((hi + kTilePos - 1) / kTilePos));
+  ProfScope ps(t, 8, n);
+  with_view(t, [&](const auto& T) {
+    typedef std::decay_t<decltype(T)> Table;
+    typedef KeyOps<Table> K;
+    const size_t lds = K::kFwdLdsWords ? 0 : query_lds_bytes(t->g.nbytes, K::kHaloWords);
+    hipLaunchKernelGGL(query_ascii_kernel<Table>, dim3(grid), dim3(kBlock), lds, t->stream, T, base, lo, hi, d_vals, d_flags, (int)(c[CTR_OVF_USED] != 0));
+  });
+  HIP_TRY(hipGetLastError());
+  return JFGPU_OK;
+}
+
+// Host arrays, staged through the table's double buffer like jfgpu_count_ascii: pieces overlap by k - 1 bytes, and the
+// first k - 1 outputs of every piece after the first (windows the piece before has answered, or that it alone sees
+// whole) are not copied back.  The outputs of a piece are copied straight into the caller's arrays.
+int jfgpu_query_ascii(jfgpu_table* t, const char* bases, size_t n, uint64_t* vals, uint8_t* flags) {
+  int rc = use(t); if(rc) return rc;
+  if(!n) return JFGPU_OK;
+  if(!bases || !vals) return fail(JFGPU_E_INVALID, "null argument");
+  if(t->g.shard_bits) return fail(JFGPU_E_UNSUPPORTED, "query_ascii: not for a shard (the keys of the other shards are not here)");
+  rc = ensure_stage(t); if(rc) return rc;
+  const size_t piece = std::min(kStageBytes, n), seam = t->g.k - 1;
+  uint64_t* d_v = nullptr; uint8_t* d_f = nullptr;
+  HIP_TRY(hipMalloc((void**)&d_v, piece * sizeof(uint64_t)));
+  if(flags && hipMalloc((void**)&d_f, piece) != hipSuccess) { hipFree(d_v); return fail(JFGPU_E_ALLOC, "hipMalloc query flags"); }
+  hipError_t e = hipSuccess;
+  for(size_t o = 0; o < n && e == hipSuccess && !rc; o += kStageBytes - seam) {
+    const size_t len = std::min(kStageBytes, n - o), skip = o ? seam : 0;
+    const int b = t->stage_next; t->stage_next ^= 1;
+    e = hipEventSynchronize(t->stage_done[b]);                 // the kernel that last read this buffer has finished
+    if(e == hipSuccess) e = hipMemcpyAsync(t->d_stage[b], bases + o, len, hipMemcpyHostToDevice, t->stream);
+    if(e == hipSuccess) rc = jfgpu_query_ascii_dev(t, (const char*)t->d_stage[b], len, d_v, d_f);
+    if(e == hipSuccess && !rc) e = hipEventRecord(t->stage_done[b], t->stream);
+    if(e == hipSuccess && !rc) e = hipMemcpyAsync(vals + o + skip, d_v + skip, (len - skip) * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream);
+    if(e == hipSuccess && !rc && flags) e = hipMemcpyAsync(flags + o + skip, d_f + skip, len - skip, hipMemcpyDeviceToHost, t->stream);
+    if(e == hipSuccess && !rc) e = hipStreamSynchronize(t->stream);      // (d_v and d_f are the next piece's too)
+    if(o + len >= n) break;
+  }
+  hipStreamSynchronize(t->stream);
+  hipFree(d_v); if(d_f) hipFree(d_f);
   if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
   return rc;
 }

@@ -322,6 +322,10 @@ __device__ inline bool table_add_val(const DevTable& T, const uint64_t* fwd_lds,
 //                                    word asks for the lane's 16 windows at once and tests a bit, two words ask key by key
 //                                    (the mask is all ones); NTable takes no filter and has neither
 //   kKeyWords                        64-bit words a routed key is stored as by store_key (0: the caller's kw, 3 or 4)
+// and, for query_ascii_kernel:
+//   same_key(a, b)                   are two keys equal
+//   text_key(T, L, j)                the k-mer ending at position j of the lane as the text has it, not its canonical form
+//   Probe, find_begin, find_end      (one word) find in two halves, so that a lane's look-ups overlap
 template <class Table> struct KeyOps;
 
 __device__ inline void load_tables_lds(uint64_t* dst, const uint64_t* src, uint32_t nbytes) {
@@ -357,7 +361,29 @@ template <> struct KeyOps<DevTable> {
     const SlotAddr a = slot_addr(T.g, hash_tables(H, key, T.g.nbytes));
     return a.shard == T.g.shard_id ? table_find_at(T, key, a) : ~0ull;
   }
+  // find in two halves (query_ascii_kernel): find_begin hashes and issues the load of the first slot probed, find_end
+  // resolves it and probes on.  Between the two a lane may begin more look-ups, so their line fills overlap.  find_end
+  // leaves the word of the slot it returns in p.w.
+  struct Probe { uint64_t low, slot, w; };
+  __device__ static Probe find_begin(const DevTable& T, const uint64_t* H, Key key) {
+    const SlotAddr a = slot_addr(T.g, hash_tables(H, key, T.g.nbytes));
+    Probe p;
+    p.low = T.g.occ_bit | make_tag(T.g, key, a.idx0);
+    p.slot = a.tile_base + probe_lin(a.idx0, 0, (uint32_t)T.g.tile_mask);
+    p.w = a.shard == T.g.shard_id ? slot_ld_relaxed(T, p.slot) : 0ull;      // (a key of another shard is not here)
+    return p;
+  }
+  __device__ static uint64_t find_end(const DevTable& T, Probe& p) {
+    uint64_t slot = p.slot;
+    for(uint32_t q = 0; p.w != 0ull; p.w = slot_ld_relaxed(T, slot)) {
+      if((p.w & T.g.low_mask) == p.low) return slot;
+      if(++q > T.max_probe) break;
+      slot = (p.slot & ~T.g.tile_mask) | ((p.slot + q) & T.g.tile_mask);      // probe_lin: linear from the bucket's start, inside the tile
+    }
+    return ~0ull;
+  }
   __device__ static uint32_t owner(const DevTable& T, const uint64_t* H, Key key) { return (uint32_t)(hash_tables(H, key, T.g.nbytes) >> T.g.lsize_l); }
+  __device__ static bool same_key(Key a, Key b) { return a == b; }
   __device__ static void store_key(uint64_t* dst, Key key, uint32_t) { dst[0] = key; }
   __device__ static Key load_key(const DevTable& T, const uint64_t* keys, uint64_t i, uint32_t, bool masked) { return masked ? keys[i] & T.g.key_mask : keys[i]; }
   __device__ static Lane stage_tile(const DevTable&, const uint8_t* __restrict__ base, int64_t tile_start, int64_t lo, int64_t hi, uint32_t* s_codes, uint32_t* s_inv) {
@@ -365,6 +391,9 @@ template <> struct KeyOps<DevTable> {
   }
   template <typename F>
   __device__ static void for_each_kmer(const DevTable& T, const Lane& L, F&& f) { jfgpu::for_each_kmer(T.g, L, [&](int j, uint64_t key) { f(j, key, true); }); }
+  __device__ static Key text_key(const DevTable& T, const Lane& L, int j) {     // the k-mer as the text has it (no canonical form) ending at position j
+    return (((((uint64_t)L.p2 << 32) | L.p1) << (2 * j + 2)) | (L.cur >> (30 - 2 * j))) & T.g.key_mask;
+  }
   __device__ static uint32_t route_rank(bool valid, uint32_t owner, uint32_t* s_hist) { return valid ? atomicAdd(&s_hist[owner], 1u) : 0u; }
   __device__ static uint32_t admit_mask(const DevTable& T, const Lane& L) { return bloom_admit_mask(T.bloom, T.g, L); }
   __device__ static bool admits(const DevTable&, uint32_t mask, int j, Key) { return (mask >> j) & 1u; }
@@ -538,6 +567,114 @@ __global__ __launch_bounds__(kBlock) void lookup_kernel(Table T, const uint64_t*
     const uint64_t s = K::find(T, H, K::load_key(T, keys, i, kw, true));
     vals[i] = s == ~0ull ? 0 : K::count_at(T, s, have_ovf);
     if(found) found[i] = s != ~0ull;
+  }
+}
+
+// ---- query: the count of every k-mer of a contract buffer, every key width (KeyOps) ----------------------------------
+// query_from_sequence (sub_commands/query_main.cc:44-51; examples/query_per_sequence): mer_iterator over the sequence and
+// array::get_val_for_key per k-mer, fused -- the tile loop of route_count_kernel with the look-up of lookup_kernel inside.
+// The table is only read: no atomics, no counters.
+// Output, indexed by the byte position p of the window's LAST base (p - lo of the aligned buffer): vals[p] the full count
+// (0 where no k-mer ends or the key is absent) and, when flags is given, JFGPU_Q_MER | JFGPU_Q_FOUND | JFGPU_Q_REVCOMP.  Every
+// entry of [0, hi - lo) is written, nothing else.  A lane's 16 positions are 128 bytes of vals and 16 of flags: eight and
+// one 16-byte stores when the caller's buffers are aligned (lo == 0, vals and flags on 16 bytes), single entries otherwise
+// and in the ragged last lane.
+// One word: a lane's 16 look-ups do not wait for one another.  Sweep one hashes every window and issues the load of the
+// first slot of its home bucket (KeyOps::find_begin, the registers of route_scatter_kernel's keys[j]); sweep two resolves
+// them (find_end), probing on where the first slot was another key's.  The wider views roll once and look up as they go.
+// A window whose key equals the previous position's takes its answer (homopolymers and short tandem repeats, the run
+// merge of count_ascii_kernel).
+// LDS: the forward tables and the tile's codes and invalid masks; static for one and two words, dynamic for NTable
+// (query_lds_bytes).
+constexpr uint32_t kQMer = 1, kQFound = 2, kQRevcomp = 4;      // JFGPU_Q_* (include/jfgpu.h)
+struct QueryLds { uint64_t* fwd; uint32_t *codes, *inv; };
+inline size_t query_lds_bytes(uint32_t nbytes, uint32_t halo_words) { return (size_t)nbytes * 256 * 8 + 2 * (kBlock + halo_words) * 4; }
+template <class Table>
+__device__ inline QueryLds query_lds(uint32_t nbytes) {
+  typedef KeyOps<Table> K;
+  constexpr uint32_t kStage = kBlock + K::kHaloWords;
+  QueryLds S;
+  if constexpr(K::kFwdLdsWords != 0) {
+    __shared__ uint64_t s_fwd[K::kFwdLdsWords];
+    __shared__ uint32_t s_codes[kStage];
+    __shared__ uint32_t s_inv[kStage];
+    S.fwd = s_fwd; S.codes = s_codes; S.inv = s_inv;
+  } else {
+    JF_DYN_LDS(s_raw);
+    S.fwd = reinterpret_cast<uint64_t*>(s_raw);
+    S.codes = reinterpret_cast<uint32_t*>(S.fwd + (size_t)nbytes * 256);
+    S.inv = S.codes + kStage;
+  }
+  return S;
+}
+
+template <class Table>
+__global__ __launch_bounds__(kBlock) void query_ascii_kernel(Table T, const uint8_t* __restrict__ base, int64_t lo, int64_t hi,
+                                                             uint64_t* __restrict__ vals, uint8_t* __restrict__ flags, int have_ovf) {
+  typedef KeyOps<Table> K;
+  typedef typename K::Key Key;
+  constexpr bool kTwoSweeps = sizeof(Key) == 8;
+  const TableGeom& g = K::geom(T);
+  const QueryLds S = query_lds<Table>(g.nbytes);
+  load_tables_lds(S.fwd, T.fwd_tbl, g.nbytes);
+  const bool aligned = lo == 0 && (((uintptr_t)vals | (uintptr_t)flags) & 15) == 0;
+  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
+  for(int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    __syncthreads();
+    const typename K::Lane L = K::stage_tile(T, base, tile * kTilePos, lo, hi, S.codes, S.inv);     // contains a barrier
+    // indexed by the unrolled position j (compile-time after unrolling) so these stay in VGPRs
+    uint64_t v[kPerThread]; uint32_t fl[kPerThread / 4] = {0, 0, 0, 0};
+    auto revcomp_bit = [&](int j, const Key& key) { return (g.canonical && !K::same_key(key, K::text_key(T, L, j))) ? kQRevcomp : 0u; };
+    auto answer = [&](int j, uint64_t count, uint32_t bits) { v[j] = count; fl[j >> 2] |= bits << (8 * (j & 3)); };
+    if constexpr(kTwoSweeps) {
+      typename K::Probe pr[kPerThread]; Key prev = 0; uint32_t mer = 0, rc = 0, same = 0;
+      K::for_each_kmer(T, L, [&](int j, const Key& key, bool) {
+        mer |= 1u << j; rc |= (revcomp_bit(j, key) ? 1u : 0u) << j;
+        if(j > 0 && ((mer >> (j - 1)) & 1u) && key == prev) { same |= 1u << j; return; }
+        prev = key;
+        pr[j] = K::find_begin(T, S.fwd, key);
+      });
+      uint64_t count = 0; uint32_t bits = 0;
+#pragma unroll
+      for(int j = 0; j < kPerThread; ++j) {
+        if(!((mer >> j) & 1u)) { v[j] = 0; continue; }
+        if(!((same >> j) & 1u)) {
+          const uint64_t slot = K::find_end(T, pr[j]);
+          bits = slot != ~0ull ? kQFound : 0u;
+          count = slot != ~0ull ? full_count(T, pr[j].w, slot, have_ovf) : 0;
+        }
+        answer(j, count, kQMer | bits | (((rc >> j) & 1u) ? kQRevcomp : 0u));
+      }
+    } else {
+#pragma unroll
+      for(int j = 0; j < kPerThread; ++j) v[j] = 0;
+      Key prev = Key(); int last = -2; uint64_t count = 0; uint32_t bits = 0;
+      K::for_each_kmer(T, L, [&](int j, const Key& key, bool valid) {
+        if(!valid) return;
+        if(last != j - 1 || !K::same_key(key, prev)) {
+          const uint64_t slot = K::find(T, S.fwd, key);
+          bits = slot != ~0ull ? kQFound : 0u;
+          count = slot != ~0ull ? K::count_at(T, slot, have_ovf) : 0;
+          prev = key;
+        }
+        last = j;
+        answer(j, count, kQMer | bits | revcomp_bit(j, key));
+      });
+    }
+    const int64_t off = tile * kTilePos + 16 * (int64_t)threadIdx.x;       // the lane's first position in the aligned buffer
+    if(aligned && off + 16 <= hi) {
+#pragma unroll
+      for(int q = 0; q < kPerThread / 2; ++q) reinterpret_cast<ulonglong2*>(vals + off)[q] = make_ulonglong2(v[2 * q], v[2 * q + 1]);
+      if(flags) *reinterpret_cast<uint4*>(flags + off) = make_uint4(fl[0], fl[1], fl[2], fl[3]);
+    } else {
+#pragma unroll
+      for(int j = 0; j < kPerThread; ++j) {
+        const int64_t p = off + j;
+        if(p < lo || p >= hi) continue;
+        vals[p - lo] = v[j];
+        if(flags) flags[p - lo] = (uint8_t)(fl[j >> 2] >> (8 * (j & 3)));
+      }
+    }
   }
 }
 

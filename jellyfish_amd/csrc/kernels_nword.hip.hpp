@@ -442,6 +442,12 @@ template <> struct KeyOps<NTable> {
   }
   template <typename F>
   __device__ static void for_each_kmer(const NTable& T, const Lane& L, F&& f) { for_each_kmer_nword(T.N, L, f); }
+  __device__ static bool same_key(const Key& a, const Key& b) { return k256_eq(a, b); }
+  __device__ static Key text_key(const NTable& T, const Lane& L, int j) {      // (L.fw: the k-mer ending just before the lane)
+    Key r = k256_shl(L.fw, 2 * j + 2);
+    r.w[0] |= L.c >> (30 - 2 * j);
+    return k256_and(r, T.N.key_mask);
+  }
   __device__ static uint32_t route_rank(bool valid, uint32_t owner, uint32_t* s_hist) { return nword_wave_rank(valid, owner, s_hist); }
 };
 

@@ -374,6 +374,11 @@ template <> struct KeyOps<WideTable> {
   }
   template <typename F>
   __device__ static void for_each_kmer(const WideTable& T, const Lane& L, F&& f) { for_each_kmer_wide(T.W, L, [&](int j, u128 key) { f(j, key, true); }); }
+  __device__ static bool same_key(Key a, Key b) { return a == b; }
+  __device__ static Key text_key(const WideTable& T, const Lane& L, int j) {
+    const u128 before = ((u128)L.p4 << 96) | ((u128)L.p3 << 64) | ((u128)L.p2 << 32) | L.p1;
+    return ((before << (2 * j + 2)) | (L.cur >> (30 - 2 * j))) & T.W.key_mask;
+  }
   __device__ static uint32_t route_rank(bool valid, uint32_t owner, uint32_t* s_hist) { return valid ? atomicAdd(&s_hist[owner], 1u) : 0u; }
   __device__ static uint32_t admit_mask(const WideTable&, const Lane&) { return ~0u; }
   __device__ static bool admits(const WideTable& T, uint32_t, int, Key key) { return bloom_admits_wide(T.bloom, key); }

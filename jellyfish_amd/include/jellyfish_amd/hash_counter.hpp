@@ -209,6 +209,13 @@ public:
     return f != 0;
   }
   bool has_key(const mer_dna& k) { return get_val_for_key(k, nullptr); }
+  // query_from_sequence (sub_commands/query_main.cc:44-51; examples/query_per_sequence) over a contract buffer in host
+  // memory: vals[p] the count of the k-mer whose last base is at p, flags[p] (optional) JFGPU_Q_MER | JFGPU_Q_FOUND |
+  // JFGPU_Q_REVCOMP; n entries each (jfgpu_query_ascii).
+  void query_sequence(const char* seq, size_t n, uint64_t* vals, uint8_t* flags) {
+    flush();
+    jf_check(jfgpu_query_ascii(t_, seq, n, vals, flags));
+  }
 
   void flush() { if(in_spill_) return; std::lock_guard<std::mutex> lock(mu_); flush_locked(); }   // (a spill runs inside an engine call)
 

@@ -446,6 +446,42 @@ int  jfgpu_parser_stream_consume(jfgpu_parser* p, size_t n);
 int  jfgpu_parser_bam_decode(jfgpu_parser* p, size_t skip, int32_t n_ref, const char** d_out, size_t* n_out,
                              uint64_t* n_records, size_t* n_left);
 
+/* ---- merge: k-way merge of sorted databases on the device ----
+ * Replaces the heap loop of merge_files (jellyfish/merge_files.cc:36-176, driven by sub_commands/merge_main.cc) for
+ * binary/sorted inputs written with one hash function: every input is sorted by (pos, key), pos = (M * key) & (size - 1);
+ * the output is their union in that order with equal keys combined.  The output records are byte for byte what
+ * merge_files writes after its header (binary_writer::write, binary_dumper.hpp:36-40). */
+typedef struct jfgpu_merge jfgpu_merge;
+typedef struct jfgpu_merge_params {
+  uint32_t k;                     /* mer length, 1..128: keys of (2k+7)/8 bytes (merge_files.cc:127 key_len) */
+  uint32_t n_inputs;              /* 1..255; more is JFGPU_E_UNSUPPORTED (the caller merges on the host) */
+  uint64_t size;                  /* the headers' "size", a power of two (merge_files.cc:129,147-148) */
+  const uint64_t* matrix_columns; /* the headers' matrix: 2k columns in file-header order; NULL = the identity flag, pos = key & (size - 1) */
+  const uint32_t* counter_len;    /* [n_inputs] bytes of a count in each input, 1..8 (they may differ, merge_files.cc:139) */
+  uint32_t out_counter_len;       /* bytes of a count in the output: the inputs' minimum in merge_files (:139,163) */
+  uint32_t op;                    /* 0 sum, 1 min, 2 max, 3 Jaccard (sub_commands/merge_main.cc; merge_files.cc:59-100) */
+  uint64_t lower, upper;          /* a combined value outside [lower, upper] is dropped; tested before it is clamped to out_counter_len bytes */
+  int32_t  device;                /* HIP device ordinal, -1 = current device */
+  uint32_t reserved;
+  uint64_t window_records;        /* records of all inputs merged in one go; 0 = the engine's default */
+} jfgpu_merge_params;
+/* Receives n_records output records (n_records * ((2k+7)/8 + out_counter_len) bytes), in order; the bytes are the
+ * engine's until it returns.  Non-zero stops the merge. */
+typedef int (*jfgpu_merge_sink)(void* user, const void* bytes, uint64_t n_records);
+int  jfgpu_merge_create(const jfgpu_merge_params* p, jfgpu_merge** out);
+void jfgpu_merge_destroy(jfgpu_merge* m);
+/* bodies[i]: host memory (the mmap of the file past its header) holding n_records[i] records of input i.  The position
+ * range is cut into windows of about window_records records; uploads, kernels and downloads of neighbouring windows
+ * overlap.  JFGPU_E_FORMAT naming the input when one is not strictly increasing in (pos, key).  op 3 writes nothing
+ * (sink may be NULL): see jfgpu_merge_tallies. */
+int  jfgpu_merge_run(jfgpu_merge* m, const void* const* bodies, const uint64_t* n_records, jfgpu_merge_sink sink, void* user);
+/* op 3, after jfgpu_merge_run: inter, winter, union, wunion as merge_files.cc:59,91-92 tallies them. */
+int  jfgpu_merge_tallies(jfgpu_merge* m, uint64_t out4[4]);
+/* Milliseconds of the last run: upload (staging + host-to-device copies), kernels (HIP events), download, sink. */
+int  jfgpu_merge_last_ms(jfgpu_merge* m, double out4[4]);
+/* The last run's windows, records read and records written. */
+int  jfgpu_merge_counts(jfgpu_merge* m, uint64_t out3[3]);
+
 /* ---- measurement helpers (bench.py; not part of the reference surface) -- */
 /* Per-kernel HIP-event timing on the table's stream.  which: 0 count (direct), 1 add_keys,
  * 2 shard partition, 3 lookup, 4 P1 partition, 5 P2 partition, 6 tile insert, 7 items-direct.  Returns accumulated milliseconds and launches since the

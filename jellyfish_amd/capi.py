@@ -49,6 +49,17 @@ class BloomParams(C.Structure):
                 ("matrix2", C.POINTER(C.c_uint64))]
 
 
+class MergeParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("n_inputs", C.c_uint32), ("size", C.c_uint64), ("matrix_columns", C.POINTER(C.c_uint64)),
+                ("counter_len", C.POINTER(C.c_uint32)), ("out_counter_len", C.c_uint32), ("op", C.c_uint32),
+                ("lower", C.c_uint64), ("upper", C.c_uint64), ("device", C.c_int32), ("reserved", C.c_uint32),
+                ("window_records", C.c_uint64)]
+
+
+MERGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
+MERGE_SUM, MERGE_MIN, MERGE_MAX, MERGE_JACCARD = range(4)
+
+
 class Stats(C.Structure):
     _fields_ = [("unique", C.c_uint64), ("distinct", C.c_uint64), ("total", C.c_uint64),
                 ("max_count", C.c_uint64), ("occupied", C.c_uint64), ("mers_fed", C.c_uint64)]
@@ -132,6 +143,12 @@ SIGNATURES = {
     "jfgpu_parser_stream_consume": (C.c_int, [_P, C.c_size_t]),
     "jfgpu_parser_bam_decode": (C.c_int, [_P, C.c_size_t, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_size_t)]),
+    "jfgpu_merge_create": (C.c_int, [C.POINTER(MergeParams), C.POINTER(_P)]),
+    "jfgpu_merge_destroy": (None, [_P]),
+    "jfgpu_merge_run": (C.c_int, [_P, _P, _P, MERGE_SINK, _P]),
+    "jfgpu_merge_tallies": (C.c_int, [_P, _P]),
+    "jfgpu_merge_last_ms": (C.c_int, [_P, _P]),
+    "jfgpu_merge_counts": (C.c_int, [_P, _P]),
     "jfgpu_set_growth": (C.c_int, [_P, C.c_int]),
     "jfgpu_reference_matrix": (C.c_int, [C.c_uint32, C.c_uint32, _P]),
     "jfgpu_table_bytes": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -685,6 +702,74 @@ def decode_records(recs: np.ndarray, k: int, counter_len: int):
     for b in range(counter_len):
         cnts |= recs[:, kb + b].astype(np.uint64) << np.uint64(8 * b)
     return (keys[:, 0] if kw == 1 else keys), cnts
+
+
+class Merge:
+    """k-way merge of sorted record bodies on the device (jfgpu_merge_*).  matrix: the 2k columns of the inputs' headers
+    (None: the identity flag); counter_lens: bytes of a count in every input; op: MERGE_SUM / _MIN / _MAX / _JACCARD."""
+
+    def __init__(self, k, size, matrix, counter_lens, out_counter_len=None, op=MERGE_SUM, lower=0, upper=2 ** 64 - 1, device=-1,
+                 window_records=0):
+        self._lib = load()
+        self.k, self.kb = k, (2 * k + 7) // 8
+        self._clen = np.ascontiguousarray(counter_lens, dtype=np.uint32)
+        self.out_counter_len = int(self._clen.min()) if out_counter_len is None else out_counter_len
+        self._cols = None if matrix is None else np.ascontiguousarray(matrix, dtype=np.uint64)
+        p = MergeParams(k=k, n_inputs=len(self._clen), size=size,
+                        matrix_columns=None if self._cols is None else self._cols.ctypes.data_as(C.POINTER(C.c_uint64)),
+                        counter_len=self._clen.ctypes.data_as(C.POINTER(C.c_uint32)), out_counter_len=self.out_counter_len, op=op,
+                        lower=lower, upper=upper, device=device, reserved=0, window_records=window_records)
+        h = _P()
+        _check(self._lib.jfgpu_merge_create(C.byref(p), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.jfgpu_merge_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def run(self, bodies):
+        """bodies: one uint8 array of whole records per input.  Returns the output records as a uint8 array."""
+        bodies = [np.ascontiguousarray(b, dtype=np.uint8).reshape(-1) for b in bodies]
+        assert len(bodies) == len(self._clen)
+        ptrs = (C.c_void_p * len(bodies))(*[b.ctypes.data for b in bodies])
+        n = np.array([len(b) // (self.kb + int(c)) for b, c in zip(bodies, self._clen)], dtype=np.uint64)
+        orb = self.kb + self.out_counter_len
+        chunks = []
+
+        def sink(_user, data, n_records):
+            chunks.append(np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_uint8)), shape=(int(n_records) * orb,)).copy())
+            return 0
+
+        cb = MERGE_SINK(sink)
+        _check(self._lib.jfgpu_merge_run(self._h, C.cast(ptrs, _P), n.ctypes.data, cb, None))
+        return np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.uint8)
+
+    def tallies(self):
+        """After a MERGE_JACCARD run: (inter, winter, union, wunion)."""
+        out = np.zeros(4, dtype=np.uint64)
+        _check(self._lib.jfgpu_merge_tallies(self._h, out.ctypes.data))
+        return tuple(int(x) for x in out)
+
+    def last_ms(self):
+        """(upload, kernels, download, sink) milliseconds of the last run."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(self._lib.jfgpu_merge_last_ms(self._h, out.ctypes.data))
+        return tuple(float(x) for x in out)
+
+    def counts(self):
+        """(windows, records read, records written) of the last run."""
+        out = np.zeros(3, dtype=np.uint64)
+        _check(self._lib.jfgpu_merge_counts(self._h, out.ctypes.data))
+        return tuple(int(x) for x in out)
 
 
 class Parser:

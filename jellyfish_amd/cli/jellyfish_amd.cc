@@ -27,7 +27,10 @@
 #include <vector>
 
 #include <jellyfish_amd/dumpers.hpp>
+#include <fcntl.h>
+#include <sys/mman.h>
 #include <sys/stat.h>
+#include <unistd.h>
 #include <sys/wait.h>
 #include <jellyfish_amd/sequence_parser.hpp>
 #include <jellyfish_amd/device_parser.hpp>
@@ -110,11 +113,14 @@ template <typename F> void for_each_record(db_file& db, F f) {
 // ---------------------------------------------------------------- merge  (jellyfish/merge_files.cc:36-176, sub_commands/merge_main.cc)
 // k-way merge of sorted databases written with the same hash function: records of every input come in (pos, key)
 // order, so a heap of the inputs' heads yields the union in that order; equal keys are combined (sum / min / max)
-// or only tallied (Jaccard).  Host code: the inputs are files.
+// or only tallied (Jaccard).  binary/sorted inputs are merged on the device (jfgpu_merge_run over the mapped files, one
+// window of positions at a time); this heap is the path of text/sorted inputs, of a machine without a device and of
+// JFGPU_MERGE_HOST=1, and the fallback when the device path fails before it has written anything.
 struct MergeError : public std::runtime_error { explicit MergeError(const std::string& s) : std::runtime_error(s) {} };
 
 template <typename Reader, typename Writer>
-static void do_merge(std::vector<std::unique_ptr<db_file>>& files, std::ostream& out, Writer&& write, uint64_t min, uint64_t max, int op) {
+static void do_merge(std::vector<std::unique_ptr<db_file>>& files, std::ostream& out, Writer&& write, uint64_t min, uint64_t max, int op,
+                     uint64_t counts[2]) {
   struct head { uint64_t pos; mer_dna key; uint64_t val; size_t src; };
   const header_matrix m = files[0]->header.matrix();
   const uint64_t mask = files[0]->header.size() - 1;
@@ -124,6 +130,7 @@ static void do_merge(std::vector<std::unique_ptr<db_file>>& files, std::ostream&
   auto push = [&](size_t i) {
     Reader& r = *readers[i];
     if(!r.next()) return;
+    ++counts[0];
     heap.push_back(head{m.times(r.key().data()) & mask, r.key(), r.val(), i});
     std::push_heap(heap.begin(), heap.end(), later);
   };
@@ -142,10 +149,75 @@ static void do_merge(std::vector<std::unique_ptr<db_file>>& files, std::ostream&
     if(present < nb_files) minc = 0;               // absent from some file: count 0 there
     if(op != 3) {
       const uint64_t val = op == 0 ? sum : op == 1 ? minc : maxc;
-      if(val >= min && val <= max) write(out, key, val);
+      if(val >= min && val <= max) { write(out, key, val); ++counts[1]; }
     } else { inter += minc > 0; winter += minc; union_ += 1; wunion += maxc; }
   }
   if(op == 3) out << "Jaccard  " << (double)inter / (double)union_ << '\n' << "wJaccard " << (double)winter / (double)wunion << '\n';
+}
+
+// The device path of merge_files: the bodies of the inputs, mapped, go to jfgpu_merge_run and the output records come
+// back through a sink that appends them to `out`.  Returns false, with the reason in `why`, when the device did not merge
+// and nothing was appended -- the caller then merges on the host; a failure after the first append throws.
+struct mapped_input {
+  void* base = MAP_FAILED; size_t len = 0;
+  ~mapped_input() { if(base != MAP_FAILED) munmap(base, len); }
+};
+struct merge_sink_state { std::ostream* out; size_t record_bytes; bool called = false; };
+static int merge_sink_write(void* user, const void* bytes, uint64_t n_records) {
+  merge_sink_state* s = (merge_sink_state*)user;
+  s->called = true;
+  s->out->write((const char*)bytes, (std::streamsize)(n_records * s->record_bytes));
+  return s->out->good() ? 0 : 1;
+}
+static bool merge_on_device(const std::vector<std::string>& inputs, std::vector<std::unique_ptr<db_file>>& files, std::ostream& out,
+                            unsigned key_len, uint64_t size, const header_matrix& matrix, unsigned out_counter_len, uint64_t min, uint64_t max,
+                            int op, uint64_t counts[3], double ms[4], std::string& why) {
+  const unsigned kb = (key_len + 7) / 8;
+  if(matrix.identity ? (matrix.r < 64 && ((uint64_t)1 << matrix.r) != size) : matrix.columns.size() != key_len) { why = "a matrix the device path does not take"; return false; }
+  std::vector<mapped_input> maps(inputs.size());
+  std::vector<const void*> bodies(inputs.size(), nullptr);
+  std::vector<uint64_t> n_records(inputs.size(), 0);
+  std::vector<uint32_t> counter_len(inputs.size());
+  for(size_t i = 0; i < inputs.size(); ++i) {
+    counter_len[i] = files[i]->header.counter_len();
+    const std::streamoff body = files[i]->is.tellg();              // the header has been read: the records start here
+    struct stat st;
+    const int fd = open(inputs[i].c_str(), O_RDONLY);
+    if(fd < 0 || body < 0 || fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { if(fd >= 0) close(fd); why = "cannot map '" + inputs[i] + "'"; return false; }
+    if((uint64_t)st.st_size > (uint64_t)body) {
+      maps[i].len = (size_t)st.st_size;
+      maps[i].base = mmap(nullptr, maps[i].len, PROT_READ, MAP_PRIVATE, fd, 0);
+      if(maps[i].base == MAP_FAILED) { close(fd); why = "cannot map '" + inputs[i] + "'"; return false; }
+      bodies[i] = (const char*)maps[i].base + body;
+      n_records[i] = ((uint64_t)st.st_size - (uint64_t)body) / (kb + counter_len[i]);   // a cut last record is not one (binary_reader::next)
+    }
+    close(fd);
+  }
+  jfgpu_merge_params p;
+  memset(&p, 0, sizeof p);
+  p.k = key_len / 2; p.n_inputs = (uint32_t)inputs.size(); p.size = size;
+  p.matrix_columns = matrix.identity ? nullptr : matrix.columns.data();
+  p.counter_len = counter_len.data(); p.out_counter_len = out_counter_len; p.op = (uint32_t)op; p.lower = min; p.upper = max; p.device = -1;
+  if(const char* e = getenv("JFGPU_MERGE_WINDOW")) p.window_records = strtoull(e, 0, 10);
+  jfgpu_merge* m = nullptr;
+  if(jfgpu_merge_create(&p, &m)) { why = jfgpu_last_error(); return false; }
+  merge_sink_state sink{&out, kb + out_counter_len};
+  const int rc = jfgpu_merge_run(m, bodies.data(), n_records.data(), merge_sink_write, &sink);
+  if(rc) {
+    why = jfgpu_last_error();
+    jfgpu_merge_destroy(m);
+    if(sink.called) throw MergeError("Merging on the device failed: " + why);
+    return false;
+  }
+  if(op == 3) {
+    uint64_t t[4];
+    jfgpu_merge_tallies(m, t);
+    out << "Jaccard  " << (double)t[0] / (double)t[2] << '\n' << "wJaccard " << (double)t[1] / (double)t[3] << '\n';
+  }
+  jfgpu_merge_counts(m, counts);
+  jfgpu_merge_last_ms(m, ms);
+  jfgpu_merge_destroy(m);
+  return true;
 }
 
 // op: 0 sum, 1 min, 2 max, 3 Jaccard
@@ -180,20 +252,45 @@ static void merge_files(const std::vector<std::string>& inputs, const std::strin
   std::ofstream out(out_file, std::ios::binary | std::ios::trunc);
   if(!out.good()) throw MergeError("Can't open out file '" + out_file + "'");
   if(op != 3) out_header.format(format);
+  const bool trace = getenv("JFGPU_MERGE_TRACE") != nullptr;      // one line on stderr: which path merged, and how much
+  uint64_t hc[2] = {0, 0};                                        // the host path's records read and written
+  bool host_ran = true;
   if(format == binary_dumper::format) {
     out_header.counter_len(out_counter_len);
     if(op != 3) out_header.write(out);
-    const unsigned kb = (key_len + 7) / 8;
-    const uint64_t vmax = out_counter_len >= 8 ? ~(uint64_t)0 : (((uint64_t)1 << (8 * out_counter_len)) - 1);
-    do_merge<binary_reader>(files, out, [&](std::ostream& o, const mer_dna& k, uint64_t v) {
-      o.write((const char*)k.data(), kb);                                  // binary_writer::write, binary_dumper.hpp:36-40
-      const uint64_t w = std::min(v, vmax);
-      o.write((const char*)&w, out_counter_len);
-    }, min, max, op);
+    // on the device when there is one (JFGPU_MERGE_HOST=1: never); the host merges when the device path declines or fails
+    // before it has written a record -- the output file is then made again
+    bool merged = false;
+    if(jfgpu_device_count() > 0 && !getenv("JFGPU_MERGE_HOST")) {
+      uint64_t dc[3] = {0, 0, 0}; double ms[4] = {0, 0, 0, 0};
+      std::string why;
+      merged = merge_on_device(inputs, files, out, key_len, size, matrix, out_counter_len, min, max, op, dc, ms, why);
+      if(merged && trace)
+        std::cerr << "merge: device inputs=" << inputs.size() << " windows=" << dc[0] << " records=" << dc[1] << " written=" << dc[2]
+                  << " upload_ms=" << ms[0] << " kernels_ms=" << ms[1] << " download_ms=" << ms[2] << " sink_ms=" << ms[3] << std::endl;
+      if(!merged) {
+        if(!getenv("JFGPU_QUIET")) std::cerr << "merge: the device path did not run (" << why << "), merging on the host" << std::endl;
+        out.close();
+        out.open(out_file, std::ios::binary | std::ios::trunc);
+        if(!out.good()) throw MergeError("Can't open out file '" + out_file + "'");
+        if(op != 3) out_header.write(out);
+      }
+    }
+    host_ran = !merged;
+    if(!merged) {
+      const unsigned kb = (key_len + 7) / 8;
+      const uint64_t vmax = out_counter_len >= 8 ? ~(uint64_t)0 : (((uint64_t)1 << (8 * out_counter_len)) - 1);
+      do_merge<binary_reader>(files, out, [&](std::ostream& o, const mer_dna& k, uint64_t v) {
+        o.write((const char*)k.data(), kb);                                  // binary_writer::write, binary_dumper.hpp:36-40
+        const uint64_t w = std::min(v, vmax);
+        o.write((const char*)&w, out_counter_len);
+      }, min, max, op, hc);
+    }
   } else if(format == text_dumper::format) {
     if(op != 3) out_header.write(out);
-    do_merge<text_reader>(files, out, [&](std::ostream& o, const mer_dna& k, uint64_t v) { o << k << ' ' << v << '\n'; }, min, max, op);
+    do_merge<text_reader>(files, out, [&](std::ostream& o, const mer_dna& k, uint64_t v) { o << k << ' ' << v << '\n'; }, min, max, op, hc);
   } else throw MergeError("Unknown format '" + format + "'");
+  if(trace && host_ran) std::cerr << "merge: host inputs=" << inputs.size() << " windows=0 records=" << hc[0] << " written=" << hc[1] << std::endl;
   out.close();
 }
 
@@ -646,6 +743,7 @@ int count_main(int argc, char* argv[]) {
     }
   }
   auto write_start = std::chrono::steady_clock::now();
+  uint64_t ctrs[JFGPU_N_COUNTERS] = {0};
   if(!no_write) {
     try {
       if(dumper->nb_files() == 0) {      // no intermediate files: dump directly into the output file (count_main.cc:348-355)
@@ -657,6 +755,11 @@ int count_main(int argc, char* argv[]) {
         dumper->dump(ary->ary());
         if(!no_merge) {
           const std::vector<std::string> parts = dumper->file_names();
+          if(!comm) {                    // the table has been written out: its memory is the merge's (the windows' buffers)
+            if(!timing.empty() && getenv("JFGPU_TIMING_DETAIL")) (void)jfgpu_get_counters(ary->handle(), ctrs, JFGPU_N_COUNTERS);
+            if(bc) { jfgpu_attach_bloom(ary->handle(), nullptr); jfgpu_bc_destroy(bc); bc = nullptr; }
+            ary.reset();
+          }
           try { merge_files(parts, output, header, lower_given ? lower : 0, upper_given ? upper : std::numeric_limits<uint64_t>::max(), 0); }
           catch(MergeError& e) { die(e.what()); }
           if(!no_unlink) for(const auto& f : parts) unlink(f.c_str());
@@ -665,8 +768,7 @@ int count_main(int argc, char* argv[]) {
     } catch(std::exception& e) { die(e.what()); }
   }
   const double write_s = seconds_since(write_start);
-  uint64_t ctrs[JFGPU_N_COUNTERS] = {0};
-  if(!timing.empty() && getenv("JFGPU_TIMING_DETAIL")) (void)jfgpu_get_counters(ary->handle(), ctrs, JFGPU_N_COUNTERS);
+  if(ary && !timing.empty() && getenv("JFGPU_TIMING_DETAIL")) (void)jfgpu_get_counters(ary->handle(), ctrs, JFGPU_N_COUNTERS);
 
   if(bc) { jfgpu_attach_bloom(ary->handle(), nullptr); jfgpu_bc_destroy(bc); }
   if(comm) {

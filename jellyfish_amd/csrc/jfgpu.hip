@@ -10,6 +10,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <chrono>
 #include <memory>
 #include <string>
 #include <type_traits>
@@ -29,6 +30,7 @@
 #include "kernels_nword.hip.hpp"
 #include "kernels_parse.hip.hpp"
 #include "kernels_bgzf.hip.hpp"
+#include "kernels_merge.hip.hpp"
 
 using namespace jfgpu;
 
@@ -1510,3 +1512,4 @@ int jfgpu_memcpy_d2h(jfgpu_table* t, void* dst, const void* d_src, size_t bytes)
 #include "abi_parser.inl"
 #include "abi_sam.inl"
 #include "abi_comm.inl"
+#include "abi_merge.inl"

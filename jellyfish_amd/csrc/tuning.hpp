@@ -20,6 +20,15 @@ namespace jfgpu {
 // not cut (a step is one piece unless the shards grow).
 constexpr uint64_t kCommNWordPieceBytes = 1ull << 30;
 
+// merge on the device (abi_merge.inl): records of all inputs in one window of positions when the caller names no size.
+// From profiles/merge_bench.txt (312 M records of k = 21, three inputs, one run a size): 10^6 0.90 s, 4 * 10^6 0.96 s, 2^23
+// 0.97 - 1.52 s over four runs, 16 * 10^6 1.11 s, 2^25 1.32 s of wall time.  The spread at one size is as large as the
+// difference between the three smallest, so this is the power of two beside the middle one of them: kernel time is flat from 2^22 up (45 - 47 ms
+// against 57 at 2^20), staging and download time grow with the window.  About 220 bytes of device memory a record at the
+// widest key (two raw and two output buffers of 40 bytes, 48 of decoded key, value and position, 12 of rank output):
+// under 1 GB, and four pinned staging buffers of a window's bytes each.
+constexpr uint64_t kMergeWindowRecords = 1ull << 22;
+
 struct Tuning {
   // ---- tables (jfgpu_create)
   int mode = 0;                  // JFGPU_MODE=direct|partitioned            0: not set, 1 direct, 2 partitioned

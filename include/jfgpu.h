@@ -482,6 +482,53 @@ int  jfgpu_merge_last_ms(jfgpu_merge* m, double out4[4]);
 /* The last run's windows, records read and records written. */
 int  jfgpu_merge_counts(jfgpu_merge* m, uint64_t out3[3]);
 
+/* ---- text: binary/sorted records formatted as text on the device ----
+ * Replaces the record loop of dump (sub_commands/dump_main.cc:35-52) and of the text dumper (text_dumper.hpp:18-20): the
+ * records whose count lies in [lower, upper], in input order, as
+ *   column  KMER<separator>COUNT\n        FASTA  >COUNT\nKMER\n
+ * KMER as mer_dna::to_str (bits of the top key byte above 2k are ignored), COUNT the decimal uint64.  The bytes are those
+ * the host loops write. */
+#define JFGPU_TEXT_COLUMN 0
+#define JFGPU_TEXT_FASTA 1
+typedef struct jfgpu_text jfgpu_text;
+typedef struct jfgpu_text_params {
+  uint32_t k;                     /* mer length, 1..128: keys of (2k+7)/8 bytes */
+  uint32_t counter_len;           /* bytes of a count in the records, 1..8 */
+  uint32_t layout;                /* JFGPU_TEXT_COLUMN or JFGPU_TEXT_FASTA */
+  uint32_t separator;             /* ' ' or '\t' (column layout) */
+  uint64_t lower, upper;          /* records whose count is outside are dropped */
+  int32_t  device;                /* HIP device ordinal, -1 = current device */
+  uint32_t reserved;
+  uint64_t window_records;        /* records formatted in one go by jfgpu_text_run; 0 = the engine's default */
+} jfgpu_text_params;
+/* Receives the text of n_records kept records (n_bytes bytes, whole lines), in order; the bytes are the engine's until it
+ * returns.  Non-zero stops the run. */
+typedef int (*jfgpu_text_sink)(void* user, const char* text, uint64_t n_bytes, uint64_t n_records);
+int  jfgpu_text_create(const jfgpu_text_params* p, jfgpu_text** out);
+void jfgpu_text_destroy(jfgpu_text* x);
+/* The longest line these parameters can produce: k + 2 + digits (+ 1 for FASTA), digits those of the largest count that
+ * counter_len bytes hold and upper lets through. */
+int  jfgpu_text_line_max(const jfgpu_text* x, uint32_t* bytes);
+/* body: host memory at any alignment (the mmap of a file past its header) holding n_records records.  Windows of
+ * window_records records: window i + 1 is staged and uploaded while the kernels of window i run and the text of window
+ * i - 1 comes down and goes to the sink.  A window that keeps nothing does not reach the sink. */
+int  jfgpu_text_run(jfgpu_text* x, const void* body, uint64_t n_records, jfgpu_text_sink sink, void* user);
+/* Device to device: d_records on a 16-byte boundary and readable up to the next one behind its last record, d_text at any
+ * alignment.  *n_bytes / *n_kept: the text's bytes and lines.  JFGPU_E_INVALID, with nothing written to d_text and
+ * *n_bytes the bytes needed, when they exceed capacity_bytes. */
+int  jfgpu_text_format_dev(jfgpu_text* x, const void* d_records, uint64_t n_records, char* d_text, uint64_t capacity_bytes,
+                           uint64_t* n_bytes, uint64_t* n_kept);
+/* Milliseconds of the last run: upload (staging + host-to-device copies), kernels (HIP events), download, sink. */
+int  jfgpu_text_last_ms(jfgpu_text* x, double out4[4]);
+/* The last run's windows, records read, records kept and bytes written. */
+int  jfgpu_text_counts(jfgpu_text* x, uint64_t out4[4]);
+/* jfgpu_dump_next with the formatter between the device-sorted chunk and the copy to the host: the text of as many whole
+ * tiles as fit capacity_bytes at jfgpu_text_line_max bytes a record (capacity_bytes must hold one tile) goes to out (host
+ * memory); *n_records, the records of the chunk, is 0 at the end.  The table's own [lower, upper] was applied by
+ * jfgpu_dump_begin; x's applies to the chunk as well (leave it at [0, 2^64 - 1] to write every record).  x's k and
+ * counter_len must be the table's k and out_counter_len and both must live on one device: JFGPU_E_INVALID otherwise. */
+int  jfgpu_dump_next_text(jfgpu_table* t, jfgpu_text* x, char* out, uint64_t capacity_bytes, uint64_t* n_records, uint64_t* n_bytes);
+
 /* ---- measurement helpers (bench.py; not part of the reference surface) -- */
 /* Per-kernel HIP-event timing on the table's stream.  which: 0 count (direct), 1 add_keys,
  * 2 shard partition, 3 lookup, 4 P1 partition, 5 P2 partition, 6 tile insert, 7 items-direct.  Returns accumulated milliseconds and launches since the

@@ -57,6 +57,16 @@ class MergeParams(C.Structure):
 
 
 MERGE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
+
+
+class TextParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("counter_len", C.c_uint32), ("layout", C.c_uint32), ("separator", C.c_uint32),
+                ("lower", C.c_uint64), ("upper", C.c_uint64), ("device", C.c_int32), ("reserved", C.c_uint32),
+                ("window_records", C.c_uint64)]
+
+
+TEXT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64)
+TEXT_COLUMN, TEXT_FASTA = 0, 1
 MERGE_SUM, MERGE_MIN, MERGE_MAX, MERGE_JACCARD = range(4)
 
 
@@ -149,6 +159,14 @@ SIGNATURES = {
     "jfgpu_merge_tallies": (C.c_int, [_P, _P]),
     "jfgpu_merge_last_ms": (C.c_int, [_P, _P]),
     "jfgpu_merge_counts": (C.c_int, [_P, _P]),
+    "jfgpu_text_create": (C.c_int, [C.POINTER(TextParams), C.POINTER(_P)]),
+    "jfgpu_text_destroy": (None, [_P]),
+    "jfgpu_text_line_max": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "jfgpu_text_run": (C.c_int, [_P, _P, C.c_uint64, TEXT_SINK, _P]),
+    "jfgpu_text_format_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "jfgpu_text_last_ms": (C.c_int, [_P, _P]),
+    "jfgpu_text_counts": (C.c_int, [_P, _P]),
+    "jfgpu_dump_next_text": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "jfgpu_set_growth": (C.c_int, [_P, C.c_int]),
     "jfgpu_reference_matrix": (C.c_int, [C.c_uint32, C.c_uint32, _P]),
     "jfgpu_table_bytes": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -402,6 +420,23 @@ class Table:
             return out
         finally:
             _check(self._lib.jfgpu_dump_end(self._h))
+
+    def dump_begin(self, lower=0, upper=2 ** 64 - 1):
+        """jfgpu_dump_begin: (records, record bytes) of the sorted dump that dump_next_text walks; end it with dump_end()."""
+        n, rb = C.c_uint64(), C.c_uint32()
+        _check(self._lib.jfgpu_dump_begin(self._h, lower, upper, C.byref(n), C.byref(rb)))
+        return n.value, rb.value
+
+    def dump_end(self):
+        _check(self._lib.jfgpu_dump_end(self._h))
+
+    def dump_next_text(self, text, capacity_bytes):
+        """jfgpu_dump_next_text: the next chunk of the sorted dump as text, formatted by `text` (a Text).  Returns
+        (records of the chunk, their text as bytes); (0, b"") at the end."""
+        buf = np.empty(max(1, capacity_bytes), dtype=np.uint8)
+        nr, nb = C.c_uint64(), C.c_uint64()
+        _check(self._lib.jfgpu_dump_next_text(self._h, text._h, buf.ctypes.data, capacity_bytes, C.byref(nr), C.byref(nb)))
+        return nr.value, buf[:nb.value].tobytes()
 
     def attach_bloom(self, bloom):
         """count --bc: admit only k-mers the Bloom counter has seen at least twice (None detaches)."""
@@ -769,6 +804,77 @@ class Merge:
         """(windows, records read, records written) of the last run."""
         out = np.zeros(3, dtype=np.uint64)
         _check(self._lib.jfgpu_merge_counts(self._h, out.ctypes.data))
+        return tuple(int(x) for x in out)
+
+
+class Text:
+    """binary/sorted records formatted as text on the device (jfgpu_text_*): "KMER<separator>COUNT\n" lines (TEXT_COLUMN) or
+    ">COUNT\nKMER\n" (TEXT_FASTA) of the records whose count lies in [lower, upper]."""
+
+    def __init__(self, k, counter_len, layout=TEXT_COLUMN, separator=" ", lower=0, upper=2 ** 64 - 1, device=-1, window_records=0):
+        self._lib = load()
+        self.k, self.kb, self.counter_len = k, (2 * k + 7) // 8, counter_len
+        p = TextParams(k=k, counter_len=counter_len, layout=layout, separator=ord(separator) if isinstance(separator, str) else separator,
+                       lower=lower, upper=upper, device=device, reserved=0, window_records=window_records)
+        h = _P()
+        _check(self._lib.jfgpu_text_create(C.byref(p), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.jfgpu_text_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def line_max(self):
+        out = C.c_uint32()
+        _check(self._lib.jfgpu_text_line_max(self._h, C.byref(out)))
+        return out.value
+
+    def run(self, body, sink=None):
+        """body: a uint8 array of whole records.  Returns the text as bytes.  sink(text: bytes, n_records) -> int, when given,
+        sees every chunk first; a non-zero answer stops the run (JfgpuError)."""
+        body = np.ascontiguousarray(body, dtype=np.uint8).reshape(-1)
+        n = len(body) // (self.kb + self.counter_len)
+        chunks = []
+
+        def on_chunk(_user, text, n_bytes, n_records):
+            data = C.string_at(text, int(n_bytes))
+            if sink is not None:
+                rc = sink(data, int(n_records))
+                if rc:
+                    return int(rc)
+            chunks.append(data)
+            return 0
+
+        cb = TEXT_SINK(on_chunk)
+        _check(self._lib.jfgpu_text_run(self._h, body.ctypes.data if n else None, n, cb, None))
+        return b"".join(chunks)
+
+    def format_dev(self, d_records, n_records, d_text, capacity_bytes):
+        """Device to device (pointers as _ptr takes them).  Returns (bytes, lines); JfgpuError when capacity_bytes is short."""
+        nb, nk = C.c_uint64(), C.c_uint64()
+        _check(self._lib.jfgpu_text_format_dev(self._h, _ptr(d_records), n_records, _ptr(d_text), capacity_bytes, C.byref(nb), C.byref(nk)))
+        return nb.value, nk.value
+
+    def last_ms(self):
+        """(upload, kernels, download, sink) milliseconds of the last run."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(self._lib.jfgpu_text_last_ms(self._h, out.ctypes.data))
+        return tuple(float(x) for x in out)
+
+    def counts(self):
+        """(windows, records read, records kept, bytes written) of the last run."""
+        out = np.zeros(4, dtype=np.uint64)
+        _check(self._lib.jfgpu_text_counts(self._h, out.ctypes.data))
         return tuple(int(x) for x in out)
 
 

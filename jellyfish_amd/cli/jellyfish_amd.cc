@@ -9,8 +9,9 @@
 //   info   sub_commands/info_main.cc:31-54
 // Dispatch like sub_commands/jellyfish.cc:138-158.  The option parsers are written by hand
 // (the reference generates them with yaggo); names, defaults and output text follow the
-// reference so scripts keep working.  dump/histo/stats/query/info are plain sequential file
-// readers (I/O bound, host only); count drives the GPU through the hash_counter facade.
+// reference so scripts keep working.  histo/stats/info are plain sequential file readers (I/O
+// bound, host only); count drives the GPU through the hash_counter facade; merge, query -s and
+// dump hand binary/sorted files to the device and keep their host loops as the fallback.
 #include <algorithm>
 #include <cerrno>
 #include <chrono>
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include <jellyfish_amd/dumpers.hpp>
+#include "../csrc/tuning.hpp"                                   // kDumpDeviceMinRecords
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -912,6 +914,67 @@ int bc_main(int argc, char* argv[]) {
   return 0;
 }
 
+// ---------------------------------------------------------------- dump  (sub_commands/dump_main.cc:35-88)
+// binary/sorted files are formatted on the device: the file's body, mapped, goes to jfgpu_text_run and the text comes back
+// through a sink that appends it to the output.  The record loop on this thread is the path of text/sorted files, of
+// JFGPU_DUMP_HOST=1, of a machine without a device, of files with fewer than JFGPU_DUMP_DEVICE_MIN records (the record
+// count is compared before anything asks for a device: a small dump never opens one) and the fallback when the device
+// path fails before it has written anything; a failure after that is an error.
+struct dump_sink_state { std::ostream* out; bool called = false; };
+static int dump_sink_write(void* user, const char* text, uint64_t n_bytes, uint64_t) {
+  dump_sink_state* s = (dump_sink_state*)user;
+  s->called = true;
+  s->out->write(text, (std::streamsize)n_bytes);
+  return s->out->good() ? 0 : 1;
+}
+// false, with the reason in `why` (empty: the device path was not meant to run), when nothing was written
+static bool dump_on_device(const std::string& path, db_file& f, std::ostream& out, bool column, bool tab, uint64_t lower, uint64_t upper, bool trace,
+                           std::string& why) {
+  const unsigned key_len = f.header.key_len(), kb = (key_len + 7) / 8, counter_len = f.header.counter_len();
+  if(key_len < 2 || key_len > 256 || (key_len & 1) || counter_len < 1 || counter_len > 8) { why = "a key or counter length the device path does not take"; return false; }
+  const std::streamoff body = f.is.tellg();                          // the header has been read: the records start here
+  struct stat st;
+  const int fd = open(path.c_str(), O_RDONLY);
+  if(fd < 0 || body < 0 || fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { if(fd >= 0) close(fd); why = "cannot map '" + path + "'"; return false; }
+  const uint64_t n_records = (uint64_t)st.st_size > (uint64_t)body ? ((uint64_t)st.st_size - (uint64_t)body) / (kb + counter_len) : 0;   // a cut last record is not one (binary_reader::next)
+  uint64_t device_min = jfgpu::kDumpDeviceMinRecords;
+  if(const char* e = getenv("JFGPU_DUMP_DEVICE_MIN")) device_min = strtoull(e, 0, 10);
+  if(n_records < device_min || jfgpu_device_count() <= 0) { close(fd); return false; }
+  mapped_input map;
+  const void* records = nullptr;
+  if(n_records) {
+    map.len = (size_t)st.st_size;
+    map.base = mmap(nullptr, map.len, PROT_READ, MAP_PRIVATE, fd, 0);
+    if(map.base == MAP_FAILED) { close(fd); why = "cannot map '" + path + "'"; return false; }
+    records = (const char*)map.base + body;
+  }
+  close(fd);
+  jfgpu_text_params p;
+  memset(&p, 0, sizeof p);
+  p.k = key_len / 2; p.counter_len = counter_len; p.layout = column ? JFGPU_TEXT_COLUMN : JFGPU_TEXT_FASTA; p.separator = tab ? '\t' : ' ';
+  p.lower = lower; p.upper = upper; p.device = -1;
+  if(const char* e = getenv("JFGPU_TEXT_WINDOW")) p.window_records = strtoull(e, 0, 10);
+  jfgpu_text* x = nullptr;
+  if(jfgpu_text_create(&p, &x)) { why = jfgpu_last_error(); return false; }
+  dump_sink_state sink{&out};
+  const int rc = jfgpu_text_run(x, records, n_records, dump_sink_write, &sink);
+  if(rc) {
+    why = jfgpu_last_error();
+    jfgpu_text_destroy(x);
+    if(sink.called) die("Dumping on the device failed: " + why);
+    return false;
+  }
+  if(trace) {
+    uint64_t c[4] = {0, 0, 0, 0}; double ms[4] = {0, 0, 0, 0};
+    jfgpu_text_counts(x, c);
+    jfgpu_text_last_ms(x, ms);
+    std::cerr << "dump: device records=" << c[1] << " kept=" << c[2] << " bytes=" << c[3] << " windows=" << c[0] << " upload_ms=" << ms[0]
+              << " kernels_ms=" << ms[1] << " download_ms=" << ms[2] << " sink_ms=" << ms[3] << std::endl;
+  }
+  jfgpu_text_destroy(x);
+  return true;
+}
+
 int dump_main(int argc, char* argv[]) {
   bool column = false, tab = false;
   uint64_t lower = 0, upper = std::numeric_limits<uint64_t>::max();
@@ -932,12 +995,22 @@ int dump_main(int argc, char* argv[]) {
   if(!output.empty()) { fout.open(output); if(!fout.good()) die("Error opening output file '" + output + "'"); }
   std::ostream& out = output.empty() ? std::cout : fout;
   db_file f(db);
+  const bool trace = getenv("JFGPU_DUMP_TRACE") != nullptr;        // one line on stderr: which path dumped, and how much
+  if(f.header.format() == binary_dumper::format && !getenv("JFGPU_DUMP_HOST")) {
+    std::string why;
+    if(dump_on_device(db, f, out, column, tab, lower, upper, trace, why)) return 0;
+    if(!why.empty() && !getenv("JFGPU_QUIET")) std::cerr << "dump: the device path did not run (" << why << "), dumping on the host" << std::endl;
+  }
   const char spacer = tab ? '\t' : ' ';
+  uint64_t records = 0, kept = 0;
   for_each_record(f, [&](const mer_dna& k, uint64_t v) {
+    ++records;
     if(v < lower || v > upper) return;
+    ++kept;
     if(column) out << k << spacer << v << "\n";
     else out << ">" << v << "\n" << k << "\n";
   });
+  if(trace) std::cerr << "dump: host records=" << records << " kept=" << kept << std::endl;
   return 0;
 }
 

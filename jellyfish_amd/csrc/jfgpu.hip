@@ -31,6 +31,7 @@
 #include "kernels_parse.hip.hpp"
 #include "kernels_bgzf.hip.hpp"
 #include "kernels_merge.hip.hpp"
+#include "kernels_text.hip.hpp"
 
 using namespace jfgpu;
 
@@ -1236,10 +1237,15 @@ int jfgpu_dump_begin(jfgpu_table* t, uint64_t lower, uint64_t upper, uint64_t* n
   return JFGPU_OK;
 }
 
-int jfgpu_dump_next(jfgpu_table* t, void* out, uint64_t capacity_records, uint64_t* n_read) {
-  int rc = use(t); if(rc) return rc;
+}  // extern "C"
+
+namespace {
+
+// The next chunk of the sorted dump -- as many whole tiles as hold at most capacity_records records -- into t->d_dump,
+// enqueued on the table's stream (jfgpu_dump_next copies it to the host, jfgpu_dump_next_text formats it first).
+// *n_read = 0 at the end.
+int dump_next_chunk(jfgpu_table* t, uint64_t capacity_records, uint64_t* n_read) {
   if(!t->dump_open) return fail(JFGPU_E_INVALID, "jfgpu_dump_begin not called");
-  if(!out || !n_read) return fail(JFGPU_E_INVALID, "null argument");
   *n_read = 0;
   const uint64_t nt = n_tiles_of(t);
   const uint64_t tsz = 1ull << t->g.tile_bits;
@@ -1256,7 +1262,7 @@ int jfgpu_dump_next(jfgpu_table* t, void* out, uint64_t capacity_records, uint64
   if(t->dump_cap_records < nrec) {
     if(t->d_dump) hipFree(t->d_dump);
     t->d_dump = nullptr; t->dump_cap_records = 0;
-    HIP_TRY(hipMalloc((void**)&t->d_dump, std::max<uint64_t>(nrec, capacity_records) * rec));
+    HIP_TRY(hipMalloc((void**)&t->d_dump, std::max<uint64_t>(nrec, capacity_records) * rec + 64));   // (the text kernels read to the next 16-byte boundary)
     t->dump_cap_records = std::max<uint64_t>(nrec, capacity_records);
   }
   if(t->tile_off_cap < ntile) {
@@ -1270,10 +1276,25 @@ int jfgpu_dump_next(jfgpu_table* t, void* out, uint64_t capacity_records, uint64
   HIP_TRY(hipMemcpyAsync(t->d_tile_off, offs.data(), ntile * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
   with_view(t, [&](const auto& T) { launch_dump(t, T, t0, ntile, key_bytes); });
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, t->d_dump, nrec * rec, hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
   t->dump_tile_cursor = t1;
   *n_read = nrec;
+  return JFGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jfgpu_dump_next(jfgpu_table* t, void* out, uint64_t capacity_records, uint64_t* n_read) {
+  int rc = use(t); if(rc) return rc;
+  if(!out || !n_read) return fail(JFGPU_E_INVALID, "null argument");
+  if(!t->dump_open) return fail(JFGPU_E_INVALID, "jfgpu_dump_begin not called");
+  const uint64_t cursor = t->dump_tile_cursor;
+  rc = dump_next_chunk(t, capacity_records, n_read); if(rc) return rc;
+  const uint32_t rec = (t->g.key_bits + 7) / 8 + t->out_counter_len;
+  hipError_t e = *n_read ? hipMemcpyAsync(out, t->d_dump, *n_read * rec, hipMemcpyDeviceToHost, t->stream) : hipSuccess;
+  if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  if(e != hipSuccess) { t->dump_tile_cursor = cursor; *n_read = 0; return fail(JFGPU_E_HIP, hipGetErrorString(e)); }   // (the chunk was not delivered)
   return JFGPU_OK;
 }
 
@@ -1513,3 +1534,4 @@ int jfgpu_memcpy_d2h(jfgpu_table* t, void* dst, const void* d_src, size_t bytes)
 #include "abi_sam.inl"
 #include "abi_comm.inl"
 #include "abi_merge.inl"
+#include "abi_text.inl"

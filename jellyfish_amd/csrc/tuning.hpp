@@ -29,6 +29,22 @@ constexpr uint64_t kCommNWordPieceBytes = 1ull << 30;
 // under 1 GB, and four pinned staging buffers of a window's bytes each.
 constexpr uint64_t kMergeWindowRecords = 1ull << 22;
 
+// dump / count --text on the device (abi_text.inl): records formatted in one window when the caller names no size
+// (JFGPU_TEXT_WINDOW from the CLI).  From profiles/dump_bench.txt (104 M records of k = 21, dump -c to a file on local
+// scratch, one run a size): 2^18 0.70 s, 2^20 0.68 s, 2^22 0.69 s, 2^24 0.97 s, 2^26 2.08 s of wall time, against 0.71 - 1.25 s
+// over three runs at 2^22: flat from 2^18 to 2^22, so the three cannot be told apart by time.  Above that the pinned output
+// buffers, allocated inside the run, cost more than longer windows save (download 62 / 69 / 101 / 201 / 583 ms); kernel
+// time is 12 - 29 ms at every size.  So the middle of the flat three: two pinned buffers of 2^20 lines (at most 151 bytes a
+// line: 158 MB each at k = 128, 35 MB at k = 21) and as much again on the device, a quarter of what 2^22 takes.
+constexpr uint64_t kTextWindowRecords = 1ull << 20;
+
+// `dump` (jellyfish_amd/cli/jellyfish_amd.cc, which includes this header for it): files with fewer records than this are
+// formatted by the host loop (JFGPU_DUMP_DEVICE_MIN overrides).  The smallest power of two in the sweep of
+// profiles/dump_bench.txt from which the device path's wall time -- process start and HIP initialisation, 0.25 - 0.3 s,
+// included -- is not above the host loop's, medians of three: 2^21 0.33 s against 0.18 s, 2^22 0.36 against 0.34,
+// 2^23 0.43 against 0.66, 2^24 0.52 against 1.32 (the host loop formats 12 - 14 M records a second).
+constexpr uint64_t kDumpDeviceMinRecords = 1ull << 23;
+
 struct Tuning {
   // ---- tables (jfgpu_create)
   int mode = 0;                  // JFGPU_MODE=direct|partitioned            0: not set, 1 direct, 2 partitioned

@@ -185,30 +185,72 @@ private:
   int val_len_, key_len_;
 };
 
-inline void write_text_records(hash_counter* ary, uint64_t min, uint64_t max, std::ostream& out) {
-  uint64_t n = 0; uint32_t rec = 0;
-  jf_check(jfgpu_dump_begin(ary->handle(), min, max, &n, &rec));
+// The "KMER count\n" lines of the table's records in (pos, key) order (text_dumper.hpp:18-20).  The device sorts the records
+// tile by tile and formats them (jfgpu_dump_next_text): the text comes down into two pinned buffers, one being written to the
+// stream while the device produces the next.  JFGPU_DUMP_HOST=1 (or a formatter that cannot be created): the records come
+// down instead (jfgpu_dump_next) and this thread formats them one at a time.
+inline void write_text_records_host(hash_counter* ary, uint32_t rec, std::ostream& out) {
   const uint64_t cap = std::max<uint64_t>((uint64_t)1 << 20, ary->info().tile_slots);
   std::vector<unsigned char> buf(cap * rec);
   const unsigned k = ary->info().k, kb = (2 * k + 7) / 8, vb = rec - kb;
   mer_dna m(k);
   std::string line;
-  try {
-    while(true) {
-      uint64_t got = 0;
-      jf_check(jfgpu_dump_next(ary->handle(), buf.data(), cap, &got));
-      if(!got) break;
-      line.clear();
-      for(uint64_t i = 0; i < got; ++i) {
-        const unsigned char* r = &buf[i * rec];
-        uint64_t val = 0;
-        memset(m.data__(), 0, m.nb_words() * sizeof(uint64_t));
-        memcpy(m.data__(), r, kb); memcpy(&val, r + kb, vb);
-        line += m.to_str(); line += ' '; line += std::to_string(val); line += '\n';
-      }
-      out.write(line.data(), line.size());
+  while(true) {
+    uint64_t got = 0;
+    jf_check(jfgpu_dump_next(ary->handle(), buf.data(), cap, &got));
+    if(!got) break;
+    line.clear();
+    for(uint64_t i = 0; i < got; ++i) {
+      const unsigned char* r = &buf[i * rec];
+      uint64_t val = 0;
+      memset(m.data__(), 0, m.nb_words() * sizeof(uint64_t));
+      memcpy(m.data__(), r, kb); memcpy(&val, r + kb, vb);
+      line += m.to_str(); line += ' '; line += std::to_string(val); line += '\n';
     }
-  } catch(...) { jfgpu_dump_end(ary->handle()); throw; }
+    out.write(line.data(), line.size());
+  }
+}
+
+inline void write_text_records_device(hash_counter* ary, jfgpu_text* x, std::ostream& out) {
+  uint32_t line_max = 0;
+  jf_check(jfgpu_text_line_max(x, &line_max));
+  const uint64_t cap = std::max<uint64_t>((uint64_t)1 << 20, ary->info().tile_slots) * line_max;
+  struct pinned {
+    char* p = nullptr; std::vector<char> fallback;
+    explicit pinned(size_t n) { void* q = nullptr; if(jfgpu_malloc_host(n, &q) == JFGPU_OK) p = (char*)q; else { fallback.resize(n); p = fallback.data(); } }
+    ~pinned() { if(fallback.empty()) jfgpu_free_host(p); }
+  } bufs[2] = {pinned(cap), pinned(cap)};
+  std::future<void> writing;                                   // the chunk before this one, on its way into the stream
+  try {
+    for(int b = 0;; b ^= 1) {
+      uint64_t nrec = 0, nbytes = 0;
+      jf_check(jfgpu_dump_next_text(ary->handle(), x, bufs[b].p, cap, &nrec, &nbytes));
+      if(writing.valid()) writing.get();                       // (chunks enter the stream in order; bufs[b ^ 1] is free again)
+      if(!nrec) break;
+      const char* src = bufs[b].p;
+      writing = std::async(std::launch::async, [&out, src, nbytes]() { out.write(src, (std::streamsize)nbytes); });
+    }
+  } catch(...) { if(writing.valid()) writing.wait(); throw; }
+}
+
+inline void write_text_records(hash_counter* ary, uint64_t min, uint64_t max, std::ostream& out) {
+  uint64_t n = 0; uint32_t rec = 0;
+  jf_check(jfgpu_dump_begin(ary->handle(), min, max, &n, &rec));
+  jfgpu_text* x = nullptr;
+  if(!getenv("JFGPU_DUMP_HOST")) {
+    jfgpu_text_params p;
+    memset(&p, 0, sizeof p);
+    p.k = ary->info().k; p.counter_len = rec - (2 * p.k + 7) / 8; p.layout = JFGPU_TEXT_COLUMN; p.separator = ' ';
+    p.lower = 0; p.upper = ~(uint64_t)0;                       // (jfgpu_dump_begin applied min and max)
+    p.device = -1;                                             // the table's: jfgpu_dump_begin made it current
+    if(jfgpu_text_create(&p, &x) != JFGPU_OK) x = nullptr;
+  }
+  if(getenv("JFGPU_DUMP_TRACE")) std::cerr << "[dump] text: " << n << " records formatted on the " << (x ? "device" : "host") << "\n";
+  try {
+    if(x) write_text_records_device(ary, x, out);
+    else write_text_records_host(ary, rec, out);
+  } catch(...) { jfgpu_text_destroy(x); jfgpu_dump_end(ary->handle()); throw; }
+  jfgpu_text_destroy(x);
   jf_check(jfgpu_dump_end(ary->handle()));
 }
 

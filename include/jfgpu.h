@@ -445,6 +445,18 @@ int  jfgpu_parser_stream_consume(jfgpu_parser* p, size_t n);
  * JFGPU_E_CORRUPT: a record whose lengths do not add up. */
 int  jfgpu_parser_bam_decode(jfgpu_parser* p, size_t skip, int32_t n_ref, const char** d_out, size_t* n_out,
                              uint64_t* n_records, size_t* n_left);
+/* bgzip-compressed FASTA / FASTQ: the inflated stream is text, and it exists only on the device, so the cut into
+ * chunks is made there.  *cut = the length of the longest prefix of the stream that jfgpu_parser_parse_dev takes as a
+ * chunk of fmt (JFGPU_PARSE_FASTA: up to and including the last '\n'; JFGPU_PARSE_FASTQ: up to the last line that
+ * starts with '@' and whose second-next line starts with '+'), 0 when there is none: inflate more, or -- at the end
+ * of the file -- parse the whole stream. */
+int  jfgpu_parser_stream_cut(jfgpu_parser* p, unsigned fmt, size_t* cut);
+/* jfgpu_parser_parse_dev over the first n bytes of the inflated stream (n <= 2^31; same flags, JFGPU_PARSE_CONTINUE
+ * included, same lifetime of *d_out, same quality mask), which are then dropped from it; *n_left = what stays.
+ * JFGPU_E_FORMAT: nothing was produced and nothing dropped -- read the bytes back (jfgpu_parser_stream_read) for the
+ * host parser. */
+int  jfgpu_parser_stream_parse(jfgpu_parser* p, size_t n, unsigned flags, const char** d_out, size_t* n_out,
+                               uint64_t* n_records, size_t* n_left);
 
 /* ---- merge: k-way merge of sorted databases on the device ----
  * Replaces the heap loop of merge_files (jellyfish/merge_files.cc:36-176, driven by sub_commands/merge_main.cc) for

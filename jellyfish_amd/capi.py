@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("JFGPU_LIB") or os.path.join(_HERE, "lib", "libjfgpu.s
 
 OK, E_INVALID, E_NO_DEVICE, E_ALLOC, E_FULL, E_HIP, E_UNSUPPORTED, E_FORMAT, E_CORRUPT = range(9)
 PARSE_FASTA, PARSE_FASTQ, PARSE_CONTINUE = 1, 2, 4
+STREAM_CUT_TILE = 4096          # bytes stream_cut_kernel looks at per round (kCutTile, kernels_stream.hip.hpp)
 Q_MER, Q_FOUND, Q_REVCOMP = 1, 2, 4                          # include/jfgpu.h: JFGPU_Q_*, the flags of query_ascii
 
 
@@ -153,6 +154,9 @@ SIGNATURES = {
     "jfgpu_parser_stream_consume": (C.c_int, [_P, C.c_size_t]),
     "jfgpu_parser_bam_decode": (C.c_int, [_P, C.c_size_t, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_size_t)]),
+    "jfgpu_parser_stream_cut": (C.c_int, [_P, C.c_uint, C.POINTER(C.c_size_t)]),
+    "jfgpu_parser_stream_parse": (C.c_int, [_P, C.c_size_t, C.c_uint, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_size_t)]),
     "jfgpu_merge_create": (C.c_int, [C.POINTER(MergeParams), C.POINTER(_P)]),
     "jfgpu_merge_destroy": (None, [_P]),
     "jfgpu_merge_run": (C.c_int, [_P, _P, _P, MERGE_SINK, _P]),
@@ -945,6 +949,19 @@ class Parser:
         """-> (device pointer, length) of the contract buffer, records, bytes left in the stream."""
         out, n_out, recs, left = _P(), C.c_size_t(), C.c_uint64(), C.c_size_t()
         _check(self._lib.jfgpu_parser_bam_decode(self._h, skip, n_ref, C.byref(out), C.byref(n_out), C.byref(recs), C.byref(left)))
+        self.records = recs.value
+        return (out.value or 0), n_out.value, recs.value, left.value
+
+    def stream_cut(self, fmt):
+        """Length of the longest prefix of the inflated stream that is a chunk of fmt (PARSE_FASTA / PARSE_FASTQ); 0: none."""
+        cut = C.c_size_t()
+        _check(self._lib.jfgpu_parser_stream_cut(self._h, fmt, C.byref(cut)))
+        return cut.value
+
+    def stream_parse(self, n, flags):
+        """Parse and drop the first n bytes of the inflated stream -> (device pointer, length), records, bytes left."""
+        out, n_out, recs, left = _P(), C.c_size_t(), C.c_uint64(), C.c_size_t()
+        _check(self._lib.jfgpu_parser_stream_parse(self._h, n, flags, C.byref(out), C.byref(n_out), C.byref(recs), C.byref(left)))
         self.records = recs.value
         return (out.value or 0), n_out.value, recs.value, left.value
 

@@ -513,7 +513,8 @@ int count_main(int argc, char* argv[]) {
     else if(a.is("", "--sam")) sam_files.push_back(a.value("", "--sam"));   // BAM / SAM, read after the files and -g (stream_manager.hpp:132-180)
     else if(a.cur() == "-h" || a.cur() == "--help") {
       std::cout << "Usage: jellyfish-amd count [options] file:path+\n\n"
-                   "Count k-mers in fasta or fastq files on an MI355X\n\n"
+                   "Count k-mers in fasta or fastq files on an MI355X.  bgzip-compressed (BGZF) fasta / fastq files are read too,\n"
+                   "inflated and cut on the device; plain gzip is not (recompress with bgzip, or use -g with zcat)\n\n"
                    " -m, --mer-len=uint32       *Length of mer\n"
                    " -s, --size=uint64          *Initial hash size\n"
                    " -t, --threads=uint32        Number of threads (1)\n"
@@ -651,8 +652,23 @@ int count_main(int argc, char* argv[]) {
   std::unique_ptr<sam_parser> sam_feed;
   {
     uint64_t total = 0, largest = 0;
-    for(const auto& f : files) { struct stat st; if(stat(f.c_str(), &st) == 0 && S_ISREG(st.st_mode)) { total += (uint64_t)st.st_size; largest = std::max<uint64_t>(largest, st.st_size); } }
+    // (a file that starts with 1f 8b is compressed: whole files per rank, its sequence taken as twice its size, as below)
+    uint64_t gz_total = 0, gz_largest = 0, n_gz = 0;
+    auto is_gz = [](const std::string& f) {
+      unsigned char m[2] = {0, 0};
+      const int fd = open(f.c_str(), O_RDONLY);
+      const bool gz = fd >= 0 && read(fd, m, 2) == 2 && m[0] == 0x1f && m[1] == 0x8b;
+      if(fd >= 0) close(fd);
+      return gz;
+    };
+    for(const auto& f : files) {
+      struct stat st;
+      if(stat(f.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) continue;
+      if(!host_parse && is_gz(f)) { if(!gpus_given || n_gz++ % gpus == (uint64_t)renv.rank) { gz_total += (uint64_t)st.st_size; gz_largest = std::max<uint64_t>(gz_largest, st.st_size); } continue; }
+      total += (uint64_t)st.st_size; largest = std::max<uint64_t>(largest, st.st_size);
+    }
     if(gpus_given) { total = total / gpus + ((uint64_t)1 << 20); largest = largest / gpus + ((uint64_t)1 << 20); }   // this rank's part
+    total += 2 * gz_total;
     // SAM / BAM files: whole files per rank (file i to rank i mod N); their sequence is taken as up to twice the
     // compressed size (a BAM record's bases are a third of it, BGZF compresses it 2 - 4 times)
     uint64_t sam_total = 0, sam_largest = 0;
@@ -666,7 +682,7 @@ int count_main(int argc, char* argv[]) {
     if(expected > ((uint64_t)64 << 20)) ary->expect_input(std::min<uint64_t>(expected, (uint64_t)12 << 30));
     init_mark("partition workspace reserved");
     if(!host_parse) {
-      try { dev_parser.reset(new device_sequence_parser(mer_len, device)); dev_parser->min_quality(min_qual); dev_parser->prepare(largest); }
+      try { dev_parser.reset(new device_sequence_parser(mer_len, device)); dev_parser->min_quality(min_qual); dev_parser->prepare(largest); dev_parser->prepare_compressed(gz_largest); }
       catch(std::exception& e) { die(e.what()); }
     }
     if(!sam_files.empty()) {
@@ -822,7 +838,24 @@ int bc_main(int argc, char* argv[]) {
     else if(a.is("-g", "--generator")) generator = a.value("-g", "--generator");
     else if(a.is("-G", "--Generators")) (void)a.value("-G", "--Generators");
     else if(a.is("-S", "--shell")) shell = a.value("-S", "--shell");
-    else if(a.cur().size() > 1 && a.cur()[0] == '-') die("Unknown option '" + a.cur() + "'");
+    else if(a.cur() == "-h" || a.cur() == "--help") {
+      std::cout << "Usage: jellyfish-amd bc [options] file:path+\n\n"
+                   "Create a bloom counter from the k-mers of fasta or fastq files on an MI355X.  bgzip-compressed (BGZF) fasta /\n"
+                   "fastq files are read too, inflated and cut on the device; plain gzip is not (recompress with bgzip, or use -g\n"
+                   "with zcat)\n\n"
+                   " -m, --mer-len=uint32       *Length of mer\n"
+                   " -s, --size=uint64          *Expected number of k-mers\n"
+                   " -f, --fpr=double            False positive rate (0.001)\n"
+                   " -C, --canonical             Count both strand, canonical representation (false)\n"
+                   " -o, --output=string         Output file (mer_bloom_filter)\n"
+                   " -g, --generator=path        File of commands generating fast[aq] (one per line, e.g. zcat reads.fa.gz)\n"
+                   " -S, --shell=string          Shell used to run generator commands ($SHELL or /bin/sh)\n"
+                   "     --timing=Timing file    Print timing information\n"
+                   "     --device=int            HIP device ordinal (current)\n"
+                   "     --gpus=N                N GPUs (a power of two), one process each (mer length <= 64)\n"
+                   "     --host-parse            Parse the sequence files on the host (default: on the device)\n";
+      return 0;
+    } else if(a.cur().size() > 1 && a.cur()[0] == '-') die("Unknown option '" + a.cur() + "'");
     else files.push_back(a.cur());
   }
   if(!mer_len) die("Error: mandatory switch missing: -m, --mer-len");

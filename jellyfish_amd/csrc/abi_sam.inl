@@ -1,10 +1,12 @@
-// jellyfish_amd/csrc/abi_sam.inl -- C ABI of the BGZF inflate and the BAM record decode (jfgpu_bgzf_scan,
-// jfgpu_parser_inflate_uploaded, _stream_read, _stream_consume, _bam_decode), included by jfgpu.hip after abi_parser.inl.
+// jellyfish_amd/csrc/abi_sam.inl -- C ABI of the BGZF inflate, the BAM record decode and the inflated FASTA / FASTQ stream
+// (jfgpu_bgzf_scan, jfgpu_parser_inflate_uploaded, _stream_read, _stream_consume, _bam_decode, _stream_cut, _stream_parse),
+// included by jfgpu.hip after abi_parser.inl.
 struct BgzfState {
   uint8_t* d_stream[2] = {nullptr, nullptr}; size_t stream_cap[2] = {0, 0};
   int scur = 0; size_t stream_len = 0;                     // inflated bytes not yet consumed, in d_stream[scur]
   jfgpu_bgzf_block* d_blocks = nullptr; size_t blocks_cap = 0;
   unsigned long long* d_err = nullptr;
+  unsigned long long* d_cut = nullptr;                     // result of stream_cut_kernel
   BamSeg* d_seg = nullptr; size_t seg_cap = 0;
   uint64_t* d_want = nullptr; size_t want_cap = 0;
   uint64_t* d_rec_off = nullptr; size_t rec_off_cap = 0;
@@ -17,7 +19,7 @@ struct BgzfState {
 
 static void bgzf_state_free(BgzfState* b) {
   if(!b) return;
-  hipFree(b->d_stream[0]); hipFree(b->d_stream[1]); hipFree(b->d_blocks); hipFree(b->d_err); hipFree(b->d_seg); hipFree(b->d_want);
+  hipFree(b->d_stream[0]); hipFree(b->d_stream[1]); hipFree(b->d_blocks); hipFree(b->d_err); hipFree(b->d_cut); hipFree(b->d_seg); hipFree(b->d_want);
   hipFree(b->d_rec_off); hipFree(b->d_out_off); hipFree(b->d_rec_start); hipFree(b->d_rec_out); hipFree(b->d_tot);
   delete b;
 }
@@ -29,6 +31,7 @@ int bgzf_state(jfgpu_parser* p) {
   std::unique_ptr<BgzfState> b(new BgzfState);
   HIP_TRY(hipMalloc((void**)&b->d_err, sizeof(unsigned long long)));
   HIP_TRY(hipMalloc((void**)&b->d_tot, sizeof(BamTotals)));
+  HIP_TRY(hipMalloc((void**)&b->d_cut, sizeof(unsigned long long)));
   p->bgzf = b.release();
   return JFGPU_OK;
 }
@@ -223,6 +226,46 @@ int jfgpu_parser_bam_decode(jfgpu_parser* p, size_t skip, int32_t n_ref, const c
   rc = jfgpu_parser_stream_consume(p, (size_t)tot.end); if(rc) return rc;    // the incomplete last record stays
   if(n_records) *n_records = tot.recs;
   if(n_left) *n_left = b.stream_len;
+  return JFGPU_OK;
+}
+
+int jfgpu_parser_stream_cut(jfgpu_parser* p, unsigned fmt, size_t* cut) {
+  int rc = use_p(p); if(rc) return rc;
+  if(!cut) return fail(JFGPU_E_INVALID, "null argument");
+  *cut = 0;
+  if(fmt != JFGPU_PARSE_FASTA && fmt != JFGPU_PARSE_FASTQ) return fail(JFGPU_E_INVALID, "format must be JFGPU_PARSE_FASTA or JFGPU_PARSE_FASTQ");
+  const size_t n = p->bgzf ? p->bgzf->stream_len : 0;
+  if(!n) return JFGPU_OK;
+  BgzfState& b = *p->bgzf;                                     // (the stream buffer has 64 bytes of slack behind stream_len)
+  HIP_TRY(hipEventRecord(p->ev_a, p->stream));
+  hipLaunchKernelGGL(stream_cut_kernel, dim3(1), dim3(kCutBlock), 0, p->stream, (const uint8_t*)b.d_stream[b.scur], (uint64_t)n,
+                     fmt == JFGPU_PARSE_FASTA ? (uint32_t)PARSE_FASTA : (uint32_t)PARSE_FASTQ, b.d_cut);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(p->ev_b, p->stream));
+  unsigned long long c = 0;
+  HIP_TRY(hipMemcpyAsync(&c, b.d_cut, sizeof(c), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  float ms = 0;
+  if(hipEventElapsedTime(&ms, p->ev_a, p->ev_b) == hipSuccess) p->last_ms = ms;
+  *cut = (size_t)c;
+  return JFGPU_OK;
+}
+
+int jfgpu_parser_stream_parse(jfgpu_parser* p, size_t n, unsigned flags, const char** d_out, size_t* n_out, uint64_t* n_records, size_t* n_left) {
+  int rc = use_p(p); if(rc) return rc;
+  if(!d_out || !n_out) return fail(JFGPU_E_INVALID, "null argument");
+  *d_out = nullptr; *n_out = 0;
+  if(n_records) *n_records = 0;
+  const size_t have = p->bgzf ? p->bgzf->stream_len : 0;
+  if(n > ((size_t)1 << 31)) return fail(JFGPU_E_INVALID, "chunk larger than 2^31 bytes");
+  if(n > have) return fail(JFGPU_E_INVALID, "parse past the inflated stream");
+  // (the stream buffer is an allocation's start: 16-byte aligned, as parse_dev's vector loads like it)
+  rc = jfgpu_parser_parse_dev(p, n ? (const char*)p->bgzf->d_stream[p->bgzf->scur] : nullptr, n, flags, d_out, n_out, n_records);
+  if(rc) return rc;                                            // JFGPU_E_FORMAT: nothing consumed, the bytes can be read back
+  const double ms = p->last_ms;
+  rc = jfgpu_parser_stream_consume(p, n); if(rc) return rc;
+  p->last_ms = n ? ms : 0;
+  if(n_left) *n_left = have - n;
   return JFGPU_OK;
 }
 

@@ -30,6 +30,7 @@
 #include "kernels_nword.hip.hpp"
 #include "kernels_parse.hip.hpp"
 #include "kernels_bgzf.hip.hpp"
+#include "kernels_stream.hip.hpp"
 #include "kernels_merge.hip.hpp"
 #include "kernels_text.hip.hpp"
 

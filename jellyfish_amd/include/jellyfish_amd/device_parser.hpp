@@ -7,6 +7,11 @@
 // mer_overlap_sequence_parser.hpp); what the device parser refuses -- FASTQ that is not in strict
 // 4-line layout -- is handed to sequence_parser from that point of the file on, so wrapped records
 // and the "Invalid fastq sequence" error behave as in the reference (:292-309).
+//
+// bgzip-compressed files (BGZF: gzip members of at most 64 KiB, sniffed from 1f 8b and the first member's header) take
+// parse_bgzf: whole members cross PCIe, are inflated on the device (jfgpu_parser_inflate_uploaded), and the inflated
+// text, which exists only there, is cut (jfgpu_parser_stream_cut) and parsed (jfgpu_parser_stream_parse) there too.
+// Plain gzip has no member table to spread over the device and is refused by name.
 #pragma once
 #include <jfgpu.h>
 #include <chrono>
@@ -57,6 +62,13 @@ public:
       if(jfgpu_parser_host_buffer(p_, w, cap, &pin_[w])) throw std::runtime_error(jfgpu_last_error());
   }
 
+  // The same for the largest bgzip-compressed file: the two pinned buffers its chunks of members are read into.
+  void prepare_compressed(size_t largest_file_bytes) {
+    if(!largest_file_bytes) return;
+    for(int w = 0; w < 2; ++w)
+      if(jfgpu_parser_host_buffer(p_, w, bgzf_window(largest_file_bytes) + 64, &pin_[w])) throw std::runtime_error(jfgpu_last_error());
+  }
+
   void parse_file(const char* path, const dev_sink_type& dev_sink, const host_sink_type& host_sink, const fence_type& fence) {
     parse_file_part(path, 0, 1, dev_sink, host_sink, fence);
   }
@@ -76,6 +88,16 @@ public:
       return;
     }
     const size_t size = (size_t)st.st_size;
+    unsigned char magic[2] = {0, 0};
+    if(size >= 2 && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
+      // A compressed file is not cut: the j-th one of the list is read whole by part j mod parts, as --sam files are.
+      // (Every part sees the same list; a call for a higher part of the same path belongs to the same file.)
+      if(bgzf_seen_ == 0 || bgzf_path_ != path || part <= bgzf_part_) ++bgzf_seen_;
+      bgzf_path_ = path; bgzf_part_ = part;
+      try { if((bgzf_seen_ - 1) % parts == part) parse_bgzf(fd, path, size, dev_sink, host_sink, fence); } catch(...) { close(fd); throw; }
+      close(fd);
+      return;
+    }
     size_t begin = 0, end = size;
     if(parts > 1) {
       char first = 0;
@@ -309,6 +331,147 @@ private:
     }
   }
 
+  // compressed bytes read for a chunk of a BGZF file of `size` bytes: a quarter of the text a chunk holds, one member at least
+  size_t bgzf_window(size_t size) const { return std::min(size, std::max<size_t>(chunk_ / 4, 65536 + 32)); }
+
+  // bgzip-compressed FASTA / FASTQ.  Chunks of whole members -- at most chunk_ bytes of text, and never more than keeps
+  // the inflated stream (carried tail + the members' ISIZE) within 1 GiB -- are read into a pinned buffer
+  // and their headers walked (jfgpu_bgzf_scan) by a background task while the device works on the chunk before; then
+  // upload, inflate (CRC32 and ISIZE checked), cut, fence, parse, sink.  The format comes from the first inflated byte.
+  // A cut of 0 before the end of the file means "inflate more"; the last chunk takes the whole stream, newline or not.
+  // What the device parser refuses (JFGPU_E_FORMAT), and a FASTQ with no record boundary in 1 GiB, is read back from
+  // that point on, the rest of the file inflated chunk by chunk and read back too, and all of it pushed into the general
+  // reader as one input (sequence_parser::push).
+  void parse_bgzf(int fd, const char* path, size_t size, const dev_sink_type& dev_sink, const host_sink_type& host_sink, const fence_type& fence) {
+    const std::string name = path;
+    auto error = [&](const std::string& what) { return std::runtime_error("Sequence file '" + name + "' " + what); };
+    auto api = [&](int rc) { if(rc) throw std::runtime_error(jfgpu_last_error()); };
+    {                                                          // the first member's header decides (as sam_parser does)
+      std::vector<char> head(std::min<size_t>(size, 65536 + 32));
+      jfgpu_bgzf_block b; size_t nb = 0, u = 0;
+      if(!read_exact(fd, 0, head.data(), head.size())) throw error("could not be read");
+      if(jfgpu_bgzf_scan(head.data(), head.size(), &b, 1, &nb, &u) == JFGPU_E_CORRUPT)
+        throw error(std::string("is gzip but not BGZF (") + jfgpu_last_error() +
+                    "): plain gzip input is not supported (recompress it with bgzip, or give `zcat` of it to -g)");
+    }
+    ++files_read_;
+    size_t max_stream = (size_t)1 << 30;
+    if(const char* e = getenv("JFGPU_BGZF_STREAM_MAX")) max_stream = std::min<size_t>(max_stream, std::max<size_t>(65536, strtoull(e, nullptr, 10)));   // (tests)
+    const size_t window = bgzf_window(size);
+    const size_t chunk_text = std::max<size_t>(chunk_, 65536);                        // inflated bytes a chunk, one member at least
+    std::vector<jfgpu_bgzf_block> blocks[2];
+    for(int w = 0; w < 2; ++w) {
+      api(jfgpu_parser_host_buffer(p_, w, window + 64, &pin_[w]));
+      blocks[w].resize(window / 28 + 1);                       // a BGZF member is at least 28 bytes
+    }
+    struct chunk_info { size_t members = 0, bytes = 0, isize = 0; std::string err; };
+    chunk_info ci[2];
+    // the whole members at file offset pos that inflate to at most `budget` bytes -> pin_[w], blocks[w] (members 0: none fits)
+    auto scan = [&](size_t pos, int w, size_t budget) {
+      chunk_info c;
+      const size_t n = std::min(window, size - pos);
+      size_t nb = 0, u = 0;
+      if(!read_slices(fd, pos, pin_[w], n)) c.err = "could not be read";
+      else if(jfgpu_bgzf_scan(pin_[w], n, blocks[w].data(), blocks[w].size(), &nb, &u))
+        c.err = std::string("is corrupt: ") + jfgpu_last_error() + " (chunk at byte " + std::to_string(pos) + " of the file)";
+      else if(nb == 0) c.err = "is truncated: incomplete BGZF member at byte " + std::to_string(pos) + " of the file";
+      else {
+        budget = std::min(budget, std::max<size_t>(chunk_text, blocks[w][0].isize));
+        while(c.members < nb && c.isize + blocks[w][c.members].isize <= budget) c.isize += blocks[w][c.members++].isize;
+        if(c.members) { const jfgpu_bgzf_block& l = blocks[w][c.members - 1]; c.bytes = (size_t)l.c_off + l.c_len + 8; }
+      }
+      return c;
+    };
+    auto upload = [&](int w) { api(jfgpu_parser_upload(p_, w, pin_[w], ci[w].bytes)); };
+    auto last_ms = [&]() { double ms = 0; jfgpu_parser_last_ms(p_, &ms); device_ms_ += ms; return ms; };
+
+    unsigned fmt = 0;
+    bool first = true, fallback = false;
+    size_t slen = 0, stream_off = 0;                           // the inflated stream now; inflated bytes taken out of it so far
+    size_t members = 0, inflated = 0, chunks = 0, fb_start = 0;
+    const size_t fb_before = fallback_bytes_;
+    double ms_inflate = 0, ms_cut = 0, ms_parse = 0;
+    std::vector<char> back;
+    auto to_host = [&]() {                                     // the whole stream -> the general reader
+      if(!fallback) { fallback = true; fb_start = stream_off; host_.push_begin(); }
+      back.resize(slen);
+      api(jfgpu_parser_stream_read(p_, 0, slen, back.data()));
+      api(jfgpu_parser_stream_consume(p_, slen));
+      fallback_bytes_ += slen; stream_off += slen;
+      const size_t n = slen; slen = 0;
+      try { host_.push(back.data(), n, host_sink); }
+      catch(std::runtime_error& e) { throw std::runtime_error(std::string(e.what()) + " (sequence file '" + name + "', inflated text from byte " + std::to_string(fb_start) + ")"); }
+    };
+
+    ci[0] = scan(0, 0, max_stream);
+    if(!ci[0].err.empty()) throw error(ci[0].err);
+    upload(0);
+    size_t pos = 0;
+    for(int w = 0; pos < size; w ^= 1) {
+      const size_t next = pos + ci[w].bytes;
+      const bool last = next >= size;
+      // the next chunk is read while this one is worked on, sized for the worst case that this one yields no cut
+      std::future<chunk_info> ahead;
+      if(!last && slen + ci[w].isize < max_stream) {
+        const size_t budget = max_stream - slen - ci[w].isize;
+        ahead = std::async(std::launch::async, [&scan, next, w, budget]() { return scan(next, w ^ 1, budget); });
+      }
+      try {
+        if(jfgpu_parser_inflate_uploaded(p_, w, blocks[w].data(), ci[w].members, &slen))
+          throw error(std::string("could not be inflated: ") + jfgpu_last_error() + " (chunk at byte " + std::to_string(pos) + " of the file)");
+        ms_inflate += last_ms();
+        members += ci[w].members; inflated += ci[w].isize; ++chunks;
+        if(!fmt && slen) {
+          char c = 0;
+          api(jfgpu_parser_stream_read(p_, 0, 1, &c));
+          if(c == '>') fmt = JFGPU_PARSE_FASTA;
+          else if(c == '@') fmt = JFGPU_PARSE_FASTQ;
+          else throw std::runtime_error("Unsupported format: sequence file '" + name + "' inflates to text that starts with neither '>' nor '@'");
+        }
+        if(fallback) { if(slen) to_host(); }
+        else if(slen) {
+          size_t cut = slen;
+          if(!last) { api(jfgpu_parser_stream_cut(p_, fmt, &cut)); ms_cut += last_ms(); }
+          if(cut) {
+            fence();
+            const char* d_out = nullptr; size_t n_out = 0, left = 0; uint64_t recs = 0;
+            const int rc = jfgpu_parser_stream_parse(p_, cut, fmt | (first ? 0u : JFGPU_PARSE_CONTINUE), &d_out, &n_out, &recs, &left);
+            if(rc == JFGPU_E_FORMAT) to_host();
+            else {
+              api(rc);
+              ms_parse += last_ms();
+              reads_read_ += recs;
+              if(n_out) dev_sink(d_out, n_out);
+              stream_off += cut; slen = left; first = false;
+            }
+          }
+        }
+      } catch(...) { if(ahead.valid()) ahead.wait(); throw; }
+      pos = next;
+      if(last) break;
+      ci[w ^ 1] = ahead.valid() ? ahead.get() : chunk_info();
+      if(ci[w ^ 1].err.empty() && ci[w ^ 1].members == 0) {    // sized for the worst case: again, for the tail as it is
+        ci[w ^ 1] = scan(pos, w ^ 1, max_stream - slen);
+        if(ci[w ^ 1].err.empty() && ci[w ^ 1].members == 0) {  // the stream is full and has no boundary
+          if(fmt == JFGPU_PARSE_FASTA) throw error("has a FASTA line longer than " + (max_stream == ((size_t)1 << 30) ? std::string("1 GiB") : std::to_string(max_stream) + " bytes"));
+          to_host();
+          ci[w ^ 1] = scan(pos, w ^ 1, max_stream);
+        }
+      }
+      if(!ci[w ^ 1].err.empty()) throw error(ci[w ^ 1].err);
+      upload(w ^ 1);
+    }
+    if(fallback) {
+      try { host_.push_end(host_sink); }
+      catch(std::runtime_error& e) { throw std::runtime_error(std::string(e.what()) + " (sequence file '" + name + "', inflated text from byte " + std::to_string(fb_start) + ")"); }
+      if(fmt == JFGPU_PARSE_FASTQ && host_.incomplete_fastq())
+        throw error("is truncated: its last FASTQ record is incomplete (the inflated text ends at byte " + std::to_string(stream_off) + ")");
+    }
+    if(getenv("JFGPU_FEED_TRACE") != nullptr)
+      fprintf(stderr, "[feed] bgzf members=%zu compressed=%zu inflated=%zu chunks=%zu fallback_bytes=%zu inflate_ms=%.3f cut_ms=%.3f parse_ms=%.3f\n",
+              members, size, inflated, chunks, fallback_bytes_ - fb_before, ms_inflate, ms_cut, ms_parse);
+  }
+
   // FASTQ record boundary inside a buffer: start of the last line that begins with '@' and whose
   // second-next line begins with '+' (see fastq_cut)
   static size_t fastq_cut_in(const char* d, size_t len) {
@@ -343,6 +506,7 @@ private:
     return nt;
   }
   sequence_parser host_;
+  size_t bgzf_seen_ = 0; std::string bgzf_path_; unsigned bgzf_part_ = 0;   // compressed files met so far, the last one's path and part
   size_t files_read_ = 0, reads_read_ = 0, fallback_bytes_ = 0;
   double device_ms_ = 0;
 

@@ -83,19 +83,30 @@ public:
         if(r == 0) { eof = true; break; }
       }
       if(data.empty()) break;
-      if(data[0] != '>' && data[0] != '@') throw std::runtime_error("Unsupported format");
-      size_t cut = data.size();
-      if(!eof) {
-        cut = data[0] == '>' ? last_fasta_record(data) : last_fastq_record(data);
-        if(cut == 0) continue;                      // one record longer than everything read so far: read on
-      }
-      parse_memory(data.data(), cut, sink);
-      any = true;
-      data.erase(0, cut);
+      if(take_records(data, eof, sink)) any = true;
     }
     (void)any;
     files_read_ = files_before + 1;                 // one stream = one file, however many pieces
   }
+
+  // The same for bytes the caller has in hand (a compressed file inflated elsewhere): push_begin, any number of push,
+  // push_end.  Pieces of about `piece` bytes of whole records go to parse_memory, as in parse_stream.
+  void push_begin(size_t piece = (size_t)64 << 20) {
+    if(const char* e = getenv("JFGPU_STREAM_PIECE")) piece = std::max<size_t>(1, strtoull(e, nullptr, 10));
+    push_piece_ = piece; push_data_.clear(); push_files_before_ = files_read_; incomplete_fastq_ = false;
+  }
+  void push(const char* d, size_t n, const sink_type& sink) {
+    push_data_.append(d, n);
+    if(push_data_.size() >= push_piece_) take_records(push_data_, false, sink);
+  }
+  void push_end(const sink_type& sink) {
+    if(!push_data_.empty()) take_records(push_data_, true, sink);
+    std::string().swap(push_data_);
+    files_read_ = push_files_before_ + 1;
+  }
+  // did the last FASTQ input end inside a record, after its header and before its '+' line?  (The reference's reader, and parse_memory with
+  // it, takes such an end silently; a caller that knows the input is a whole file may want to say so.)
+  bool incomplete_fastq() const { return incomplete_fastq_; }
 
   void parse_memory(const char* data, size_t n, const sink_type& sink) {
     ++files_read_;
@@ -115,6 +126,23 @@ private:
   std::string buf_;
   size_t files_read_ = 0, reads_read_ = 0;
   int min_qual_ = 0;
+  std::string push_data_;
+  size_t push_piece_ = 0, push_files_before_ = 0;
+  bool incomplete_fastq_ = false;
+
+  // The whole records at the front of data (eof: all of it) go to parse_memory and leave data.  false: one record
+  // longer than everything in data, read on.
+  bool take_records(std::string& data, bool eof, const sink_type& sink) {
+    if(data[0] != '>' && data[0] != '@') throw std::runtime_error("Unsupported format");
+    size_t cut = data.size();
+    if(!eof) {
+      cut = data[0] == '>' ? last_fasta_record(data) : last_fastq_record(data);
+      if(cut == 0) return false;
+    }
+    parse_memory(data.data(), cut, sink);
+    data.erase(0, cut);
+    return true;
+  }
 
   // start of the last record that begins inside d (0: none but the first)
   static size_t last_fasta_record(const std::string& d) {
@@ -187,6 +215,7 @@ private:
 
   void parse_fastq(const char* p, const char* end, const sink_type& sink) {
     p = line_end(p, end); if(p < end) ++p;   // first '@' header
+    incomplete_fastq_ = true;                // until its '+' line is seen
     ++reads_read_;
     while(p < end) {
       // sequence lines until a line starting with '+'
@@ -202,6 +231,7 @@ private:
         p = e < end ? e + 1 : end;
       }
       if(p >= end) break;
+      incomplete_fastq_ = false;
       // '+' line, then exactly seq_len quality characters (line breaks tolerated)
       p = line_end(p, end); if(p < end) ++p;
       size_t quals = 0;
@@ -222,6 +252,7 @@ private:
         buf_.push_back('N');
         p = line_end(p, end); if(p < end) ++p;
         ++reads_read_;
+        incomplete_fastq_ = true;
       }
       maybe_flush(sink);
     }

@@ -1,43 +1,40 @@
 // jellyfish_amd/csrc/abi_bloom.inl -- C ABI of the Bloom counter (jfgpu_bc_*), included by jfgpu.hip.
+// The counter owns its stream and device memory (hip_own.hpp); DevBloom, what the kernels get, points into them (view()).
 // ---- Bloom counter (jellyfish bc / count --bc, BASELINE config 3) ---------------------------------
 struct jfgpu_bloom {
   int device = 0, n_cu = 256;
   Tuning tun;                    // the JFGPU_* switches as they were at creation (tuning.hpp)
-  hipStream_t stream = nullptr;
+  Stream stream;                 // (before the buffers used on it: they go first)
   TableGeom g{};                 // only k / key_mask / canonical / nbytes are used (encode side)
   bool wide = false; WideGeom wg{};   // 33 <= k <= 64: two-word keys
   bool nword = false; NGeom ng{};     // 65 <= k <= 128: keys of three and four words (kernels_nword.hip.hpp), direct path only
   uint64_t m = 0; uint32_t nh = 0;
   Gf2Matrix m1, m2;
-  uint64_t *d_t1 = nullptr, *d_t2 = nullptr;
-  uint32_t* d_data = nullptr; size_t data_bytes = 0, alloc_bytes = 0;
-  unsigned long long* d_mers = nullptr;
-  uint8_t* d_stage = nullptr;
+  DevBuf<uint64_t> d_t1, d_t2;
+  DevBuf<uint8_t> d_data; size_t data_bytes = 0, alloc_bytes = 0;      // alloc_bytes: a multiple of 4, read as 32-bit words
+  DevBuf<unsigned long long> d_mers;
+  DevBuf<uint8_t> d_stage;
   // partitioned insert (kernels_bloom_part.hip.hpp, bloom_partition.inl)
   BloomPart bp{}; bool part_ok = false;
   uint32_t kind = 0;               // 0: Bloom counter (bc / count --bc); 1: one-pass Bloom filter of bits (count --bf-size)
   int mode = 0;                    // 0 auto, 1 direct (global CAS), 2 partitioned (JFGPU_BLOOM_MODE / jfgpu_bc_set_mode)
   double slack = 0.03;             // head-room of a bucket region over the mean
   int g1 = 0;
-  uint8_t* ws = nullptr; size_t ws_cap = 0, ws_used = 0;
+  DevBuf<uint8_t> ws; size_t ws_cap = 0, ws_used = 0;                  // bump arena
   struct Pending { uint32_t* items; uint64_t* off; unsigned long long* tot; uint32_t cap; };
   std::vector<Pending> pending;
-  uint32_t* d_M2 = nullptr;
-  uint64_t* d_strag2 = nullptr; uint32_t* d_strag2_n = nullptr; uint32_t strag2_lists = 0;     // p2_ring_kernel's straggler lists
-  uint64_t* d_strag1 = nullptr; uint32_t* d_strag1_n = nullptr;                                // p1_bloom_ring_kernel's (one list per workgroup)
+  DevBuf<uint32_t> d_M2;
+  DevBuf<uint64_t> d_strag2; DevBuf<uint32_t> d_strag2_n; uint32_t strag2_lists = 0;           // p2_ring_kernel's straggler lists
+  DevBuf<uint64_t> d_strag1; DevBuf<uint32_t> d_strag1_n;                                      // p1_bloom_ring_kernel's (one list per workgroup)
   int p1_ring_per = 0;                                                                         // cells per lane and round of the ring P1b (0: the sort-based kernels)
   bool prof_on = false;
-  std::vector<ProfSpan> spans;
+  std::vector<OwnedSpan> spans;
   double prof_ms[5] = {}; uint64_t prof_launches[5] = {}, prof_units[5] = {};      // [BS_COUNT] (bloom_partition.inl)
-  DevBloom view() const { DevBloom b; b.data = d_data; b.m = m; b.recip = bloom_recip(m); b.nh = nh; b.kind = kind; b.pad_ = 0; b.nbytes = g.nbytes; b.tbl1 = d_t1; b.tbl2 = d_t2; b.cache = nullptr; b.cache_mask = 0; return b; }
+  DevBloom view() const { DevBloom b; b.data = (uint32_t*)d_data.get(); b.m = m; b.recip = bloom_recip(m); b.nh = nh; b.kind = kind; b.pad_ = 0; b.nbytes = g.nbytes; b.tbl1 = d_t1; b.tbl2 = d_t2; b.cache = nullptr; b.cache_mask = 0; return b; }
 };
 
 namespace {
-int use_b(const jfgpu_bloom* b) {
-  if(!b) return fail(JFGPU_E_INVALID, "null bloom counter");
-  HIP_TRY(hipSetDevice(b->device));
-  return JFGPU_OK;
-}
+int use_b(const jfgpu_bloom* b) { return use_dev(b, "null bloom counter"); }
 Gf2Matrix random_full_matrix(uint32_t c, uint64_t& seed_state) {   // hash_pair<mer_dna>: 64 x 2k, any matrix
   Gf2Matrix m; m.r = 64; m.c = c; m.columns.assign(c, 0);
   for(uint32_t i = 0; i < c; ++i) m.columns[i] = splitmix64(seed_state);
@@ -67,12 +64,8 @@ static int bloom_create(const jfgpu_bloom_params* p, jfgpu_bloom** out, uint32_t
   if(p->k < 1) return fail(JFGPU_E_INVALID, "mer length must be >= 1");
   if(p->k > 128) return fail(JFGPU_E_UNSUPPORTED, "mer length > 128 (more than four key words) is not built");
   if(p->m < 1 || p->nb_hashes < 1 || p->nb_hashes > 64) return fail(JFGPU_E_INVALID, "bad Bloom counter size / number of hashes");
-  int ndev = 0;
-  if(hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(JFGPU_E_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-  int dev = p->device;
-  if(dev < 0) HIP_TRY(hipGetDevice(&dev));
-  if(dev >= ndev) return fail(JFGPU_E_NO_DEVICE, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(dev));
+  int dev = 0;
+  int rc = pick_device(p->device, &dev); if(rc) return rc;
   std::unique_ptr<jfgpu_bloom> b(new jfgpu_bloom);
   b->device = dev; b->m = p->m; b->nh = p->nb_hashes; b->kind = kind;
   if(p->k > 64) {
@@ -108,7 +101,7 @@ static int bloom_create(const jfgpu_bloom_params* p, jfgpu_bloom** out, uint32_t
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, dev));
   b->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+  rc = b->stream.create(); if(rc) return rc;
   b->data_bytes = kind == 1 ? b->m / 8 + (b->m % 8 != 0)         // bloom_filter.hpp:25-27
                             : b->m / 5 + (b->m % 5 != 0);        // bloom_counter2.hpp:40-42
   b->alloc_bytes = (b->data_bytes + 3) / 4 * 4 + 4;
@@ -142,12 +135,12 @@ static int bloom_create(const jfgpu_bloom_params* p, jfgpu_bloom** out, uint32_t
     HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_kernel<BloomRingDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
     HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_roles_kernel<uint32_t, 2, BloomRingDirect, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
   }
-  HIP_TRY(hipMalloc((void**)&b->d_data, b->alloc_bytes));
+  rc = b->d_data.alloc(b->alloc_bytes); if(rc) return rc;
   HIP_TRY(hipMemsetAsync(b->d_data, 0, b->alloc_bytes, b->stream));
-  HIP_TRY(hipMalloc((void**)&b->d_t1, t1.size() * 8)); HIP_TRY(hipMalloc((void**)&b->d_t2, t2.size() * 8));
+  if((rc = b->d_t1.alloc(t1.size())) || (rc = b->d_t2.alloc(t2.size()))) return rc;
   HIP_TRY(hipMemcpy(b->d_t1, t1.data(), t1.size() * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_t2, t2.data(), t2.size() * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc((void**)&b->d_mers, sizeof(unsigned long long)));
+  rc = b->d_mers.alloc(1); if(rc) return rc;
   HIP_TRY(hipMemsetAsync(b->d_mers, 0, sizeof(unsigned long long), b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
   *out = b.release();
@@ -159,13 +152,6 @@ void jfgpu_bc_destroy(jfgpu_bloom* b) {
   hipSetDevice(b->device);
   if(b->stream) hipStreamSynchronize(b->stream);
   bloom_prof_collect(b);
-  hipFree(b->d_data); hipFree(b->d_t1); hipFree(b->d_t2); hipFree(b->d_mers);
-  if(b->d_stage) hipFree(b->d_stage);
-  if(b->ws) hipFree(b->ws);
-  if(b->d_M2) hipFree(b->d_M2);
-  if(b->d_strag2) { hipFree(b->d_strag2); hipFree(b->d_strag2_n); }
-  if(b->d_strag1) { hipFree(b->d_strag1); hipFree(b->d_strag1_n); }
-  if(b->stream) hipStreamDestroy(b->stream);
   delete b;
 }
 
@@ -186,13 +172,13 @@ int jfgpu_bc_insert_ascii(jfgpu_bloom* b, const char* bases, size_t n) {
   int rc = use_b(b); if(rc) return rc;
   if(n < b->g.k) return JFGPU_OK;
   if(!bases) return fail(JFGPU_E_INVALID, "null buffer");
-  if(!b->d_stage) HIP_TRY(hipMalloc((void**)&b->d_stage, kStageBytes));
+  if(!b->d_stage) { rc = b->d_stage.alloc(kStageBytes); if(rc) return rc; }
   const size_t step = kStageBytes - (b->g.k - 1);
   for(size_t o = 0; o < n; o += step) {
     const size_t len = std::min(kStageBytes, n - o);
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipMemcpyAsync(b->d_stage, bases + o, len, hipMemcpyHostToDevice, b->stream));
-    rc = jfgpu_bc_insert_ascii_dev(b, (const char*)b->d_stage, len); if(rc) return rc;
+    rc = jfgpu_bc_insert_ascii_dev(b, (const char*)b->d_stage.get(), len); if(rc) return rc;
     if(o + len >= n) break;
   }
   return JFGPU_OK;
@@ -249,22 +235,21 @@ int jfgpu_bc_keys(jfgpu_bloom* b, const uint64_t* keys, size_t n, uint8_t* out, 
   if(b->kind != 0) return fail(JFGPU_E_UNSUPPORTED, "check / insert on encoded k-mers is built for Bloom counters only");
   rc = bloom_flush(b); if(rc) return rc;
   if(!n) return JFGPU_OK;
-  uint64_t* d_k = nullptr; uint8_t* d_o = nullptr;
+  DevBuf<uint64_t> d_k; DevBuf<uint8_t> d_o;
   const size_t kw = b->nword ? (2 * b->g.k + 63) / 64 : b->wide ? 2 : 1;      // words per key (little-endian words, like jfgpu_add_keys)
-  HIP_TRY(hipMalloc((void**)&d_k, n * 8 * kw));
-  if(hipMalloc((void**)&d_o, n) != hipSuccess) { hipFree(d_k); return fail(JFGPU_E_ALLOC, "hipMalloc"); }
+  rc = d_k.alloc(n * kw); if(rc) return rc;
+  if(!d_o.try_alloc(n)) return fail(JFGPU_E_ALLOC, "hipMalloc");
   hipError_t e = hipMemcpyAsync(d_k, keys, n * 8 * kw, hipMemcpyHostToDevice, b->stream);
   if(e == hipSuccess) {
     const int grid = (int)std::max<size_t>(1, std::min<size_t>((n + kBlock - 1) / kBlock, (size_t)b->n_cu * 8));
-    if(b->nword) hipLaunchKernelGGL(bloom_keys_nword_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->ng.key_mask, (uint32_t)kw, (const uint64_t*)d_k, (uint64_t)n, d_o, do_insert);
-    else if(b->wide) hipLaunchKernelGGL(bloom_keys_wide_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->wg.key_mask, (const uint64_t*)d_k, (uint64_t)n, d_o, do_insert);
+    if(b->nword) hipLaunchKernelGGL(bloom_keys_nword_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->ng.key_mask, (uint32_t)kw, (const uint64_t*)d_k, (uint64_t)n, d_o.get(), do_insert);
+    else if(b->wide) hipLaunchKernelGGL(bloom_keys_wide_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->wg.key_mask, (const uint64_t*)d_k, (uint64_t)n, d_o.get(), do_insert);
     else
-    hipLaunchKernelGGL(bloom_keys_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), (const uint64_t*)d_k, (uint64_t)n, d_o, do_insert);
+    hipLaunchKernelGGL(bloom_keys_kernel, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), (const uint64_t*)d_k, (uint64_t)n, d_o.get(), do_insert);
     e = hipGetLastError();
   }
   if(e == hipSuccess && out) e = hipMemcpyAsync(out, d_o, n, hipMemcpyDeviceToHost, b->stream);
   hipStreamSynchronize(b->stream);
-  hipFree(d_k); hipFree(d_o);
   if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
   return JFGPU_OK;
 }
@@ -329,7 +314,7 @@ int jfgpu_attach_bloom(jfgpu_table* t, jfgpu_bloom* b) {   // count --bc (count_
   if(t->d_bcache) {
     HIP_TRY(hipStreamSynchronize(t->stream));
     t->dt.bloom.cache = nullptr; t->dt.bloom.cache_mask = 0;
-    hipFree(t->d_bcache); t->d_bcache = nullptr;
+    (void)t->d_bcache.reset();
   }
   t->bcache_state = 0;
   if(!b) { memset(&t->dt.bloom, 0, sizeof t->dt.bloom); memset(&t->wt.bloom, 0, sizeof t->wt.bloom); memset(&t->nt.bloom, 0, sizeof t->nt.bloom); return JFGPU_OK; }

@@ -991,7 +991,7 @@ int comm_grow(jfgpu_comm* c) {
   // (round-5 advisor finding: it used to return before the all-reduce, the peers blocked in it).
   auto free_prepared = [&]() {
     for(size_t q = 0; q < c->ranks.size(); ++q)
-      if(prepared[q]) { DevTable& nd = N[q].nd; hipFree(nd.slots); hipFree(nd.ovf_key); hipFree(nd.ovf_cnt); hipFree(nd.dirty); hipFree(N[q].nf); hipFree(N[q].ni); prepared[q] = 0; }
+      if(prepared[q]) { N[q].drop(); prepared[q] = 0; }
   };
   uint64_t agreed = hard ? 2 : cannot ? 1 : 0;
   if(!c->local) { int rc = jfgpu_comm_allreduce_u64(c, &agreed, 1, 1); if(rc) { free_prepared(); return rc; } }
@@ -1135,7 +1135,7 @@ int comm_bc_merge(jfgpu_comm* c, jfgpu_bloom** blooms) {
     if(c->ranks[q].inflight) { rc = fail(JFGPU_E_INVALID, "bc merge: a count step is still in flight on this communicator"); break; }
     rc = bloom_flush(b); if(rc) break;
     if(hipStreamSynchronize(b->stream) != hipSuccess) { rc = fail(JFGPU_E_HIP, "bc merge: sync"); break; }
-    shim[q].reset(new jfgpu_table); shim[q]->stream = b->stream; shim[q]->device = b->device;
+    shim[q].reset(new jfgpu_table); shim[q]->stream.borrow(b->stream); shim[q]->device = b->device;
     c->ranks[q].t = shim[q].get();
   }
   auto restore = [&]() { for(size_t q = 0; q < nr; ++q) c->ranks[q].t = saved[q]; };
@@ -1165,7 +1165,7 @@ int comm_bc_merge(jfgpu_comm* c, jfgpu_bloom** blooms) {
     jfgpu_comm::Rank& R = c->ranks[q]; jfgpu_bloom* b = blooms[q];
     const int me = rank_of(q);
     const uint64_t n = r_len(me);
-    uint64_t* mine = reinterpret_cast<uint64_t*>(b->d_data) + r_lo(me);
+    uint64_t* mine = reinterpret_cast<uint64_t*>(b->d_data.get()) + r_lo(me);
     if(hipStreamWaitEvent(b->stream, R.exchanged[0], 0) != hipSuccess) { rc = fail(JFGPU_E_HIP, "bc merge: event"); break; }
     if(n) {
       (void)hipMemsetAsync(mine, 0, n * 8, b->stream);
@@ -1187,7 +1187,7 @@ int comm_bc_merge(jfgpu_comm* c, jfgpu_bloom** blooms) {
     jfgpu_comm::Rank& R = c->ranks[q]; jfgpu_bloom* b = blooms[q];
     if(hipStreamWaitEvent(b->stream, R.exchanged[1], 0) != hipSuccess) { rc = fail(JFGPU_E_HIP, "bc merge: event"); break; }
     for(int p = 0; p < W; ++p)
-      if(R.rcount[1][p]) (void)hipMemcpyAsync(reinterpret_cast<uint64_t*>(b->d_data) + r_lo(p), R.recv[1] + R.roff[1][p], R.rcount[1][p] * 8, hipMemcpyDeviceToDevice, b->stream);
+      if(R.rcount[1][p]) (void)hipMemcpyAsync(reinterpret_cast<uint64_t*>(b->d_data.get()) + r_lo(p), R.recv[1] + R.roff[1][p], R.rcount[1][p] * 8, hipMemcpyDeviceToDevice, b->stream);
     (void)hipEventRecord(R.consumed[1], b->stream);
     unsigned long long m = 0;
     if(hipMemcpyAsync(&m, b->d_mers, sizeof m, hipMemcpyDeviceToHost, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) { rc = fail(JFGPU_E_HIP, "bc merge: sync"); break; }
@@ -1602,10 +1602,10 @@ int jfgpu_add_key_vals(jfgpu_table* t, const uint64_t* keys, const uint64_t* val
   if(!keys || !vals) return fail(JFGPU_E_INVALID, "null argument");
   if(t->g.shard_bits) return fail(JFGPU_E_UNSUPPORTED, "add_key_vals: not for a shard (route the keys first)");
   const size_t kw = t->key_words;
-  uint64_t *d_k = nullptr, *d_v = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_k, n * kw * sizeof(uint64_t)));
-  if(hipMalloc((void**)&d_v, n * sizeof(uint64_t)) != hipSuccess) { hipFree(d_k); return fail(JFGPU_E_ALLOC, "hipMalloc values"); }
-  auto done = [&](int r) { hipStreamSynchronize(t->stream); hipFree(d_k); hipFree(d_v); return r; };
+  DevBuf<uint64_t> d_k, d_v;
+  rc = d_k.alloc(n * kw); if(rc) return rc;
+  if(!d_v.try_alloc(n)) return fail(JFGPU_E_ALLOC, "hipMalloc values");
+  auto done = [&](int r) { hipStreamSynchronize(t->stream); return r; };
   if(hipMemcpyAsync(d_k, keys, n * kw * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream) != hipSuccess ||
      hipMemcpyAsync(d_v, vals, n * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream) != hipSuccess) return done(fail(JFGPU_E_HIP, "add_key_vals: copy"));
   size_t off = 0;

@@ -1,31 +1,23 @@
 // jellyfish_amd/csrc/abi_merge.inl -- C ABI of the device merge of sorted databases (jfgpu_merge_*), included by jfgpu.hip.
 // Kernels: kernels_merge.hip.hpp.  The host side here owns the windowing (cuts of every input at position boundaries,
 // found by binary search over the caller's mapped bodies), the two-deep pipeline of uploads, kernels and downloads, and
-// the growth of the working buffers when one position holds more than a window.
+// the growth of the working buffers when one position holds more than a window.  The pipeline's streams, events and
+// per-slot buffers are a WindowPipe (hip_own.hpp), shared with abi_text.inl; what is the merge's own is here.
 struct jfgpu_merge {
   int device = 0;
+  WindowPipe pipe;                                          // (first: its streams outlive the buffers below)
   uint32_t k = 0, kb = 0, kw = 0, key_bits = 0, n_inputs = 0, ocl = 0;
   int op = 0;
   uint64_t size = 0, lower = 0, upper = 0, window_records = 0, vmax = 0;
   bool identity = false;
   std::vector<uint32_t> clen;
   std::vector<uint64_t> h_fwd;                              // byte tables of the matrix, for the host's cuts too
-  uint64_t* d_fwd = nullptr;
-  hipStream_t s_up = nullptr, s_k = nullptr, s_down = nullptr;
-  hipEvent_t up_a[2] = {nullptr, nullptr}, up_done[2] = {nullptr, nullptr}, ev_a[2] = {nullptr, nullptr}, ev_b[2] = {nullptr, nullptr},
-             k_done[2] = {nullptr, nullptr};
-  uint8_t* h_in[2] = {nullptr, nullptr}; size_t h_in_cap[2] = {0, 0};     // pinned staging, in and out
-  uint8_t* h_out[2] = {nullptr, nullptr}; size_t h_out_cap[2] = {0, 0};
-  uint8_t* d_raw[2] = {nullptr, nullptr}; size_t raw_cap[2] = {0, 0};
-  uint8_t* d_out[2] = {nullptr, nullptr}; size_t out_cap[2] = {0, 0};
-  uint64_t* d_keys = nullptr; uint64_t* d_vals = nullptr; uint64_t* d_pos = nullptr; uint64_t* d_oval = nullptr;
-  uint32_t* d_osrc = nullptr; uint32_t* d_bcnt = nullptr; uint64_t* d_boff = nullptr; size_t rec_cap = 0;
-  uint64_t* d_nkept = nullptr;                              // [2]
-  uint32_t* d_unsorted = nullptr;                           // [n_inputs]
-  unsigned long long* d_tallies = nullptr;                  // [4]
-  uint64_t* h_status[2] = {nullptr, nullptr};               // pinned: n_kept, then the unsorted flags
-  uint64_t tallies[4] = {0, 0, 0, 0};
-  double ms[4] = {0, 0, 0, 0};                              // upload, kernels, download, sink
+  DevBuf<uint64_t> d_fwd;
+  DevBuf<uint64_t> d_keys, d_vals, d_pos, d_oval, d_boff; DevBuf<uint32_t> d_osrc, d_bcnt; size_t rec_cap = 0;    // of one window's records
+  DevBuf<uint64_t> d_nkept;                                 // [2]
+  DevBuf<uint32_t> d_unsorted;                              // [n_inputs]
+  DevBuf<unsigned long long> d_tallies;                     // [4]
+  uint64_t tallies[4] = {0, 0, 0, 0};                       // (a slot's status block: n_kept, then the unsorted flags)
   uint64_t counts[3] = {0, 0, 0};                           // windows, records in, records out
 };
 
@@ -33,11 +25,7 @@ namespace {
 
 struct MergeWindow { std::vector<uint64_t> lo, hi; uint64_t total = 0; };
 
-int use_m(const jfgpu_merge* m) {
-  if(!m) return fail(JFGPU_E_INVALID, "null merge");
-  HIP_TRY(hipSetDevice(m->device));
-  return JFGPU_OK;
-}
+int use_m(const jfgpu_merge* m) { return use_dev(m, "null merge"); }
 
 // pos of the record at rec: the kernels' product, byte table by byte table
 uint64_t merge_host_pos(const jfgpu_merge* m, const uint8_t* rec) {
@@ -75,33 +63,23 @@ void merge_split(const jfgpu_merge* m, const void* const* bodies, uint64_t P0, u
   merge_split(m, bodies, mid, P1, cut, hi, out);
 }
 
-int merge_grow_host(uint8_t*& ptr, size_t& cap, size_t need) {
-  if(need <= cap) return JFGPU_OK;
-  if(ptr) { HIP_TRY(hipHostFree(ptr)); ptr = nullptr; cap = 0; }
-  const size_t want = need + need / 8;
-  HIP_TRY(hipHostMalloc((void**)&ptr, want, hipHostMallocDefault));
-  cap = want;
-  return JFGPU_OK;
-}
-
 size_t merge_segs_bytes(const jfgpu_merge* m) { return ((size_t)m->n_inputs * sizeof(MergeSeg) + 255) & ~(size_t)255; }
 
 template <int KW>
 void merge_launch(jfgpu_merge* m, const MergeWin& W, const uint8_t* raw, int slot) {
   const uint64_t pos_mask = m->size - 1;
-  hipLaunchKernelGGL((merge_decode_kernel<KW>), dim3(W.n_tiles), dim3(kMergeBlock), 0, m->s_k, W, raw,
-                     (const uint64_t*)(m->identity ? nullptr : m->d_fwd), m->kb, m->key_bits, pos_mask, m->d_unsorted);
-  hipLaunchKernelGGL((merge_rank_kernel<KW>), dim3(W.n_tiles), dim3(kMergeBlock), 0, m->s_k, W, m->op, m->lower, m->upper, m->vmax,
-                     m->d_oval, m->d_osrc, m->d_tallies);
+  const hipStream_t s_k = m->pipe.s_k;
+  hipLaunchKernelGGL((merge_decode_kernel<KW>), dim3(W.n_tiles), dim3(kMergeBlock), 0, s_k, W, raw,
+                     (const uint64_t*)(m->identity ? nullptr : m->d_fwd.get()), m->kb, m->key_bits, pos_mask, m->d_unsorted.get());
+  hipLaunchKernelGGL((merge_rank_kernel<KW>), dim3(W.n_tiles), dim3(kMergeBlock), 0, s_k, W, m->op, m->lower, m->upper, m->vmax,
+                     m->d_oval.get(), m->d_osrc.get(), m->d_tallies.get());
   if(m->op == 3) return;
   const uint32_t nb = (uint32_t)((W.total + kMergeBlock - 1) / kMergeBlock);
-  hipLaunchKernelGGL(merge_count_kernel, dim3(nb), dim3(kMergeBlock), 0, m->s_k, (const uint32_t*)m->d_osrc, W.total, m->d_bcnt);
-  hipLaunchKernelGGL(merge_scan_kernel, dim3(1), dim3(kMergeBlock), 0, m->s_k, (const uint32_t*)m->d_bcnt, nb, m->d_boff, m->d_nkept + slot);
-  hipLaunchKernelGGL((merge_pack_kernel<KW>), dim3(nb), dim3(kMergeBlock), 0, m->s_k, W, (const uint64_t*)m->d_oval, (const uint32_t*)m->d_osrc,
-                     (const uint64_t*)m->d_boff, m->kb, m->ocl, m->d_out[slot]);
+  hipLaunchKernelGGL(merge_count_kernel, dim3(nb), dim3(kMergeBlock), 0, s_k, (const uint32_t*)m->d_osrc, W.total, m->d_bcnt.get());
+  hipLaunchKernelGGL(merge_scan_kernel, dim3(1), dim3(kMergeBlock), 0, s_k, (const uint32_t*)m->d_bcnt, nb, m->d_boff.get(), m->d_nkept + slot);
+  hipLaunchKernelGGL((merge_pack_kernel<KW>), dim3(nb), dim3(kMergeBlock), 0, s_k, W, (const uint64_t*)m->d_oval, (const uint32_t*)m->d_osrc,
+                     (const uint64_t*)m->d_boff, m->kb, m->ocl, m->pipe.slot[slot].d_out.get());
 }
-
-double merge_wall_ms(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 }  // namespace
 
@@ -118,13 +96,9 @@ int jfgpu_merge_create(const jfgpu_merge_params* p, jfgpu_merge** out) {
   if(p->op > 3) return fail(JFGPU_E_INVALID, "merge: operation must be 0 sum, 1 min, 2 max or 3 Jaccard");
   for(uint32_t f = 0; f < p->n_inputs; ++f)
     if(p->counter_len[f] < 1 || p->counter_len[f] > 8) return fail(JFGPU_E_INVALID, "merge: counter_len must be in [1, 8]");
-  int ndev = 0;
-  if(hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(JFGPU_E_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-  int dev = p->device;
-  if(dev < 0) HIP_TRY(hipGetDevice(&dev));
-  if(dev >= ndev) return fail(JFGPU_E_NO_DEVICE, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(dev));
-  std::unique_ptr<jfgpu_merge, void (*)(jfgpu_merge*)> m(new jfgpu_merge, jfgpu_merge_destroy);
+  int dev = 0;
+  int rc = pick_device(p->device, &dev); if(rc) return rc;
+  std::unique_ptr<jfgpu_merge> m(new jfgpu_merge);
   m->device = dev; m->k = p->k; m->key_bits = 2 * p->k; m->kb = (m->key_bits + 7) / 8; m->kw = (m->key_bits + 63) / 64;
   m->n_inputs = p->n_inputs; m->ocl = p->out_counter_len; m->op = (int)p->op; m->size = p->size; m->lower = p->lower; m->upper = p->upper;
   m->window_records = p->window_records ? p->window_records : kMergeWindowRecords;
@@ -135,20 +109,10 @@ int jfgpu_merge_create(const jfgpu_merge_params* p, jfgpu_merge** out) {
     std::vector<uint64_t> img(m->key_bits);
     for(uint32_t j = 0; j < m->key_bits; ++j) img[j] = p->matrix_columns[m->key_bits - 1 - j];
     gf2_byte_tables(img, m->kb, m->h_fwd);
-    HIP_TRY(hipMalloc((void**)&m->d_fwd, m->h_fwd.size() * sizeof(uint64_t)));
+    if((rc = m->d_fwd.alloc(m->h_fwd.size()))) return rc;
     HIP_TRY(hipMemcpy(m->d_fwd, m->h_fwd.data(), m->h_fwd.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
   }
-  HIP_TRY(hipStreamCreateWithFlags(&m->s_up, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&m->s_k, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&m->s_down, hipStreamNonBlocking));
-  for(int i = 0; i < 2; ++i) {
-    HIP_TRY(hipEventCreate(&m->up_a[i])); HIP_TRY(hipEventCreate(&m->up_done[i]));
-    HIP_TRY(hipEventCreate(&m->ev_a[i])); HIP_TRY(hipEventCreate(&m->ev_b[i])); HIP_TRY(hipEventCreate(&m->k_done[i]));
-    HIP_TRY(hipHostMalloc((void**)&m->h_status[i], 8 + 4 * (size_t)m->n_inputs, hipHostMallocDefault));
-  }
-  HIP_TRY(hipMalloc((void**)&m->d_nkept, 2 * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc((void**)&m->d_unsorted, m->n_inputs * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc((void**)&m->d_tallies, 4 * sizeof(unsigned long long)));
+  if((rc = m->pipe.create(8 + 4 * (size_t)m->n_inputs)) || (rc = m->d_nkept.alloc(2)) || (rc = m->d_unsorted.alloc(m->n_inputs)) || (rc = m->d_tallies.alloc(4))) return rc;
   *out = m.release();
   return JFGPU_OK;
 }
@@ -156,16 +120,7 @@ int jfgpu_merge_create(const jfgpu_merge_params* p, jfgpu_merge** out) {
 void jfgpu_merge_destroy(jfgpu_merge* m) {
   if(!m) return;
   hipSetDevice(m->device);
-  for(hipStream_t s : {m->s_up, m->s_k, m->s_down}) if(s) { hipStreamSynchronize(s); hipStreamDestroy(s); }
-  for(int i = 0; i < 2; ++i) {
-    for(hipEvent_t e : {m->up_a[i], m->up_done[i], m->ev_a[i], m->ev_b[i], m->k_done[i]}) if(e) hipEventDestroy(e);
-    if(m->h_in[i]) hipHostFree(m->h_in[i]);
-    if(m->h_out[i]) hipHostFree(m->h_out[i]);
-    if(m->h_status[i]) hipHostFree(m->h_status[i]);
-    hipFree(m->d_raw[i]); hipFree(m->d_out[i]);
-  }
-  hipFree(m->d_fwd); hipFree(m->d_keys); hipFree(m->d_vals); hipFree(m->d_pos); hipFree(m->d_oval); hipFree(m->d_osrc);
-  hipFree(m->d_bcnt); hipFree(m->d_boff); hipFree(m->d_nkept); hipFree(m->d_unsorted); hipFree(m->d_tallies);
+  m->pipe.sync();
   delete m;
 }
 
@@ -174,8 +129,9 @@ int jfgpu_merge_run(jfgpu_merge* m, const void* const* bodies, const uint64_t* n
   if(!bodies || !n_records) return fail(JFGPU_E_INVALID, "null argument");
   if(m->op != 3 && !sink) return fail(JFGPU_E_INVALID, "merge: no sink");
   for(uint32_t f = 0; f < m->n_inputs; ++f) if(n_records[f] && !bodies[f]) return fail(JFGPU_E_INVALID, "merge: null body");
-  HIP_TRY(hipStreamSynchronize(m->s_up)); HIP_TRY(hipStreamSynchronize(m->s_k)); HIP_TRY(hipStreamSynchronize(m->s_down));   // (a run that failed may have left work behind)
-  for(int i = 0; i < 4; ++i) { m->ms[i] = 0; m->tallies[i] = 0; }
+  WindowPipe& P = m->pipe;
+  rc = P.begin_run(); if(rc) return rc;
+  for(int i = 0; i < 4; ++i) m->tallies[i] = 0;
   m->counts[0] = m->counts[1] = m->counts[2] = 0;
   const uint32_t nf = m->n_inputs, orb = m->kb + m->ocl;
 
@@ -197,34 +153,26 @@ int jfgpu_merge_run(jfgpu_merge* m, const void* const* bodies, const uint64_t* n
     }
   }
 
-  HIP_TRY(hipMemsetAsync(m->d_unsorted, 0, nf * sizeof(uint32_t), m->s_k));
-  HIP_TRY(hipMemsetAsync(m->d_tallies, 0, 4 * sizeof(unsigned long long), m->s_k));
+  HIP_TRY(hipMemsetAsync(m->d_unsorted, 0, nf * sizeof(uint32_t), P.s_k));
+  HIP_TRY(hipMemsetAsync(m->d_tallies, 0, 4 * sizeof(unsigned long long), P.s_k));
 
   const size_t segs_bytes = merge_segs_bytes(m);
   bool sunk = false;
   // the download, the check and the sink of a window whose kernels are enqueued
   auto finish = [&](size_t j) -> int {
     const int slot = (int)(j & 1);
-    HIP_TRY(hipEventSynchronize(m->k_done[slot]));
-    float ms = 0;
-    if(hipEventElapsedTime(&ms, m->ev_a[slot], m->ev_b[slot]) == hipSuccess) m->ms[1] += ms;
-    if(hipEventElapsedTime(&ms, m->up_a[slot], m->up_done[slot]) == hipSuccess) m->ms[0] += ms;
-    const uint32_t* flags = (const uint32_t*)(m->h_status[slot] + 1);
+    int frc = P.wait(slot); if(frc) return frc;
+    const uint64_t* status = P.status_words(slot);
+    const uint32_t* flags = (const uint32_t*)(status + 1);
     for(uint32_t f = 0; f < nf; ++f)
       if(flags[f]) return fail(JFGPU_E_FORMAT, "merge: input " + std::to_string(f) + " is not sorted by (position, key)" + (sunk ? " (output already written)" : ""));
-    const uint64_t nk = m->op == 3 ? 0 : m->h_status[slot][0];
+    const uint64_t nk = m->op == 3 ? 0 : status[0];
     if(nk > wins[j].total) return fail(JFGPU_E_HIP, "merge: the device kept more records than the window holds");
     m->counts[2] += nk;
     if(nk) {
-      auto t0 = std::chrono::steady_clock::now();
-      rc = merge_grow_host(m->h_out[slot], m->h_out_cap[slot], (size_t)nk * orb); if(rc) return rc;
-      HIP_TRY(hipMemcpyAsync(m->h_out[slot], m->d_out[slot], (size_t)nk * orb, hipMemcpyDeviceToHost, m->s_down));
-      HIP_TRY(hipStreamSynchronize(m->s_down));
-      m->ms[2] += merge_wall_ms(t0);
-      t0 = std::chrono::steady_clock::now();
+      frc = P.download(slot, (size_t)nk * orb); if(frc) return frc;
       sunk = true;
-      if(sink(user, m->h_out[slot], nk)) return fail(JFGPU_E_INVALID, "merge: the sink asked to stop");
-      m->ms[3] += merge_wall_ms(t0);
+      if(P.sink([&] { return sink(user, P.slot[slot].h_out, nk); })) return fail(JFGPU_E_INVALID, "merge: the sink asked to stop");
     }
     return JFGPU_OK;
   };
@@ -233,6 +181,7 @@ int jfgpu_merge_run(jfgpu_merge* m, const void* const* bodies, const uint64_t* n
   for(size_t i = 0; i < wins.size(); ++i) {
     const MergeWindow& w = wins[i];
     const int slot = (int)(i & 1);
+    WindowPipe::Slot& S = P.slot[slot];
     if(w.total >= ((uint64_t)1 << 31)) return fail(JFGPU_E_UNSUPPORTED, "merge: one position holds 2^31 records or more");
     // ---- layout of the window's bytes: the segment table, then every input's records from a 16-byte boundary
     size_t in_bytes = segs_bytes;
@@ -249,64 +198,50 @@ int jfgpu_merge_run(jfgpu_merge* m, const void* const* bodies, const uint64_t* n
     }
     const size_t raw_need = in_bytes + 64;                   // the decode reads up to 32 bytes past the last record
     const size_t out_need = (size_t)w.total * orb + 64;
-    if(w.total > m->rec_cap || raw_need > m->raw_cap[slot] || out_need > m->out_cap[slot]) {
+    if(w.total > m->rec_cap || raw_need > S.d_raw.cap() || out_need > S.d_out.cap()) {
       // one position holds more than a window, or the first windows: everything in flight ends, then the buffers grow
       if(pending >= 0) { rc = finish((size_t)pending); pending = -1; if(rc) return rc; }
-      HIP_TRY(hipStreamSynchronize(m->s_up)); HIP_TRY(hipStreamSynchronize(m->s_k));
-      rc = grow_buf(m->d_raw[slot], m->raw_cap[slot], raw_need); if(rc) return rc;
-      rc = grow_buf(m->d_out[slot], m->out_cap[slot], out_need); if(rc) return rc;
+      HIP_TRY(hipStreamSynchronize(P.s_up)); HIP_TRY(hipStreamSynchronize(P.s_k));
+      if((rc = S.d_raw.reserve(raw_need)) || (rc = S.d_out.reserve(out_need))) return rc;
       if(w.total > m->rec_cap) {
         const size_t cap = (size_t)w.total + (size_t)w.total / 8, nb = cap / kMergeBlock + 2;
-        auto renew = [&](auto*& ptr, size_t bytes) -> int {
-          if(ptr) { HIP_TRY(hipFree(ptr)); ptr = nullptr; }
-          HIP_TRY(hipMalloc((void**)&ptr, bytes));
-          return JFGPU_OK;
-        };
         m->rec_cap = 0;
-        if((rc = renew(m->d_keys, cap * m->kw * sizeof(uint64_t))) || (rc = renew(m->d_vals, cap * sizeof(uint64_t))) ||
-           (rc = renew(m->d_pos, cap * sizeof(uint64_t))) || (rc = renew(m->d_oval, cap * sizeof(uint64_t))) ||
-           (rc = renew(m->d_osrc, cap * sizeof(uint32_t))) || (rc = renew(m->d_bcnt, nb * sizeof(uint32_t))) ||
-           (rc = renew(m->d_boff, nb * sizeof(uint64_t)))) return rc;
+        if((rc = m->d_keys.alloc(cap * m->kw)) || (rc = m->d_vals.alloc(cap)) || (rc = m->d_pos.alloc(cap)) || (rc = m->d_oval.alloc(cap)) ||
+           (rc = m->d_osrc.alloc(cap)) || (rc = m->d_bcnt.alloc(nb)) || (rc = m->d_boff.alloc(nb))) return rc;
         m->rec_cap = cap;
       }
     }
     // ---- stage and upload (the kernels of window i - 1 run meanwhile)
-    auto t0 = std::chrono::steady_clock::now();
-    rc = merge_grow_host(m->h_in[slot], m->h_in_cap[slot], in_bytes); if(rc) return rc;
-    memcpy(m->h_in[slot], segs.data(), nf * sizeof(MergeSeg));
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = S.h_in.reserve(in_bytes); if(rc) return rc;
+    memcpy(S.h_in, segs.data(), nf * sizeof(MergeSeg));
     for(uint32_t f = 0; f < nf; ++f)
-      if(segs[f].n) memcpy(m->h_in[slot] + segs_bytes + segs[f].raw_off, (const uint8_t*)bodies[f] + w.lo[f] * segs[f].rb, (size_t)segs[f].n * segs[f].rb);
-    m->ms[0] += merge_wall_ms(t0);
-    HIP_TRY(hipEventRecord(m->up_a[slot], m->s_up));
-    HIP_TRY(hipMemcpyAsync(m->d_raw[slot], m->h_in[slot], in_bytes, hipMemcpyHostToDevice, m->s_up));
-    HIP_TRY(hipEventRecord(m->up_done[slot], m->s_up));
+      if(segs[f].n) memcpy(S.h_in + segs_bytes + segs[f].raw_off, (const uint8_t*)bodies[f] + w.lo[f] * segs[f].rb, (size_t)segs[f].n * segs[f].rb);
+    rc = P.upload(slot, in_bytes, t0); if(rc) return rc;
     // ---- kernels
     MergeWin W;
-    W.segs = (const MergeSeg*)m->d_raw[slot]; W.n_inputs = nf; W.n_tiles = n_tiles; W.total = w.total; W.cap = m->rec_cap;
+    W.segs = (const MergeSeg*)S.d_raw.get(); W.n_inputs = nf; W.n_tiles = n_tiles; W.total = w.total; W.cap = m->rec_cap;
     W.keys = m->d_keys; W.vals = m->d_vals; W.pos = m->d_pos;
-    HIP_TRY(hipStreamWaitEvent(m->s_k, m->up_done[slot], 0));
-    HIP_TRY(hipEventRecord(m->ev_a[slot], m->s_k));
-    const uint8_t* raw = m->d_raw[slot] + segs_bytes;          // the records follow the segment table in the same buffer
+    rc = P.kernels_begin(slot); if(rc) return rc;
+    const uint8_t* raw = S.d_raw + segs_bytes;                 // the records follow the segment table in the same buffer
     switch(m->kw) {
     case 1: merge_launch<1>(m, W, raw, slot); break;
     case 2: merge_launch<2>(m, W, raw, slot); break;
     case 3: merge_launch<3>(m, W, raw, slot); break;
     default: merge_launch<4>(m, W, raw, slot); break;
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(m->ev_b[slot], m->s_k));
-    if(m->op != 3) HIP_TRY(hipMemcpyAsync(m->h_status[slot], m->d_nkept + slot, sizeof(uint64_t), hipMemcpyDeviceToHost, m->s_k));
-    HIP_TRY(hipMemcpyAsync(m->h_status[slot] + 1, m->d_unsorted, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, m->s_k));
-    HIP_TRY(hipEventRecord(m->k_done[slot], m->s_k));
+    rc = P.kernels_end(slot); if(rc) return rc;
+    if(m->op != 3) { rc = P.status(slot, 0, m->d_nkept + slot, sizeof(uint64_t)); if(rc) return rc; }
+    if((rc = P.status(slot, 1, m->d_unsorted, nf * sizeof(uint32_t))) || (rc = P.done(slot))) return rc;
     m->counts[0] += 1; m->counts[1] += w.total;
     // ---- the window before this one: download and sink while this one's kernels run
-    if(pending >= 0) { rc = finish((size_t)pending); pending = -1; if(rc) { hipStreamSynchronize(m->s_k); return rc; } }
+    if(pending >= 0) { rc = finish((size_t)pending); pending = -1; if(rc) { hipStreamSynchronize(P.s_k); return rc; } }
     pending = (long)i;
   }
   if(pending >= 0) { rc = finish((size_t)pending); if(rc) return rc; }
   if(m->op == 3) {
-    HIP_TRY(hipMemcpyAsync(m->tallies, m->d_tallies, sizeof m->tallies, hipMemcpyDeviceToHost, m->s_k));
-    HIP_TRY(hipStreamSynchronize(m->s_k));
+    HIP_TRY(hipMemcpyAsync(m->tallies, m->d_tallies, sizeof m->tallies, hipMemcpyDeviceToHost, P.s_k));
+    HIP_TRY(hipStreamSynchronize(P.s_k));
   }
   return JFGPU_OK;
 }
@@ -319,7 +254,7 @@ int jfgpu_merge_tallies(jfgpu_merge* m, uint64_t out4[4]) {
 
 int jfgpu_merge_last_ms(jfgpu_merge* m, double out4[4]) {
   if(!m || !out4) return fail(JFGPU_E_INVALID, "null argument");
-  for(int i = 0; i < 4; ++i) out4[i] = m->ms[i];
+  for(int i = 0; i < 4; ++i) out4[i] = m->pipe.ms[i];
   return JFGPU_OK;
 }
 

@@ -1,44 +1,32 @@
 // jellyfish_amd/csrc/abi_parser.inl -- C ABI of the device-side sequence parser (jfgpu_parser_*), included by jfgpu.hip.
+// The parser owns its streams, events and buffers (hip_own.hpp): they grow with reserve() and go with the handle.
 // ---- device-side FASTA / FASTQ parse (kernels_parse.hip.hpp) ----------------------------------------
 struct BgzfState;                                          // BGZF / BAM work buffers (abi_sam.inl)
-static void bgzf_state_free(BgzfState* b);
 struct jfgpu_parser {
+  jfgpu_parser();
+  ~jfgpu_parser();                                         // (BgzfState is complete in abi_sam.inl)
   int device = 0;
   uint32_t k = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  uint8_t* d_raw = nullptr; size_t raw_cap = 0;            // host-fed chunks land here
+  Stream stream, copy_stream;                              // copy_stream: created by the first jfgpu_parser_upload
+  Event ev_a, ev_b, up_done[2];
+  DevBuf<uint8_t> d_raw;                                   // host-fed chunks land here
   // pipelined feed (jfgpu_parser_upload / _parse_uploaded): chunk i+1 travels on the copy stream while chunk i is parsed
-  uint8_t* d_up[2] = {nullptr, nullptr}; size_t up_cap[2] = {0, 0}; size_t up_len[2] = {0, 0};
-  hipStream_t copy_stream = nullptr; hipEvent_t up_done[2] = {nullptr, nullptr};
-  uint8_t* d_out[2] = {nullptr, nullptr}; size_t out_cap[2] = {0, 0};
+  DevBuf<uint8_t> d_up[2]; size_t up_len[2] = {0, 0};
+  DevBuf<uint8_t> d_out[2];
   int cur = 0;
-  ParseAgg* d_agg = nullptr; ParseStart* d_start = nullptr; size_t tiles_cap = 0;
-  uint32_t* d_nlpos = nullptr; size_t nlpos_cap = 0;
-  ParseResult* d_res = nullptr;
-  uint8_t* d_carry = nullptr; uint32_t carry_len = 0;      // last k-1 characters of the previous chunk's output
-  char* h_pin[2] = {nullptr, nullptr}; size_t pin_cap[2] = {0, 0};   // pinned host staging for callers that read files
+  DevBuf<ParseAgg> d_agg; DevBuf<ParseStart> d_start;
+  DevBuf<uint32_t> d_nlpos;
+  DevBuf<ParseResult> d_res;
+  DevBuf<uint8_t> d_carry; uint32_t carry_len = 0;         // last k-1 characters of the previous chunk's output
+  PinBuf<char> h_pin[2];                                   // pinned host staging for callers that read files
   double last_ms = 0;
   uint32_t min_qual = 0;                                   // > 0: FASTQ bases with a lower quality character become 'N'
-  BgzfState* bgzf = nullptr;                               // created by the first jfgpu_parser_inflate_uploaded
+  std::unique_ptr<BgzfState> bgzf;                         // created by the first jfgpu_parser_inflate_uploaded
 };
 
 namespace {
 constexpr size_t kOutPad = 256;                             // room for the seam in front of the compacted bytes
-int use_p(const jfgpu_parser* p) {
-  if(!p) return fail(JFGPU_E_INVALID, "null parser");
-  HIP_TRY(hipSetDevice(p->device));
-  return JFGPU_OK;
-}
-template <typename T>
-int grow_buf(T*& ptr, size_t& cap, size_t need) {
-  if(need <= cap) return JFGPU_OK;
-  if(ptr) { HIP_TRY(hipFree(ptr)); ptr = nullptr; cap = 0; }
-  const size_t want = need + need / 8;
-  HIP_TRY(hipMalloc((void**)&ptr, want * sizeof(T)));
-  cap = want;
-  return JFGPU_OK;
-}
+int use_p(const jfgpu_parser* p) { return use_dev(p, "null parser"); }
 }  // namespace
 
 extern "C" {
@@ -47,18 +35,11 @@ int jfgpu_parser_create(int device, uint32_t k, jfgpu_parser** out) {
   if(!out) return fail(JFGPU_E_INVALID, "null argument");
   *out = nullptr;
   if(k < 1 || k > 127) return fail(JFGPU_E_INVALID, "mer length must be in [1, 127]");
-  int ndev = 0;
-  if(hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(JFGPU_E_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-  int dev = device;
-  if(dev < 0) HIP_TRY(hipGetDevice(&dev));
-  if(dev >= ndev) return fail(JFGPU_E_NO_DEVICE, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(dev));
+  int dev = 0;
+  int rc = pick_device(device, &dev); if(rc) return rc;
   std::unique_ptr<jfgpu_parser> p(new jfgpu_parser);
   p->device = dev; p->k = k;
-  HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreate(&p->ev_a)); HIP_TRY(hipEventCreate(&p->ev_b));
-  HIP_TRY(hipMalloc((void**)&p->d_res, sizeof(ParseResult)));
-  HIP_TRY(hipMalloc((void**)&p->d_carry, 256));
+  if((rc = p->stream.create()) || (rc = p->ev_a.create()) || (rc = p->ev_b.create()) || (rc = p->d_res.alloc(1)) || (rc = p->d_carry.alloc(256))) return rc;
   *out = p.release();
   return JFGPU_OK;
 }
@@ -66,16 +47,7 @@ int jfgpu_parser_create(int device, uint32_t k, jfgpu_parser** out) {
 void jfgpu_parser_destroy(jfgpu_parser* p) {
   if(!p) return;
   hipSetDevice(p->device);
-  if(p->stream) hipStreamSynchronize(p->stream);
-  hipFree(p->d_raw); hipFree(p->d_out[0]); hipFree(p->d_out[1]); hipFree(p->d_agg); hipFree(p->d_start);
-  hipFree(p->d_nlpos); hipFree(p->d_res); hipFree(p->d_carry);
-  bgzf_state_free(p->bgzf);
-  if(p->copy_stream) { hipStreamSynchronize(p->copy_stream); hipStreamDestroy(p->copy_stream); }
-  for(int i = 0; i < 2; ++i) { if(p->d_up[i]) hipFree(p->d_up[i]); if(p->up_done[i]) hipEventDestroy(p->up_done[i]); }
-  for(int i = 0; i < 2; ++i) if(p->h_pin[i]) hipHostFree(p->h_pin[i]);
-  if(p->ev_a) hipEventDestroy(p->ev_a);
-  if(p->ev_b) hipEventDestroy(p->ev_b);
-  if(p->stream) hipStreamDestroy(p->stream);
+  p->stream.sync(); p->copy_stream.sync();
   delete p;
 }
 
@@ -95,15 +67,10 @@ int jfgpu_parser_parse_dev(jfgpu_parser* p, const char* d_bytes, size_t n, unsig
   align_buffer(d_bytes, n, base, lo, hi);
   const int64_t nt = (hi + kParseTile - 1) / kParseTile;
   const int w = p->cur; p->cur ^= 1;
-  rc = grow_buf(p->d_out[w], p->out_cap[w], kOutPad + n + 64); if(rc) return rc;
-  if((size_t)nt > p->tiles_cap) {
-    size_t c1 = p->tiles_cap, c2 = p->tiles_cap;
-    rc = grow_buf(p->d_agg, c1, (size_t)nt); if(rc) return rc;
-    rc = grow_buf(p->d_start, c2, (size_t)nt); if(rc) return rc;
-    p->tiles_cap = std::min(c1, c2);
-  }
+  rc = p->d_out[w].reserve(kOutPad + n + 64); if(rc) return rc;
+  if((rc = p->d_agg.reserve((size_t)nt)) || (rc = p->d_start.reserve((size_t)nt))) return rc;
   const uint64_t max_lines = n / 8 + 16;                     // FASTQ chunks with shorter lines go to the host parser
-  if(fmt == JFGPU_PARSE_FASTQ) { rc = grow_buf(p->d_nlpos, p->nlpos_cap, (size_t)max_lines); if(rc) return rc; }
+  if(fmt == JFGPU_PARSE_FASTQ) { rc = p->d_nlpos.reserve((size_t)max_lines); if(rc) return rc; }
   uint8_t* out0 = p->d_out[w] + kOutPad;
   HIP_TRY(hipMemsetAsync(p->d_res, 0, sizeof(ParseResult), p->stream));
   HIP_TRY(hipEventRecord(p->ev_a, p->stream));
@@ -184,10 +151,10 @@ int jfgpu_parser_parse(jfgpu_parser* p, const char* bytes, size_t n, unsigned fl
   if(n && !bytes) return fail(JFGPU_E_INVALID, "null buffer");
   if(n > ((size_t)1 << 31)) return fail(JFGPU_E_INVALID, "chunk larger than 2^31 bytes");
   if(n) {
-    rc = grow_buf(p->d_raw, p->raw_cap, n + 64); if(rc) return rc;
+    rc = p->d_raw.reserve(n + 64); if(rc) return rc;
     HIP_TRY(hipMemcpyAsync(p->d_raw, bytes, n, hipMemcpyHostToDevice, p->stream));
   }
-  return jfgpu_parser_parse_dev(p, (const char*)p->d_raw, n, flags, d_out, n_out, n_records);
+  return jfgpu_parser_parse_dev(p, (const char*)p->d_raw.get(), n, flags, d_out, n_out, n_records);
 }
 
 // Pipelined form of jfgpu_parser_parse for callers that read files: upload(which) enqueues the host-to-device copy of
@@ -198,13 +165,11 @@ int jfgpu_parser_upload(jfgpu_parser* p, int which, const char* bytes, size_t n)
   int rc = use_p(p); if(rc) return rc;
   if(which < 0 || which > 1 || (n && !bytes)) return fail(JFGPU_E_INVALID, "bad argument");
   if(n > ((size_t)1 << 31)) return fail(JFGPU_E_INVALID, "chunk larger than 2^31 bytes");
-  if(!p->copy_stream) {
-    HIP_TRY(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
-    for(int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&p->up_done[i], hipEventDisableTiming));
-  }
-  if(n + 64 > p->up_cap[which]) {
+  if(!p->copy_stream && (rc = p->copy_stream.create())) return rc;
+  for(int i = 0; i < 2; ++i) if(!p->up_done[i] && (rc = p->up_done[i].create(hipEventDisableTiming))) return rc;
+  if(n + 64 > p->d_up[which].cap()) {
     HIP_TRY(hipStreamSynchronize(p->copy_stream)); HIP_TRY(hipStreamSynchronize(p->stream));
-    rc = grow_buf(p->d_up[which], p->up_cap[which], n + 64); if(rc) return rc;
+    rc = p->d_up[which].reserve(n + 64); if(rc) return rc;
   }
   if(n) HIP_TRY(hipMemcpyAsync(p->d_up[which], bytes, n, hipMemcpyHostToDevice, p->copy_stream));
   HIP_TRY(hipEventRecord(p->up_done[which], p->copy_stream));
@@ -223,18 +188,14 @@ int jfgpu_parser_parse_uploaded(jfgpu_parser* p, int which, unsigned flags, cons
   int rc = use_p(p); if(rc) return rc;
   if(which < 0 || which > 1 || !p->copy_stream) return fail(JFGPU_E_INVALID, "nothing was uploaded");
   HIP_TRY(hipStreamWaitEvent(p->stream, p->up_done[which], 0));
-  return jfgpu_parser_parse_dev(p, (const char*)p->d_up[which], p->up_len[which], flags, d_out, n_out, n_records);
+  return jfgpu_parser_parse_dev(p, (const char*)p->d_up[which].get(), p->up_len[which], flags, d_out, n_out, n_records);
 }
 
 int jfgpu_parser_host_buffer(jfgpu_parser* p, int which, size_t bytes, char** out) {
   int rc = use_p(p); if(rc) return rc;
   if(!out || which < 0 || which > 1) return fail(JFGPU_E_INVALID, "bad argument");
   *out = nullptr;
-  if(bytes > p->pin_cap[which]) {
-    if(p->h_pin[which]) { HIP_TRY(hipHostFree(p->h_pin[which])); p->h_pin[which] = nullptr; p->pin_cap[which] = 0; }
-    HIP_TRY(hipHostMalloc((void**)&p->h_pin[which], bytes, hipHostMallocDefault));
-    p->pin_cap[which] = bytes;
-  }
+  if(bytes > p->h_pin[which].cap()) { rc = p->h_pin[which].alloc(bytes); if(rc) return rc; }
   *out = p->h_pin[which];
   return JFGPU_OK;
 }

@@ -1,54 +1,34 @@
 // jellyfish_amd/csrc/abi_sam.inl -- C ABI of the BGZF inflate, the BAM record decode and the inflated FASTA / FASTQ stream
 // (jfgpu_bgzf_scan, jfgpu_parser_inflate_uploaded, _stream_read, _stream_consume, _bam_decode, _stream_cut, _stream_parse),
-// included by jfgpu.hip after abi_parser.inl.
+// included by jfgpu.hip after abi_parser.inl.  BgzfState, the parser's BGZF / BAM work buffers, owns them (hip_own.hpp) and
+// goes with the parser.
 struct BgzfState {
-  uint8_t* d_stream[2] = {nullptr, nullptr}; size_t stream_cap[2] = {0, 0};
+  DevBuf<uint8_t> d_stream[2];
   int scur = 0; size_t stream_len = 0;                     // inflated bytes not yet consumed, in d_stream[scur]
-  jfgpu_bgzf_block* d_blocks = nullptr; size_t blocks_cap = 0;
-  unsigned long long* d_err = nullptr;
-  unsigned long long* d_cut = nullptr;                     // result of stream_cut_kernel
-  BamSeg* d_seg = nullptr; size_t seg_cap = 0;
-  uint64_t* d_want = nullptr; size_t want_cap = 0;
-  uint64_t* d_rec_off = nullptr; size_t rec_off_cap = 0;
-  uint64_t* d_out_off = nullptr; size_t out_off_cap = 0;
-  uint64_t* d_rec_start = nullptr; size_t rec_start_cap = 0;
-  uint64_t* d_rec_out = nullptr; size_t rec_out_cap = 0;
-  BamTotals* d_tot = nullptr;
+  DevBuf<jfgpu_bgzf_block> d_blocks;
+  DevBuf<unsigned long long> d_err;
+  DevBuf<unsigned long long> d_cut;                        // result of stream_cut_kernel
+  DevBuf<BamSeg> d_seg;
+  DevBuf<uint64_t> d_want, d_rec_off, d_out_off, d_rec_start, d_rec_out;
+  DevBuf<BamTotals> d_tot;
   bool lds_set = false;
 };
-
-static void bgzf_state_free(BgzfState* b) {
-  if(!b) return;
-  hipFree(b->d_stream[0]); hipFree(b->d_stream[1]); hipFree(b->d_blocks); hipFree(b->d_err); hipFree(b->d_cut); hipFree(b->d_seg); hipFree(b->d_want);
-  hipFree(b->d_rec_off); hipFree(b->d_out_off); hipFree(b->d_rec_start); hipFree(b->d_rec_out); hipFree(b->d_tot);
-  delete b;
-}
+jfgpu_parser::jfgpu_parser() = default;
+jfgpu_parser::~jfgpu_parser() = default;
 
 namespace {
 
 int bgzf_state(jfgpu_parser* p) {
   if(p->bgzf) return JFGPU_OK;
   std::unique_ptr<BgzfState> b(new BgzfState);
-  HIP_TRY(hipMalloc((void**)&b->d_err, sizeof(unsigned long long)));
-  HIP_TRY(hipMalloc((void**)&b->d_tot, sizeof(BamTotals)));
-  HIP_TRY(hipMalloc((void**)&b->d_cut, sizeof(unsigned long long)));
-  p->bgzf = b.release();
+  int rc;
+  if((rc = b->d_err.alloc(1)) || (rc = b->d_tot.alloc(1)) || (rc = b->d_cut.alloc(1))) return rc;
+  p->bgzf = std::move(b);
   return JFGPU_OK;
 }
 
 // the stream buffer `w` holds at least `need` bytes; its first `keep` bytes survive a reallocation
-int stream_reserve(jfgpu_parser* p, int w, size_t keep, size_t need) {
-  BgzfState& b = *p->bgzf;
-  if(need <= b.stream_cap[w]) return JFGPU_OK;
-  const size_t want = need + need / 4 + 4096;
-  uint8_t* fresh = nullptr;
-  HIP_TRY(hipMalloc((void**)&fresh, want));
-  if(keep) HIP_TRY(hipMemcpyAsync(fresh, b.d_stream[w], keep, hipMemcpyDeviceToDevice, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  if(b.d_stream[w]) HIP_TRY(hipFree(b.d_stream[w]));
-  b.d_stream[w] = fresh; b.stream_cap[w] = want;
-  return JFGPU_OK;
-}
+int stream_reserve(jfgpu_parser* p, int w, size_t keep, size_t need) { return p->bgzf->d_stream[w].reserve_keep(keep, need, p->stream); }
 
 const char* inflate_reason(uint32_t code) {
   switch(code) {
@@ -125,7 +105,7 @@ int jfgpu_parser_inflate_uploaded(jfgpu_parser* p, int which, const jfgpu_bgzf_b
   const int w = b.scur;
   rc = stream_reserve(p, w, b.stream_len, b.stream_len + total + 64); if(rc) return rc;
   if(n_blocks) {
-    rc = grow_buf(b.d_blocks, b.blocks_cap, n_blocks); if(rc) return rc;
+    rc = b.d_blocks.reserve(n_blocks); if(rc) return rc;
     if(!b.lds_set) { HIP_TRY(hipFuncSetAttribute((const void*)bgzf_inflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kInfLds)); b.lds_set = true; }
     HIP_TRY(hipStreamWaitEvent(p->stream, p->up_done[which], 0));
     HIP_TRY(hipMemcpyAsync(b.d_blocks, blocks, n_blocks * sizeof(jfgpu_bgzf_block), hipMemcpyHostToDevice, p->stream));
@@ -196,9 +176,7 @@ int jfgpu_parser_bam_decode(jfgpu_parser* p, size_t skip, int32_t n_ref, const c
   BamTotals tot = {0, 0, skip, 0, 0};
   if(nseg) {
     const uint8_t* S = b.d_stream[b.scur];
-    if((rc = grow_buf(b.d_seg, b.seg_cap, nseg)) || (rc = grow_buf(b.d_want, b.want_cap, nseg)) ||
-       (rc = grow_buf(b.d_rec_off, b.rec_off_cap, nseg)) || (rc = grow_buf(b.d_out_off, b.out_off_cap, nseg)))
-      return rc;
+    if((rc = b.d_seg.reserve(nseg)) || (rc = b.d_want.reserve(nseg)) || (rc = b.d_rec_off.reserve(nseg)) || (rc = b.d_out_off.reserve(nseg))) return rc;
     HIP_TRY(hipEventRecord(p->ev_a, p->stream));
     hipLaunchKernelGGL(bam_guess_kernel, dim3((nseg + 255) / 256), dim3(256), 0, p->stream, S, n, (uint64_t)skip, nseg, n_ref, b.d_seg);
     hipLaunchKernelGGL(bam_fix_kernel, dim3(1), dim3(1024), 0, p->stream, S, n, (uint64_t)skip, nseg, b.d_seg, b.d_want, b.d_rec_off, b.d_out_off, b.d_tot);
@@ -208,15 +186,13 @@ int jfgpu_parser_bam_decode(jfgpu_parser* p, size_t skip, int32_t n_ref, const c
     if(tot.bad) return fail(JFGPU_E_CORRUPT, "BAM record whose lengths do not add up (corrupt stream)");
     if(tot.recs) {
       const int w = p->cur; p->cur ^= 1;
-      if((rc = grow_buf(b.d_rec_start, b.rec_start_cap, tot.recs)) || (rc = grow_buf(b.d_rec_out, b.rec_out_cap, tot.recs)) ||
-         (rc = grow_buf(p->d_out[w], p->out_cap[w], tot.out + 64)))
-        return rc;
+      if((rc = b.d_rec_start.reserve(tot.recs)) || (rc = b.d_rec_out.reserve(tot.recs)) || (rc = p->d_out[w].reserve(tot.out + 64))) return rc;
       hipLaunchKernelGGL(bam_list_kernel, dim3((nseg + 255) / 256), dim3(256), 0, p->stream, S, n, (uint64_t)skip, nseg, b.d_seg, b.d_rec_off, b.d_out_off,
                          b.d_rec_start, b.d_rec_out);
       const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((tot.recs + 3) / 4, 16384));
       hipLaunchKernelGGL(bam_emit_kernel, dim3(grid), dim3(256), 0, p->stream, S, tot.recs, b.d_rec_start, b.d_rec_out, p->min_qual, p->d_out[w]);
       HIP_TRY(hipGetLastError());
-      *d_out = (const char*)p->d_out[w]; *n_out = tot.out;
+      *d_out = (const char*)p->d_out[w].get(); *n_out = tot.out;
     }
     HIP_TRY(hipEventRecord(p->ev_b, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
@@ -260,7 +236,7 @@ int jfgpu_parser_stream_parse(jfgpu_parser* p, size_t n, unsigned flags, const c
   if(n > ((size_t)1 << 31)) return fail(JFGPU_E_INVALID, "chunk larger than 2^31 bytes");
   if(n > have) return fail(JFGPU_E_INVALID, "parse past the inflated stream");
   // (the stream buffer is an allocation's start: 16-byte aligned, as parse_dev's vector loads like it)
-  rc = jfgpu_parser_parse_dev(p, n ? (const char*)p->bgzf->d_stream[p->bgzf->scur] : nullptr, n, flags, d_out, n_out, n_records);
+  rc = jfgpu_parser_parse_dev(p, n ? (const char*)p->bgzf->d_stream[p->bgzf->scur].get() : nullptr, n, flags, d_out, n_out, n_records);
   if(rc) return rc;                                            // JFGPU_E_FORMAT: nothing consumed, the bytes can be read back
   const double ms = p->last_ms;
   rc = jfgpu_parser_stream_consume(p, n); if(rc) return rc;

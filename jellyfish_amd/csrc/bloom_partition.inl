@@ -1,16 +1,16 @@
 // jellyfish_amd/csrc/bloom_partition.inl -- host orchestration of the partitioned Bloom insert
 // (kernels_bloom_part.hip.hpp): geometry, workspace arena, P1b ingestion in pieces, the flush (P2 + segment kernel).
-// Included by abi_bloom.inl inside its anonymous namespace.
+// Included by abi_bloom.inl inside its anonymous namespace.  Everything allocated here is a member of jfgpu_bloom (an owner).
 
 constexpr size_t kBloomMinPiece = (size_t)1 << 20;        // bytes of sequence: smaller pieces take the direct kernel
 enum BloomSlot { BS_DIRECT = 0, BS_P1 = 1, BS_P2 = 2, BS_SEG = 3, BS_P2RING = 4, BS_COUNT = 5 };      // (BS_P2RING: launches of the ring P2 only, inside BS_P2's time)
 
 struct BloomProf {      // HIP-event pair around a group of launches on the Bloom counter's stream
-  jfgpu_bloom* b; int which; uint64_t units; hipEvent_t a = nullptr, e = nullptr;
+  jfgpu_bloom* b; int which; uint64_t units; Event a, e;
   BloomProf(jfgpu_bloom* b_, int w, uint64_t u) : b(b_), which(w), units(u) {
-    if(b->prof_on) { hipEventCreate(&a); hipEventCreate(&e); hipEventRecord(a, b->stream); }
+    if(b->prof_on) { (void)a.create(); (void)e.create(); hipEventRecord(a, b->stream); }
   }
-  ~BloomProf() { if(b->prof_on) { hipEventRecord(e, b->stream); b->spans.push_back({a, e, which, units}); } }
+  ~BloomProf() { if(b->prof_on) { hipEventRecord(e, b->stream); b->spans.push_back({std::move(a), std::move(e), which, units}); } }
 };
 
 void bloom_prof_collect(jfgpu_bloom* b) {
@@ -18,7 +18,6 @@ void bloom_prof_collect(jfgpu_bloom* b) {
     float ms = 0;
     hipEventSynchronize(s.b);
     if(hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) { b->prof_ms[s.which] += ms; b->prof_launches[s.which] += 1; b->prof_units[s.which] += s.units; }
-    hipEventDestroy(s.a); hipEventDestroy(s.b);
   }
   b->spans.clear();
 }
@@ -56,13 +55,13 @@ int bloom_ws_ensure(jfgpu_bloom* b, size_t want) {
   if(!b->pending.empty()) return JFGPU_OK;                    // never reallocate under pending batches
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipStreamSynchronize(b->stream));
-  if(b->ws) { hipFree(b->ws); b->ws = nullptr; b->ws_cap = 0; }
+  (void)b->ws.reset(); b->ws_cap = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   const size_t keep = (size_t)4 << 30;
   size_t cap = want ? want : (size_t)96 << 30;
   if(free_b < keep + ((size_t)256 << 20)) return -1;
   cap = std::min(cap, free_b - keep);
-  if(hipMalloc((void**)&b->ws, cap) != hipSuccess) { (void)hipGetLastError(); b->ws = nullptr; return -1; }
+  if(!b->ws.try_alloc(cap)) { (void)hipGetLastError(); return -1; }
   b->ws_cap = cap; b->ws_used = 0;
   HIP_TRY(hipMemsetAsync(b->ws, 0, cap, b->stream));          // first touch now, not inside the first pass
   return JFGPU_OK;
@@ -108,9 +107,9 @@ int bloom_ingest(jfgpu_bloom* b, const uint8_t* base, int64_t lo, int64_t hi) {
     if(ring && b->bp.b1 <= 9 && b->bp.b2 > 0 && (used >= 200 || ring >= 2) && b->g.nbytes <= 8) {
       b->p1_ring_per = ring == 2 ? 10 : ring == 3 ? 5 : used >= 400 ? 10 : 5;
       b->g1 = 2 * b->n_cu;
-      if(!b->d_strag1) {
-        HIP_TRY(hipMalloc((void**)&b->d_strag1, (size_t)b->n_cu * kStragPerBlock * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc((void**)&b->d_strag1_n, (size_t)b->n_cu * sizeof(uint32_t)));
+      if(!b->d_strag1 || !b->d_strag1_n) {
+        int rc;
+        if((rc = b->d_strag1.alloc((size_t)b->n_cu * kStragPerBlock)) || (rc = b->d_strag1_n.alloc((size_t)b->n_cu))) return rc;
       }
     }
   }
@@ -221,7 +220,7 @@ int bloom_flush_inner(jfgpu_bloom* b) {
     launch_segments(S1, std::min<uint32_t>(nb1, b->bp.n_seg), total);
   } else {
     const int g2 = 32;
-    if(!b->d_M2) HIP_TRY(hipMalloc((void**)&b->d_M2, (size_t)nb1 * g2 * nb2 * sizeof(uint32_t)));
+    if(!b->d_M2) { const int rc = b->d_M2.alloc((size_t)nb1 * g2 * nb2); if(rc) return rc; }
     const uint64_t n_tiles = (uint64_t)nb1 * nb2;
     uint64_t* d_goff = (uint64_t*)bloom_ws_alloc(b, (n_tiles + 1) * sizeof(uint64_t));
     uint64_t* d_base = (uint64_t*)bloom_ws_alloc(b, nb1 * sizeof(uint64_t));
@@ -292,9 +291,9 @@ int bloom_flush_inner(jfgpu_bloom* b) {
           if(n_ring) {
             const uint32_t n_lists = roles ? n_ring : kG2Single * n_ring;
             if(!b->d_strag2 || b->strag2_lists < n_lists) {
-              if(b->d_strag2) { hipFree(b->d_strag2); hipFree(b->d_strag2_n); b->d_strag2 = nullptr; b->d_strag2_n = nullptr; }
-              HIP_TRY(hipMalloc((void**)&b->d_strag2, (size_t)n_lists * kP2StragPerBlock * sizeof(uint64_t)));
-              HIP_TRY(hipMalloc((void**)&b->d_strag2_n, (size_t)n_lists * sizeof(uint32_t)));
+              (void)b->d_strag2.reset(); (void)b->d_strag2_n.reset();
+              int rc;
+              if((rc = b->d_strag2.alloc((size_t)n_lists * kP2StragPerBlock)) || (rc = b->d_strag2_n.alloc(n_lists))) return rc;
               b->strag2_lists = n_lists;
             }
             const BloomRingDirect RD{B.data};

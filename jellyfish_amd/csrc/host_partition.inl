@@ -1,6 +1,7 @@
 // jellyfish_amd/csrc/host_partition.inl -- host orchestration of the partitioned insert path (kernels_part.hip.hpp):
 // workspace arena, P1 ingestion of a batch, the flush (P2 + tile insert).  Included by jfgpu.hip inside its
-// anonymous namespace.
+// anonymous namespace.  What lives across calls (the arena, M1 / M2, the straggler lists, the second stream) is a member of
+// jfgpu_table and owned by it; what a flush allocates for itself when the arena has no room is a local DevBuf (hip_own.hpp).
 // ---- partitioned insert path: host orchestration (kernels_part.hip.hpp) -------------------
 constexpr uint64_t kPartMinBytes = 1u << 20;   // AUTO: smaller device batches take the direct kernel
 
@@ -27,7 +28,7 @@ size_t item_size(const jfgpu_table* t) { return t->item128 ? 16 : t->item32 ? 4 
 // The table's descriptor in device memory, for kernels that leave their hot loop through a real call (item_direct_call):
 // refreshed in stream order before every launch that uses it.
 int refresh_d_dt(jfgpu_table* t) {
-  if(!t->d_dt) HIP_TRY(hipMalloc((void**)&t->d_dt, sizeof(DevTable)));
+  if(!t->d_dt) { const int rc = t->d_dt.alloc(1); if(rc) return rc; }
   HIP_TRY(hipMemcpyAsync(t->d_dt, &t->dt, sizeof(DevTable), hipMemcpyHostToDevice, t->stream));
   return JFGPU_OK;
 }
@@ -42,12 +43,12 @@ int ws_grow(jfgpu_table* t, size_t need) {
   size_t want = std::max(need + need / 8, t->ws_cap * 2);
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipStreamSynchronize(t->stream));
-  if(t->ws) { hipFree(t->ws); t->ws = nullptr; t->ws_cap = 0; }
+  (void)t->ws.reset(); t->ws_cap = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   const size_t keep = (size_t)2 << 30;                      // leave room for the caller's buffers
   if(want + keep > free_b) want = need;
   if(want + keep / 2 > free_b) return -1;
-  HIP_TRY(hipMalloc((void**)&t->ws, want));
+  { const int rc = t->ws.alloc(want); if(rc) return rc; }
   t->ws_cap = want;
   return JFGPU_OK;
 }
@@ -112,23 +113,24 @@ int launch_p2_rings(jfgpu_table* t, uint32_t b2e, uint32_t tag_bits, const SegLi
   const bool roles = p2_rings_roles(t, b2e, nbk);
   *dense = roles;
   const uint32_t n_lists = roles ? nbk : kG2Blocks * nbk;
-  if(!t->d_strag2 || t->strag2_lists < n_lists) {
-    if(t->d_strag2) { hipFree(t->d_strag2); hipFree(t->d_strag2_n); t->d_strag2 = nullptr; t->d_strag2_n = nullptr; }
-    HIP_TRY(hipMalloc((void**)&t->d_strag2, (size_t)n_lists * kP2StragPerBlock * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc((void**)&t->d_strag2_n, (size_t)n_lists * sizeof(uint32_t)));
+  if(!t->d_strag2 || !t->d_strag2_n || t->strag2_lists < n_lists) {
+    t->strag2_lists = 0;
+    (void)t->d_strag2.reset(); (void)t->d_strag2_n.reset();
+    int rc;
+    if((rc = t->d_strag2.alloc((size_t)n_lists * kP2StragPerBlock)) || (rc = t->d_strag2_n.alloc(n_lists))) return rc;
     t->strag2_lists = n_lists;
   }
   const P2RingDirect pd{t->d_dt, t->pg.b2, b2e, (int)rt};
   unsigned long long* ctr = (unsigned long long*)&t->dt.counters[CTR_DIRECT];
   const size_t lds = ((size_t)1 << b2e) * 128 + 128;
   if(roles) ++t->n_p2_roles; else ++t->n_p2_ring;
-#define P2R(NV, PD) hipLaunchKernelGGL((p2_ring_roles_kernel<uint32_t, NV, P2RingDirect, PD>), dim3(nbk), dim3(kPBlock), lds, t->stream, pd, b2e, tag_bits, S1, cap2, d_gcur2, out_v, b0, t->d_strag2, t->d_strag2_n, ctr)
+#define P2R(NV, PD) hipLaunchKernelGGL((p2_ring_roles_kernel<uint32_t, NV, P2RingDirect, PD>), dim3(nbk), dim3(kPBlock), lds, t->stream, pd, b2e, tag_bits, S1, cap2, d_gcur2, out_v, b0, t->d_strag2.get(), t->d_strag2_n.get(), ctr)
   if(roles && b2e == 10) { if(t->tun.p2_depth == 1) P2R(2, 1); else if(t->tun.p2_depth == 2) P2R(2, 2); else P2R(2, 3); }
   else if(roles) { if(t->tun.p2_depth == 1) P2R(1, 1); else if(t->tun.p2_depth == 2) P2R(1, 2); else P2R(1, 3); }
 #undef P2R
   else
     hipLaunchKernelGGL((p2_ring_kernel<P2RingDirect>), dim3(kG2Blocks, nbk), dim3(kPBlock), lds, t->stream, pd, b2e, tag_bits, S1, cap2, d_gcur2, d_gcur2 + n_dest,
-                       out_v, b0, (unsigned long long*)nullptr, t->d_strag2, t->d_strag2_n, ctr);
+                       out_v, b0, (unsigned long long*)nullptr, t->d_strag2.get(), t->d_strag2_n.get(), ctr);
   hipLaunchKernelGGL((p1_stragglers_kernel<uint32_t, P2RingDirect>), dim3(t->n_cu), dim3(256), 0, t->stream, pd, ctr, (const uint64_t*)t->d_strag2, (const uint32_t*)t->d_strag2_n,
                      n_lists, cap2, d_gcur2, (unsigned long long*)nullptr, out_v, kP2StragPerBlock);
   if(t->tun.flush_trace) return trace_strag_lists(t->stream, t->d_strag2_n, n_lists, kP2StragPerBlock, roles ? 1 : kG2Blocks, b0);
@@ -136,10 +138,10 @@ int launch_p2_rings(jfgpu_table* t, uint32_t b2e, uint32_t tag_bits, const SegLi
 }
 
 int ensure_strag(jfgpu_table* t) {
-  if(t->d_strag) return JFGPU_OK;
+  if(t->d_strag && t->d_strag_n) return JFGPU_OK;
   const size_t words = Ring<uint32_t>::kWords;
-  HIP_TRY(hipMalloc((void**)&t->d_strag, (size_t)t->n_cu * kStragPerBlock * words * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc((void**)&t->d_strag_n, (size_t)t->n_cu * sizeof(uint32_t)));
+  int rc;
+  if((rc = t->d_strag.alloc((size_t)t->n_cu * kStragPerBlock * words)) || (rc = t->d_strag_n.alloc((size_t)t->n_cu))) return rc;
   return JFGPU_OK;
 }
 
@@ -176,7 +178,7 @@ int bloom_cache_enable(jfgpu_table* t) {
   uint32_t lg = t->tun.bloom_cache_log2;
   while(lg > 16 && ((size_t)16 << lg) + ((size_t)6 << 30) > free_b) --lg;
   if(((size_t)16 << lg) + ((size_t)1 << 30) > free_b && lg > 16) return JFGPU_OK;
-  if(hipMalloc((void**)&t->d_bcache, (size_t)16 << lg) != hipSuccess) { (void)hipGetLastError(); t->d_bcache = nullptr; return JFGPU_OK; }
+  if(!t->d_bcache.try_alloc((size_t)2 << lg)) { (void)hipGetLastError(); return JFGPU_OK; }
   HIP_TRY(hipMemsetAsync(t->d_bcache, 0, (size_t)16 << lg, t->stream));
   t->dt.bloom.cache = t->d_bcache; t->dt.bloom.cache_mask = ((uint64_t)1 << lg) - 1;
   t->bcache_state = 1;
@@ -211,7 +213,7 @@ int part_ingest(jfgpu_table* t, const uint8_t* base, int64_t lo, int64_t hi, boo
   const uint32_t nb = 1u << t->pg.b1;
   if(!t->d_M1) {
     t->g1 = 2 * t->n_cu;   // two 1024-thread blocks per CU: one stages while the other computes
-    HIP_TRY(hipMalloc((void**)&t->d_M1, (size_t)t->g1 * kMaxBuckets * sizeof(uint32_t)));
+    const int rc = t->d_M1.alloc((size_t)t->g1 * kMaxBuckets); if(rc) return rc;
   }
   if(t->pending.size() >= kMaxSeg) { int rc = part_flush(t); if(rc) return rc; }
   // 16-byte items: the arena is what limits the k-mers per flush, and every flush streams the whole table.  Before the
@@ -296,7 +298,7 @@ int part_ingest(jfgpu_table* t, const uint8_t* base, int64_t lo, int64_t hi, boo
       else if(t->g.nbytes == 8) PK(false, 8);
       else PK(false, 0);
     } else
-#define PG(IT, BL, N, CN) hipLaunchKernelGGL((p1_ring_kernel<IT, BL, N, CN>), dim3(t->n_cu), dim3(kPBlock), (size_t)nb * 128 + 128, t->stream, t->dt, od, t->pg, base, lo, hi, gcap, gcur, b.tot, (IT*)b.items, t->d_strag, t->d_strag_n)
+#define PG(IT, BL, N, CN) hipLaunchKernelGGL((p1_ring_kernel<IT, BL, N, CN>), dim3(t->n_cu), dim3(kPBlock), (size_t)nb * 128 + 128, t->stream, t->dt, od, t->pg, base, lo, hi, gcap, gcur, b.tot, (IT*)b.items, t->d_strag.get(), t->d_strag_n.get())
     {
       // what cannot be stored in a region (p1_stragglers_kernel) reads the table's descriptor from device memory
       { int rc = refresh_d_dt(t); if(rc) return rc; }
@@ -521,9 +523,11 @@ int part_flush_t(jfgpu_table* t) {
   } else {
     // breadth-first: every P1 bucket through P2 in one launch per pass, then every tile in one launch
     const int g2 = 32;
-    if(!t->d_M2) HIP_TRY(hipMalloc((void**)&t->d_M2, (size_t)nb1 * g2 * nb2 * sizeof(uint32_t)));
+    if(!t->d_M2) { const int rc = t->d_M2.alloc((size_t)nb1 * g2 * nb2); if(rc) return rc; }
     ITEM* tmp = nullptr; uint64_t *d_goff = nullptr, *d_base = nullptr;
-    bool tmp_owned = false;
+    // one-off blocks for when the arena has no room: tmp / d_goff / d_base, and the regions d_gcur2 / d_off2 / out2 point into
+    // these.  They go when the flush returns, whichever way (hipFree waits for the kernels still reading them).
+    DevBuf<ITEM> own_tmp, own_out2; DevBuf<uint64_t> own_goff, own_base, own_off2; DevBuf<unsigned int> own_gcur2;
     // 32-bit items into 32-bit slots: P2 routes to pairs of adjacent tiles (half as many destinations, and chunks of 28 Ki
     // items), so the runs it writes are ~112 bytes on average instead of 32; the tile kernel owns a pair (64 KiB) in LDS
     const bool pair = sizeof(ITEM) == 4 && t->g.slot32 && t->pg.b2 >= 1 && t->tun.tile_pair;
@@ -533,7 +537,7 @@ int part_flush_t(jfgpu_table* t) {
     // what is pending, the P1 buckets go through P2 and the tile insert in `single_groups` groups sharing one buffer.
     constexpr uint32_t kG2Single = 4;                       // blocks per P1 bucket
     constexpr bool kSingleItems = sizeof(ITEM) == 4 || sizeof(ITEM) == 8 || sizeof(ITEM) == 16;
-    uint32_t cap2 = 0, single_groups = 1; unsigned int* d_gcur2 = nullptr; uint64_t* d_off2 = nullptr; ITEM* out2 = nullptr; bool own2 = false;
+    uint32_t cap2 = 0, single_groups = 1; unsigned int* d_gcur2 = nullptr; uint64_t* d_off2 = nullptr; ITEM* out2 = nullptr;
     // (4-byte items: pairs only; 8- and 16-byte items: single tiles.  The single-pass kernel places one destination per thread
     // (GranuleLds: kGranMaxB = 1024); from 2^34 slots on b2 is 11, and what is not routed to pairs takes the exact scheme,
     // whose kernels go to kMaxBuckets = 2048 destinations)
@@ -575,10 +579,9 @@ int part_flush_t(jfgpu_table* t) {
           t->ws_used = mark;
           d_gcur2 = nullptr; d_off2 = nullptr; out2 = nullptr;
           single_groups = forced && forced <= nb1 / 8 ? forced : 1;
-          if(t->tun.p2_single > 1 && hipMalloc((void**)&d_gcur2, 2 * n_dest * sizeof(unsigned int)) == hipSuccess &&
-             hipMalloc((void**)&d_off2, 2 * n_dest * sizeof(uint64_t)) == hipSuccess &&
-             hipMalloc((void**)&out2, (n_dest / single_groups) * cap2 * sizeof(ITEM)) == hipSuccess) own2 = true;
-          else { if(d_gcur2) hipFree(d_gcur2); if(d_off2) hipFree(d_off2); if(out2) hipFree(out2); cap2 = 0; single_groups = 1; }
+          if(t->tun.p2_single > 1 && own_gcur2.try_alloc(2 * n_dest) && own_off2.try_alloc(2 * n_dest) && own_out2.try_alloc((n_dest / single_groups) * cap2)) {
+            d_gcur2 = own_gcur2; d_off2 = own_off2; out2 = own_out2;
+          } else { (void)own_gcur2.reset(); (void)own_off2.reset(); (void)own_out2.reset(); cap2 = 0; single_groups = 1; }
         }
         if(cap2) HIP_TRY(hipMemsetAsync(d_gcur2, 0, 2 * n_dest * sizeof(unsigned int), t->stream));
       }
@@ -609,14 +612,9 @@ int part_flush_t(jfgpu_table* t) {
       tmp = (ITEM*)ws_alloc(t, tmp_items * sizeof(ITEM));
       if(!d_goff || !d_base || !tmp) {     // arena too small for the flush temporaries: one-off allocation
         if(!forced) { share_groups = 0; tmp_items = std::max<uint64_t>(total, 1); }
-        tmp_owned = true;
-        tmp = nullptr; d_goff = nullptr; d_base = nullptr;
-        HIP_TRY(hipMalloc((void**)&tmp, tmp_items * sizeof(ITEM)));
-        if(hipMalloc((void**)&d_goff, (n_tiles + 1) * sizeof(uint64_t)) != hipSuccess ||
-           hipMalloc((void**)&d_base, nb1 * sizeof(uint64_t)) != hipSuccess) {
-          hipFree(tmp); if(d_goff) hipFree(d_goff);
-          return fail(JFGPU_E_ALLOC, "hipMalloc partition offsets");
-        }
+        { const int rc = own_tmp.alloc(tmp_items); if(rc) return rc; }
+        if(!own_goff.try_alloc(n_tiles + 1) || !own_base.try_alloc(nb1)) return fail(JFGPU_E_ALLOC, "hipMalloc partition offsets");
+        tmp = own_tmp; d_goff = own_goff; d_base = own_base;
       }
       std::vector<uint64_t> base(nb1);                     // where a bucket's tiles start in tmp (groups sharing tmp: from 0 again)
       { uint64_t run = 0; for(uint32_t j = 0; j < nb1; ++j) { if(share_groups && j % (nb1 / share_groups) == 0) run = 0; base[j] = run; run += bucket_tot[j]; } }
@@ -631,9 +629,9 @@ int part_flush_t(jfgpu_table* t) {
     const bool two_streams = n_groups > 1 && !share_groups;
     const uint32_t gsz = nb1 / n_groups;
     if(two_streams && !t->stream2) {
-      HIP_TRY(hipStreamCreateWithFlags(&t->stream2, hipStreamNonBlocking));
-      for(auto& ev : t->flush_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&t->flush_done, hipEventDisableTiming));
+      int rc;
+      if((rc = t->stream2.create()) || (rc = t->flush_ev[0].create(hipEventDisableTiming)) || (rc = t->flush_ev[1].create(hipEventDisableTiming)) ||
+         (rc = t->flush_done.create(hipEventDisableTiming))) return rc;
     }
     hipEvent_t p2a = nullptr, p2b = nullptr, ta = nullptr, tb = nullptr;
     if(t->prof_on && !share_groups) { p2a = get_event(t); p2b = get_event(t); ta = get_event(t); tb = get_event(t); hipEventRecord(p2a, t->stream); }
@@ -755,8 +753,6 @@ int part_flush_t(jfgpu_table* t) {
       HIP_TRY(hipStreamWaitEvent(t->stream, t->flush_done, 0));
     }
     hipError_t e = hipStreamSynchronize(t->stream);
-    if(tmp_owned) { hipFree(tmp); hipFree(d_goff); hipFree(d_base); }
-    if(own2) { hipFree(d_gcur2); hipFree(d_off2); hipFree(out2); }
     if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
   }
   hipError_t e = hipGetLastError();

@@ -4,6 +4,7 @@
 // owns the table (mer_hash ctor, :275), drives the counting threads (:331-333)
 // and hands the table to the dumper (:349-355).  Here the "threads" are HIP
 // kernels enqueued on one stream per table; there is no CPU fallback.
+// Who owns what on the host: hip_own.hpp (owners in handles, raw pointers only inside the structs handed to kernels).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -67,9 +68,11 @@ struct PendingBatch {
   uint64_t bound = 0;                         // what ensure_capacity charged for this batch (an upper bound on its k-mers; 0: not charged)
 };
 
-struct ProfSpan { hipEvent_t a, b; int which; uint64_t units; };
+struct ProfSpan { hipEvent_t a, b; int which; uint64_t units; };   // (events of the table's pool: get_event)
 
 }  // namespace
+
+#include "hip_own.hpp"
 
 struct jfgpu_table {
   jfgpu_params params{};
@@ -77,11 +80,13 @@ struct jfgpu_table {
   Gf2Matrix matrix;
   int device = 0;
   int n_cu = 256;
-  hipStream_t stream = nullptr;
+  Stream stream, stream2;        // (before every buffer used on them: the buffers go first.  stream2: part_flush_t's second one, on demand)
+  // what kernels receive (DevTable, WideTable, NTable) holds raw pointers, set from the owners here
   DevTable dt{};
-  DevTable* d_dt = nullptr;      // a copy of dt in device memory for kernels that call out of line with it (refreshed before every such launch)
-  uint64_t* d_fwd = nullptr;
-  uint64_t* d_inv = nullptr;
+  DevBuf<uint8_t> slots, dirty;
+  DevBuf<uint64_t> ovf_key, ovf_cnt, counters;
+  DevBuf<DevTable> d_dt;         // a copy of dt in device memory for kernels that call out of line with it (refreshed before every such launch)
+  DevBuf<uint64_t> d_fwd, d_inv;
   int failed = 0; std::string failed_msg;   // a flush failed: every call reports it until jfgpu_clear (host_partition.inl: part_flush)
   uint64_t ovf_cap = 0;
   // what the side table may have to hold: an entry needs 2^cnt_bits occurrences of its key, or one add of a large value
@@ -91,7 +96,7 @@ struct jfgpu_table {
   // rings, shared rings, the sort-based single pass, the exact count + scatter -- and P1 launches: ring kernel, any other
   // count --bc: the cache of admitted k-mers (kernels_bloom.hip.hpp) -- 0 undecided, 1 on, -1 off; decided from the first
   // filtered batches (host_partition.inl: bloom_cache_decide), dropped when the counter is detached
-  uint64_t* d_bcache = nullptr; int bcache_state = 0; uint64_t mers_seen = 0;
+  DevBuf<uint64_t> d_bcache; int bcache_state = 0; uint64_t mers_seen = 0;
   uint64_t n_p2_roles = 0, n_p2_ring = 0, n_p2_sort = 0, n_p2_exact = 0, n_p1_ring = 0, n_p1_other = 0, n_tile_dense = 0;
   uint64_t ovf_failed_need = 0;                  // the side-table size whose allocation failed (not retried per batch)
   bool returning = false;
@@ -111,13 +116,14 @@ struct jfgpu_table {
   uint32_t key_words = 1;        // 64-bit words of a key in the API (mer_dna::data(): ceil(2k / 64))
   uint32_t slot_words = 1;       // 64-bit words of a table slot (1, 2 or 4)
   // staging for host buffers
-  uint8_t* d_stage[2] = {nullptr, nullptr};
-  hipEvent_t stage_done[2] = {nullptr, nullptr};
+  DevBuf<uint8_t> d_stage[2];
+  Event stage_done[2];
   int stage_next = 0;
   // profiling
   bool prof_on = false;
   std::vector<ProfSpan> prof_pending;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_all;         // every event of the profile spans, for good
+  std::vector<hipEvent_t> ev_pool;   // ... and those of them that are free (get_event)
   std::vector<std::pair<int, float>> prof_log;   // every span since the last reset, in launch order (jfgpu_profile_spans)
   double prof_ms[kNumProf] = {};
   uint64_t prof_launches[kNumProf] = {};
@@ -137,24 +143,24 @@ struct jfgpu_table {
   int (*spill_fn)(void*) = nullptr; void* spill_user = nullptr;     // jfgpu_set_spill
   int operation = 0;             // what count_ascii does with a k-mer: 0 add, 1 set (prime), 2 update_add (jfgpu_set_operation)
   Tuning tun;                    // the JFGPU_* switches as they were when the table was created (tuning.hpp)
-  hipStream_t stream2 = nullptr; hipEvent_t flush_ev[2] = {nullptr, nullptr}; hipEvent_t flush_done = nullptr;
+  Event flush_ev[2], flush_done;   // with stream2
   double items_per_byte = 0;     // k-mers per sequence byte seen by the last flush (0: unknown yet)
   uint64_t reserved_input = 0;   // sequence bytes the caller announced (jfgpu_reserve): lets forced flushes be spaced evenly
-  uint32_t* d_M1 = nullptr; int g1 = 0;
-  uint64_t* d_strag2 = nullptr; uint32_t* d_strag2_n = nullptr; uint32_t strag2_lists = 0;      // ... and of the ring P2, one per workgroup
-  uint64_t* d_strag = nullptr; uint32_t* d_strag_n = nullptr;      // straggler lists of the ring P1 (kernels_p1ring.hip.hpp), one per workgroup
-  uint32_t* d_M2 = nullptr; int g2 = 0;
+  DevBuf<uint32_t> d_M1; int g1 = 0;
+  DevBuf<uint64_t> d_strag2; DevBuf<uint32_t> d_strag2_n; uint32_t strag2_lists = 0;      // ... and of the ring P2, one per workgroup
+  DevBuf<uint64_t> d_strag; DevBuf<uint32_t> d_strag_n;      // straggler lists of the ring P1 (kernels_p1ring.hip.hpp), one per workgroup
+  DevBuf<uint32_t> d_M2; int g2 = 0;
   // workspace arena for pending batches and flush temporaries: bump-allocated, reset at flush,
   // grown geometrically (allocation of tens of GB costs ~100 ms, so never inside the hot path twice)
-  uint8_t* ws = nullptr; size_t ws_cap = 0, ws_used = 0;
+  DevBuf<uint8_t> ws; size_t ws_cap = 0, ws_used = 0;
   // dump state
   bool dump_open = false;
   uint64_t dump_lower = 0, dump_upper = 0;
   int dump_have_ovf = 0;
   std::vector<uint64_t> dump_prefix;  // per tile exclusive prefix, size n_tiles + 1
   uint64_t dump_tile_cursor = 0;
-  uint8_t* d_dump = nullptr; uint64_t dump_cap_records = 0;
-  uint64_t* d_tile_off = nullptr; uint64_t tile_off_cap = 0;
+  DevBuf<uint8_t> d_dump; uint64_t dump_cap_records = 0;
+  DevBuf<uint64_t> d_tile_off;
 };
 
 namespace {
@@ -176,9 +182,9 @@ int grid_for(const jfgpu_table* t, uint64_t work_items) {
 
 hipEvent_t get_event(jfgpu_table* t) {
   if(!t->ev_pool.empty()) { hipEvent_t e = t->ev_pool.back(); t->ev_pool.pop_back(); return e; }
-  hipEvent_t e = nullptr;
-  hipEventCreate(&e);
-  return e;
+  t->ev_all.emplace_back();
+  (void)t->ev_all.back().create();
+  return t->ev_all.back();
 }
 
 struct ProfScope {  // records a HIP-event pair around a launch on the table's stream
@@ -273,21 +279,20 @@ int ensure_ovf(jfgpu_table* t, uint64_t more_occurrences, uint64_t more_big_adds
   while(cap2 < need) cap2 <<= 1;
   HIP_TRY(hipStreamSynchronize(t->stream));
   if(t->stream2) HIP_TRY(hipStreamSynchronize(t->stream2));
-  uint64_t *nk = nullptr, *nc = nullptr;
-  if(hipMalloc((void**)&nk, cap2 * 8) != hipSuccess || hipMalloc((void**)&nc, cap2 * 8) != hipSuccess) {
-    if(nk) hipFree(nk);
+  DevBuf<uint64_t> nk, nc;
+  if(!nk.try_alloc(cap2) || !nc.try_alloc(cap2)) {
     (void)hipGetLastError();
     t->ovf_failed_need = need;
     return JFGPU_OK;                                              // no memory: carry on, CTR_OVF_FULL reports it if it really overflows
   }
   HIP_TRY(hipMemsetAsync(nk, 0, cap2 * 8, t->stream));
   HIP_TRY(hipMemsetAsync(nc, 0, cap2 * 8, t->stream));
-  hipLaunchKernelGGL(ovf_rehash_kernel, dim3(grid_for(t, t->ovf_cap / kBlock + 1)), dim3(kBlock), 0, t->stream, t->dt.ovf_key, t->dt.ovf_cnt, t->ovf_cap, nk, nc, cap2 - 1,
+  hipLaunchKernelGGL(ovf_rehash_kernel, dim3(grid_for(t, t->ovf_cap / kBlock + 1)), dim3(kBlock), 0, t->stream, t->dt.ovf_key, t->dt.ovf_cnt, t->ovf_cap, nk.get(), nc.get(), cap2 - 1,
                      (unsigned long long*)&t->dt.counters[CTR_OVF_FULL]);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(t->stream));
-  hipFree(t->dt.ovf_key); hipFree(t->dt.ovf_cnt);
-  t->dt.ovf_key = nk; t->dt.ovf_cnt = nc; t->dt.ovf_mask = cap2 - 1; t->ovf_cap = cap2;
+  t->ovf_key = std::move(nk); t->ovf_cnt = std::move(nc);
+  t->dt.ovf_key = t->ovf_key; t->dt.ovf_cnt = t->ovf_cnt; t->dt.ovf_mask = cap2 - 1; t->ovf_cap = cap2;
   refresh_views(t);
   return JFGPU_OK;
 }
@@ -413,8 +418,9 @@ int launch_count(jfgpu_table* t, const char* d_bases, size_t n) {
 
 int ensure_stage(jfgpu_table* t) {
   for(int i = 0; i < 2; ++i) {
-    if(!t->d_stage[i]) HIP_TRY(hipMalloc((void**)&t->d_stage[i], kStageBytes));
-    if(!t->stage_done[i]) HIP_TRY(hipEventCreateWithFlags(&t->stage_done[i], hipEventDisableTiming));
+    int rc;
+    if(!t->d_stage[i] && (rc = t->d_stage[i].alloc(kStageBytes))) return rc;
+    if(!t->stage_done[i] && (rc = t->stage_done[i].create(hipEventDisableTiming))) return rc;
   }
   return JFGPU_OK;
 }
@@ -447,14 +453,14 @@ void launch_scan(jfgpu_table* t, const Table& T, const ScanArgs& a, unsigned lon
 void launch_dump(jfgpu_table* t, const DevTable& T, uint64_t t0, uint64_t ntile, uint32_t key_bytes) {
   const size_t lds = ((size_t)8 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits) + (size_t)t->g.nbytes * 2048;
   hipLaunchKernelGGL(dump_tiles_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), lds, t->stream, T, t->dump_lower,
-                     t->dump_upper, t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump, key_bytes,
+                     t->dump_upper, t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump.get(), key_bytes,
                      t->out_counter_len);
 }
 template <class Table>
 void launch_dump(jfgpu_table* t, const Table& T, uint64_t t0, uint64_t ntile, uint32_t key_bytes) {
   const size_t lds = ((size_t)(8 * KeyOps<Table>::kSlotWords) << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits);     // 16 or 32 bytes of slot, 2 of index
   hipLaunchKernelGGL(dump_tiles_words_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), lds, t->stream, T, t->dump_lower, t->dump_upper,
-                     t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump, key_bytes, t->out_counter_len);
+                     t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump.get(), key_bytes, t->out_counter_len);
 }
 
 // The sender's two passes over one contract buffer (route_count_kernel, route_scatter_kernel): the buffer's k-mers into `out`,
@@ -498,13 +504,12 @@ int route_buffer(jfgpu_table* t, const char* d_bases, size_t n, unsigned long lo
 
 // One scan into n 64-bit counters of its own (4, or a histogram's buckets), copied to `out` when it is complete.
 int scan_to_host(jfgpu_table* t, const ScanArgs& a, uint64_t n, uint64_t* out) {
-  unsigned long long* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, n * sizeof(unsigned long long)));
+  DevBuf<unsigned long long> d;
+  int rc = d.alloc(n); if(rc) return rc;
   HIP_TRY(hipMemsetAsync(d, 0, n * sizeof(unsigned long long), t->stream));
-  with_view(t, [&](const auto& T) { launch_scan(t, T, a, d, (uint32_t*)nullptr); });
+  with_view(t, [&](const auto& T) { launch_scan(t, T, a, d.get(), (uint32_t*)nullptr); });
   hipError_t e = hipMemcpyAsync(out, d, n * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream);
   if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  hipFree(d);
   if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
   return JFGPU_OK;
 }
@@ -528,9 +533,11 @@ struct GrowNew {
   TableGeom g2; WideGeom w2; NGeom ng2;
   Gf2Matrix m2;
   DevTable nd; WideTable nw; NTable nn;
-  uint64_t *nf = nullptr, *ni = nullptr;
+  DevBuf<uint8_t> slots, dirty;            // the new table's blocks until grow_swap hands them to the table; nd, nw and nn point at them
+  DevBuf<uint64_t> ovf_key, ovf_cnt, nf, ni;
   uint64_t cap2 = 0;
   uint64_t ctr[CTR_COUNT];
+  void drop() { slots = {}; dirty = {}; ovf_key = {}; ovf_cnt = {}; nf = {}; ni = {}; }      // a prepared doubling that will not happen
 };
 // ... and the old view together with the new one
 template <class F> void with_view(jfgpu_table* t, GrowNew& N, F&& f) {
@@ -582,14 +589,14 @@ int grow_prepare(jfgpu_table* t, GrowNew& N) {
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   if(n2 * slot_bytes + cap2 * 16 + ((size_t)1 << 30) > free_b) return -1;
-  bool ok = hipMalloc((void**)&nd.slots, n2 * slot_bytes) == hipSuccess && hipMalloc((void**)&nd.ovf_key, cap2 * 8) == hipSuccess &&
-            hipMalloc((void**)&nd.ovf_cnt, cap2 * 8) == hipSuccess && hipMalloc((void**)&nd.dirty, (size_t)1 << (g2.lsize_l - g2.tile_bits)) == hipSuccess &&
-            hipMalloc((void**)&N.nf, fwd.size() * 8) == hipSuccess && hipMalloc((void**)&N.ni, inv.size() * 8) == hipSuccess;
+  const bool ok = N.slots.try_alloc(n2 * slot_bytes) && N.ovf_key.try_alloc(cap2) && N.ovf_cnt.try_alloc(cap2) &&
+                  N.dirty.try_alloc((size_t)1 << (g2.lsize_l - g2.tile_bits)) && N.nf.try_alloc(fwd.size()) && N.ni.try_alloc(inv.size());
   if(!ok) {
-    hipFree(nd.slots); hipFree(nd.ovf_key); hipFree(nd.ovf_cnt); hipFree(nd.dirty); hipFree(N.nf); hipFree(N.ni);
+    N.drop();
     (void)hipGetLastError();
     return -1;
   }
+  nd.slots = (decltype(nd.slots))N.slots.get(); nd.ovf_key = N.ovf_key; nd.ovf_cnt = N.ovf_cnt; nd.dirty = N.dirty;
   nd.fwd_tbl = N.nf; nd.inv_tbl = N.ni; nd.ovf_mask = cap2 - 1;
   nd.max_probe = (uint32_t)std::min<uint64_t>(g2.tile_mask, 1023);
   HIP_TRY(hipMemsetAsync(nd.slots, 0, n2 * slot_bytes, t->stream));
@@ -614,11 +621,12 @@ int grow_prepare(jfgpu_table* t, GrowNew& N) {
 
 // the new table takes the old one's place (the entries have been moved and the stream is idle)
 int grow_swap(jfgpu_table* t, GrowNew& N) {
-  hipFree(t->dt.slots); hipFree(t->dt.ovf_key); hipFree(t->dt.ovf_cnt); hipFree(t->dt.dirty); hipFree(t->d_fwd); hipFree(t->d_inv);
-  t->dt = N.nd; t->g = N.g2; t->matrix = N.m2; t->d_fwd = N.nf; t->d_inv = N.ni; t->ovf_cap = N.cap2;
+  t->slots = std::move(N.slots); t->ovf_key = std::move(N.ovf_key); t->ovf_cnt = std::move(N.ovf_cnt); t->dirty = std::move(N.dirty);
+  t->d_fwd = std::move(N.nf); t->d_inv = std::move(N.ni);
+  t->dt = N.nd; t->g = N.g2; t->matrix = N.m2; t->ovf_cap = N.cap2;
   t->returning = t->g.cnt_bits < 40; t->ovf_failed_need = 0;
-  if(t->d_M2) { hipFree(t->d_M2); t->d_M2 = nullptr; }
-  if(t->d_strag) { hipFree(t->d_strag); hipFree(t->d_strag_n); t->d_strag = nullptr; t->d_strag_n = nullptr; }     // (the item width may change with the geometry)
+  (void)t->d_M2.reset();
+  (void)t->d_strag.reset(); (void)t->d_strag_n.reset();     // (the item width may change with the geometry)
   if(t->nword) {
     t->nt = N.nn;
     t->pristine = false;
@@ -679,13 +687,8 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
   if(p->k > 128) return fail(JFGPU_E_UNSUPPORTED, "mer length > 128 (more than four key words) is not built");
   if(p->shard_bits > 8) return fail(JFGPU_E_INVALID, "at most 256 shards");
   if(p->shard_id >= (1u << p->shard_bits)) return fail(JFGPU_E_INVALID, "shard_id out of range");
-  int ndev = 0;
-  if(hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(JFGPU_E_NO_DEVICE, "no HIP device: the engine has no CPU fallback");
-  int dev = p->device;
-  if(dev < 0) HIP_TRY(hipGetDevice(&dev));
-  if(dev >= ndev) return fail(JFGPU_E_NO_DEVICE, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(dev));
+  int dev = 0;
+  int rc = pick_device(p->device, &dev); if(rc) return rc;
 
   // size -> lsize (large_hash_array.hpp:156-157 rounds up to a power of two, :997-1000 caps at 4^k)
   const bool nword = p->k > 64, wide = p->k > 32 && !nword;
@@ -753,7 +756,7 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, dev));
   t->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  HIP_TRY(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+  rc = t->stream.create(); if(rc) return rc;
 
   const uint64_t n_slots = 1ull << t->g.lsize_l;
   t->ovf_cap = std::max<uint64_t>(kMinOvf, std::min<uint64_t>(n_slots / 256, 1ull << 26));
@@ -762,13 +765,10 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
 
   DevTable& d = t->dt;
   d.g = t->g;
-  HIP_TRY(hipMalloc((void**)&d.slots, n_slots * slot_bytes_of(t.get())));
-  HIP_TRY(hipMalloc((void**)&t->d_fwd, fwd.size() * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc((void**)&t->d_inv, inv.size() * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc((void**)&d.ovf_key, t->ovf_cap * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc((void**)&d.ovf_cnt, t->ovf_cap * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc((void**)&d.counters, CTR_COUNT * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc((void**)&d.dirty, (size_t)1 << (t->g.lsize_l - t->g.tile_bits)));
+  if((rc = t->slots.alloc(n_slots * slot_bytes_of(t.get()))) || (rc = t->d_fwd.alloc(fwd.size())) || (rc = t->d_inv.alloc(inv.size())) ||
+     (rc = t->ovf_key.alloc(t->ovf_cap)) || (rc = t->ovf_cnt.alloc(t->ovf_cap)) || (rc = t->counters.alloc(CTR_COUNT)) ||
+     (rc = t->dirty.alloc((size_t)1 << (t->g.lsize_l - t->g.tile_bits)))) return rc;
+  d.slots = (decltype(d.slots))t->slots.get(); d.ovf_key = t->ovf_key; d.ovf_cnt = t->ovf_cnt; d.counters = (decltype(d.counters))t->counters.get(); d.dirty = t->dirty;
   d.fwd_tbl = t->d_fwd; d.inv_tbl = t->d_inv; d.ovf_mask = t->ovf_cap - 1;
   // Give up on a tile after 1024 probes (load > 99.8%); the reference gives up after 126
   // (count_main_cmdline.yaggo -p).  Small tiles are probed exhaustively.
@@ -887,10 +887,9 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
     HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_wide_pipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wt));
     HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_wide_pipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wt));
   }
-  jfgpu_table* raw = t.release();
-  int rc = jfgpu_clear(raw);
-  if(rc) { jfgpu_destroy(raw); return rc; }
-  *out = raw;
+  rc = jfgpu_clear(t.get());
+  if(rc) { t->stream.sync(); return rc; }      // (drained before the handle goes, like every destroy path)
+  *out = t.release();
   return JFGPU_OK;
 }
 
@@ -899,26 +898,8 @@ void jfgpu_destroy(jfgpu_table* t) {
   hipSetDevice(t->device);
   if(t->stream) hipStreamSynchronize(t->stream);
   prof_collect(t);
-  for(auto e : t->ev_pool) hipEventDestroy(e);
-  hipFree(t->dt.slots); hipFree(t->d_fwd); hipFree(t->d_inv);
-  if(t->d_dt) hipFree(t->d_dt);
-  hipFree(t->dt.ovf_key); hipFree(t->dt.ovf_cnt); hipFree(t->dt.counters); hipFree(t->dt.dirty);
-  for(int i = 0; i < 2; ++i) { if(t->d_stage[i]) hipFree(t->d_stage[i]); if(t->stage_done[i]) hipEventDestroy(t->stage_done[i]); }
-  if(t->d_dump) hipFree(t->d_dump);
-  if(t->d_bcache) hipFree(t->d_bcache);
-  if(t->d_tile_off) hipFree(t->d_tile_off);
   part_discard(t);
-  if(t->d_M1) hipFree(t->d_M1);
-  if(t->d_strag) hipFree(t->d_strag);
-  if(t->d_strag2) hipFree(t->d_strag2);
-  if(t->d_strag2_n) hipFree(t->d_strag2_n);
-  if(t->d_strag_n) hipFree(t->d_strag_n);
-  if(t->d_M2) hipFree(t->d_M2);
-  if(t->ws) hipFree(t->ws);
-  if(t->stream2) hipStreamDestroy(t->stream2);
-  for(auto ev : t->flush_ev) if(ev) hipEventDestroy(ev);
-  if(t->flush_done) hipEventDestroy(t->flush_done);
-  if(t->stream) hipStreamDestroy(t->stream);
+  t->stream2.sync();
   delete t;
 }
 
@@ -1009,7 +990,7 @@ int jfgpu_count_ascii(jfgpu_table* t, const char* bases, size_t n) {
     const int b = t->stage_next; t->stage_next ^= 1;
     HIP_TRY(hipEventSynchronize(t->stage_done[b]));  // kernel that last read this buffer has finished
     HIP_TRY(hipMemcpyAsync(t->d_stage[b], bases + o, len, hipMemcpyHostToDevice, t->stream));
-    rc = launch_count(t, (const char*)t->d_stage[b], len); if(rc) return rc;
+    rc = launch_count(t, (const char*)t->d_stage[b].get(), len); if(rc) return rc;
     HIP_TRY(hipEventRecord(t->stage_done[b], t->stream));
     if(o + len >= n) break;
   }
@@ -1064,14 +1045,13 @@ int jfgpu_add_keys_dev(jfgpu_table* t, const uint64_t* d_keys, size_t n, uint64_
 int jfgpu_add_keys(jfgpu_table* t, const uint64_t* keys, size_t n, uint64_t val, uint8_t* is_new) {
   int rc = use(t); if(rc) return rc;
   if(!n) return JFGPU_OK;
-  uint64_t* d_k = nullptr; uint8_t* d_n = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_k, n * sizeof(uint64_t) * t->key_words));
-  if(is_new && hipMalloc((void**)&d_n, n) != hipSuccess) { hipFree(d_k); return fail(JFGPU_E_ALLOC, "hipMalloc is_new"); }
+  DevBuf<uint64_t> d_k; DevBuf<uint8_t> d_n;
+  rc = d_k.alloc(n * t->key_words); if(rc) return rc;
+  if(is_new && !d_n.try_alloc(n)) return fail(JFGPU_E_ALLOC, "hipMalloc is_new");
   hipError_t e = hipMemcpyAsync(d_k, keys, n * sizeof(uint64_t) * t->key_words, hipMemcpyHostToDevice, t->stream);
   if(e == hipSuccess) { rc = jfgpu_add_keys_dev(t, d_k, n, val, d_n); }
   if(e == hipSuccess && !rc && is_new) e = hipMemcpyAsync(is_new, d_n, n, hipMemcpyDeviceToHost, t->stream);
   hipStreamSynchronize(t->stream);
-  hipFree(d_k); if(d_n) hipFree(d_n);
   if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
   if(rc) return rc;
   return check_deferred(t);
@@ -1096,18 +1076,14 @@ int jfgpu_lookup_dev(jfgpu_table* t, const uint64_t* d_keys, size_t n, uint64_t*
 int jfgpu_lookup(jfgpu_table* t, const uint64_t* keys, size_t n, uint64_t* vals, uint8_t* found) {
   int rc = use(t); if(rc) return rc;
   if(!n) return JFGPU_OK;
-  uint64_t *d_k = nullptr, *d_v = nullptr; uint8_t* d_f = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_k, n * sizeof(uint64_t) * t->key_words));
-  if(hipMalloc((void**)&d_v, n * sizeof(uint64_t)) != hipSuccess || hipMalloc((void**)&d_f, n) != hipSuccess) {
-    hipFree(d_k); if(d_v) hipFree(d_v);
-    return fail(JFGPU_E_ALLOC, "hipMalloc lookup buffers");
-  }
+  DevBuf<uint64_t> d_k, d_v; DevBuf<uint8_t> d_f;
+  rc = d_k.alloc(n * t->key_words); if(rc) return rc;
+  if(!d_v.try_alloc(n) || !d_f.try_alloc(n)) return fail(JFGPU_E_ALLOC, "hipMalloc lookup buffers");
   hipError_t e = hipMemcpyAsync(d_k, keys, n * sizeof(uint64_t) * t->key_words, hipMemcpyHostToDevice, t->stream);
   if(e == hipSuccess) rc = jfgpu_lookup_dev(t, d_k, n, d_v, d_f);
   if(e == hipSuccess && !rc) e = hipMemcpyAsync(vals, d_v, n * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream);
   if(e == hipSuccess && !rc && found) e = hipMemcpyAsync(found, d_f, n, hipMemcpyDeviceToHost, t->stream);
   hipStreamSynchronize(t->stream);
-  hipFree(d_k); hipFree(d_v); hipFree(d_f);
   if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
   return rc;
 }
@@ -1145,16 +1121,16 @@ int jfgpu_query_ascii(jfgpu_table* t, const char* bases, size_t n, uint64_t* val
   if(t->g.shard_bits) return fail(JFGPU_E_UNSUPPORTED, "query_ascii: not for a shard (the keys of the other shards are not here)");
   rc = ensure_stage(t); if(rc) return rc;
   const size_t piece = std::min(kStageBytes, n), seam = t->g.k - 1;
-  uint64_t* d_v = nullptr; uint8_t* d_f = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_v, piece * sizeof(uint64_t)));
-  if(flags && hipMalloc((void**)&d_f, piece) != hipSuccess) { hipFree(d_v); return fail(JFGPU_E_ALLOC, "hipMalloc query flags"); }
+  DevBuf<uint64_t> d_v; DevBuf<uint8_t> d_f;
+  rc = d_v.alloc(piece); if(rc) return rc;
+  if(flags && !d_f.try_alloc(piece)) return fail(JFGPU_E_ALLOC, "hipMalloc query flags");
   hipError_t e = hipSuccess;
   for(size_t o = 0; o < n && e == hipSuccess && !rc; o += kStageBytes - seam) {
     const size_t len = std::min(kStageBytes, n - o), skip = o ? seam : 0;
     const int b = t->stage_next; t->stage_next ^= 1;
     e = hipEventSynchronize(t->stage_done[b]);                 // the kernel that last read this buffer has finished
     if(e == hipSuccess) e = hipMemcpyAsync(t->d_stage[b], bases + o, len, hipMemcpyHostToDevice, t->stream);
-    if(e == hipSuccess) rc = jfgpu_query_ascii_dev(t, (const char*)t->d_stage[b], len, d_v, d_f);
+    if(e == hipSuccess) rc = jfgpu_query_ascii_dev(t, (const char*)t->d_stage[b].get(), len, d_v, d_f);
     if(e == hipSuccess && !rc) e = hipEventRecord(t->stage_done[b], t->stream);
     if(e == hipSuccess && !rc) e = hipMemcpyAsync(vals + o + skip, d_v + skip, (len - skip) * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream);
     if(e == hipSuccess && !rc && flags) e = hipMemcpyAsync(flags + o + skip, d_f + skip, len - skip, hipMemcpyDeviceToHost, t->stream);
@@ -1162,7 +1138,6 @@ int jfgpu_query_ascii(jfgpu_table* t, const char* bases, size_t n, uint64_t* val
     if(o + len >= n) break;
   }
   hipStreamSynchronize(t->stream);
-  hipFree(d_v); if(d_f) hipFree(d_f);
   if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
   return rc;
 }
@@ -1176,11 +1151,9 @@ int jfgpu_partition_ascii_dev(jfgpu_table* t, const char* d_bases, size_t n, uin
   for(uint32_t i = 0; i < n_shards; ++i) counts_out[i] = 0;
   if(n < t->g.k) return JFGPU_OK;
   if(!d_bases || !d_keys_out) return fail(JFGPU_E_INVALID, "null buffer");
-  unsigned long long* d_cnt = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_cnt, sizeof(unsigned long long) * n_shards));
-  rc = route_buffer(t, d_bases, n, d_cnt, d_keys_out, capacity, counts_out);
-  hipFree(d_cnt);
-  return rc;
+  DevBuf<unsigned long long> d_cnt;
+  rc = d_cnt.alloc(n_shards); if(rc) return rc;
+  return route_buffer(t, d_bases, n, d_cnt, d_keys_out, capacity, counts_out);
 }
 
 int jfgpu_stats_compute(jfgpu_table* t, uint64_t lower, uint64_t upper, jfgpu_stats* out) {
@@ -1220,15 +1193,14 @@ int jfgpu_dump_begin(jfgpu_table* t, uint64_t lower, uint64_t upper, uint64_t* n
   uint64_t c[CTR_COUNT];
   rc = check_deferred(t, c); if(rc) return rc;
   const uint64_t nt = n_tiles_of(t);
-  uint32_t* d_cnt = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_cnt, nt * sizeof(uint32_t)));
+  DevBuf<uint32_t> d_cnt;
+  rc = d_cnt.alloc(nt); if(rc) return rc;
   t->dump_have_ovf = c[CTR_OVF_USED] != 0;
   if(t->slot_words > 1) HIP_TRY(hipMemsetAsync(d_cnt, 0, nt * sizeof(uint32_t), t->stream));      // (scan_kernel adds to them; tile_count_kernel writes every one)
-  with_view(t, [&](const auto& T) { launch_scan(t, T, ScanArgs{SCAN_TILES, lower, upper, t->dump_have_ovf}, (unsigned long long*)nullptr, d_cnt); });
+  with_view(t, [&](const auto& T) { launch_scan(t, T, ScanArgs{SCAN_TILES, lower, upper, t->dump_have_ovf}, (unsigned long long*)nullptr, d_cnt.get()); });
   std::vector<uint32_t> h(nt);
   hipError_t e = hipMemcpyAsync(h.data(), d_cnt, nt * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream);
   if(e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  hipFree(d_cnt);
   if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
   t->dump_prefix.assign(nt + 1, 0);
   for(uint64_t i = 0; i < nt; ++i) t->dump_prefix[i + 1] = t->dump_prefix[i] + h[i];
@@ -1261,17 +1233,11 @@ int dump_next_chunk(jfgpu_table* t, uint64_t capacity_records, uint64_t* n_read)
   const uint64_t ntile = t1 - t0, nrec = t->dump_prefix[t1] - t->dump_prefix[t0];
   const uint32_t key_bytes = (t->g.key_bits + 7) / 8, rec = key_bytes + t->out_counter_len;
   if(t->dump_cap_records < nrec) {
-    if(t->d_dump) hipFree(t->d_dump);
-    t->d_dump = nullptr; t->dump_cap_records = 0;
-    HIP_TRY(hipMalloc((void**)&t->d_dump, std::max<uint64_t>(nrec, capacity_records) * rec + 64));   // (the text kernels read to the next 16-byte boundary)
+    t->dump_cap_records = 0;
+    const int rc = t->d_dump.alloc(std::max<uint64_t>(nrec, capacity_records) * rec + 64); if(rc) return rc;   // (the text kernels read to the next 16-byte boundary)
     t->dump_cap_records = std::max<uint64_t>(nrec, capacity_records);
   }
-  if(t->tile_off_cap < ntile) {
-    if(t->d_tile_off) hipFree(t->d_tile_off);
-    t->d_tile_off = nullptr; t->tile_off_cap = 0;
-    HIP_TRY(hipMalloc((void**)&t->d_tile_off, ntile * sizeof(uint64_t)));
-    t->tile_off_cap = ntile;
-  }
+  if(t->d_tile_off.cap() < ntile) { const int rc = t->d_tile_off.alloc(ntile); if(rc) return rc; }
   std::vector<uint64_t> offs(ntile);
   for(uint64_t i = 0; i < ntile; ++i) offs[i] = t->dump_prefix[t0 + i] - t->dump_prefix[t0];
   HIP_TRY(hipMemcpyAsync(t->d_tile_off, offs.data(), ntile * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
@@ -1303,8 +1269,8 @@ int jfgpu_dump_end(jfgpu_table* t) {
   int rc = use(t); if(rc) return rc;
   t->dump_open = false;
   t->dump_prefix.clear(); t->dump_prefix.shrink_to_fit();
-  if(t->d_dump) { hipFree(t->d_dump); t->d_dump = nullptr; t->dump_cap_records = 0; }
-  if(t->d_tile_off) { hipFree(t->d_tile_off); t->d_tile_off = nullptr; t->tile_off_cap = 0; }
+  (void)t->d_dump.reset(); t->dump_cap_records = 0;
+  (void)t->d_tile_off.reset();
   return JFGPU_OK;
 }
 
@@ -1339,8 +1305,8 @@ int jfgpu_reserve(jfgpu_table* t, uint64_t input_bytes) {
   if(rc) return rc;
   // touch every page once now: first-touch of fresh device pages costs ~40% on the first pass over them
   HIP_TRY(hipMemsetAsync(t->ws, 0, t->ws_cap, t->stream));
-  if(!t->d_M1) { t->g1 = 2 * t->n_cu; HIP_TRY(hipMalloc((void**)&t->d_M1, (size_t)t->g1 * kMaxBuckets * sizeof(uint32_t))); }
-  if(t->pg.b2 && !t->d_M2) HIP_TRY(hipMalloc((void**)&t->d_M2, (size_t)nb1 * 32 * nb2 * sizeof(uint32_t)));
+  if(!t->d_M1) { t->g1 = 2 * t->n_cu; rc = t->d_M1.alloc((size_t)t->g1 * kMaxBuckets); if(rc) return rc; }
+  if(t->pg.b2 && !t->d_M2) { rc = t->d_M2.alloc((size_t)nb1 * 32 * nb2); if(rc) return rc; }
   return JFGPU_OK;
 }
 
@@ -1472,23 +1438,22 @@ int jfgpu_gen_genome_reads_dev(jfgpu_table* t, char* d_out, uint64_t first_read,
 int jfgpu_gups(jfgpu_table* t, uint64_t n_updates, int mode, double* ups) {
   int rc = use(t); if(rc) return rc;
   if(!ups) return fail(JFGPU_E_INVALID, "null out");
-  unsigned long long* d_sink = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_sink, sizeof(unsigned long long)));
+  DevBuf<unsigned long long> d_sink;
+  rc = d_sink.alloc(1); if(rc) return rc;
   HIP_TRY(hipMemsetAsync(d_sink, 0, sizeof(unsigned long long), t->stream));
-  hipEvent_t a, b;
-  HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
+  Event a, b;
+  if((rc = a.create()) || (rc = b.create())) return rc;
   const uint64_t mask = (((1ull << t->g.lsize_l) * slot_bytes_of(t)) >> 3) - 1;    // 64-bit words of the table's allocation
   t->pristine = false;
   HIP_TRY(hipMemsetAsync(t->dt.dirty, 1, (size_t)1 << (t->g.lsize_l - t->g.tile_bits), t->stream));
   const int grid = grid_for(t, (n_updates + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(gups_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->dt.slots, mask, std::min<uint64_t>(n_updates, 1u << 20), mode, 1ull, d_sink);  // warm-up
+  hipLaunchKernelGGL(gups_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->dt.slots, mask, std::min<uint64_t>(n_updates, 1u << 20), mode, 1ull, d_sink.get());  // warm-up
   HIP_TRY(hipEventRecord(a, t->stream));
-  hipLaunchKernelGGL(gups_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->dt.slots, mask, n_updates, mode, 42ull, d_sink);
+  hipLaunchKernelGGL(gups_kernel, dim3(grid), dim3(kBlock), 0, t->stream, t->dt.slots, mask, n_updates, mode, 42ull, d_sink.get());
   HIP_TRY(hipEventRecord(b, t->stream));
   HIP_TRY(hipEventSynchronize(b));
   float ms = 0;
   HIP_TRY(hipEventElapsedTime(&ms, a, b));
-  hipEventDestroy(a); hipEventDestroy(b); hipFree(d_sink);
   *ups = ms > 0 ? (double)n_updates / (ms * 1e-3) : 0;
   return JFGPU_OK;
 }

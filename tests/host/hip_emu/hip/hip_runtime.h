@@ -64,6 +64,12 @@ struct hipDeviceProp_t { char name[64]; int multiProcessorCount; size_t totalGlo
 namespace hip_emu {
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 inline size_t& mem_in_use() { static size_t v = 0; return v; }
+// tests of ownership (tests/host/own_check.cc): fail_alloc_in() = n makes the n-th hipMalloc / hipHostMalloc from now on fail
+// once with hipErrorOutOfMemory (0: off); streams and events alive, beside mem_in_use()
+inline long& fail_alloc_in() { static long v = 0; return v; }
+inline bool alloc_fails() { long& v = fail_alloc_in(); return v > 0 && --v == 0; }
+inline long& live_streams() { static long v = 0; return v; }
+inline long& live_events() { static long v = 0; return v; }
 inline size_t mem_total() { const char* e = getenv("JFGPU_EMU_MEM_MB"); return (size_t)(e ? atol(e) : 49152) << 20; }
 inline int n_cus() { const char* e = getenv("JFGPU_EMU_CUS"); const int v = e ? atoi(e) : 2; return v > 0 ? v : 2; }
 struct AllocHeader { size_t bytes; size_t magic; char pad[256 - 2 * sizeof(size_t)]; };
@@ -84,7 +90,7 @@ static inline hipError_t hipMemGetInfo(size_t* free_b, size_t* total_b) {
 }
 template <typename T> static inline hipError_t hipMalloc(T** p, size_t bytes) {
   using hip_emu::AllocHeader;
-  if(hip_emu::mem_in_use() + bytes > hip_emu::mem_total()) { *p = nullptr; return hipErrorOutOfMemory; }
+  if(hip_emu::alloc_fails() || hip_emu::mem_in_use() + bytes > hip_emu::mem_total()) { *p = nullptr; return hipErrorOutOfMemory; }
   const size_t total = sizeof(AllocHeader) + bytes + 256;      // slack: kernels read whole 16-byte vectors at buffer ends
   void* raw = nullptr;
   if(total > ((size_t)64 << 20)) {                             // big tables: untouched pages stay virtual
@@ -109,7 +115,10 @@ static inline hipError_t hipFree(void* p) {
   else { fprintf(stderr, "hip_emu: hipFree of a pointer that was not allocated (or freed twice)\n"); abort(); }
   return hipSuccess;
 }
-template <typename T> static inline hipError_t hipHostMalloc(T** p, size_t bytes, unsigned = 0) { *p = (T*)malloc(bytes ? bytes : 16); return *p ? hipSuccess : hipErrorOutOfMemory; }
+template <typename T> static inline hipError_t hipHostMalloc(T** p, size_t bytes, unsigned = 0) {
+  if(hip_emu::alloc_fails()) { *p = nullptr; return hipErrorOutOfMemory; }
+  *p = (T*)malloc(bytes ? bytes : 16); return *p ? hipSuccess : hipErrorOutOfMemory;
+}
 static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if(n) memmove(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { if(n) memmove(d, s, n); return hipSuccess; }
@@ -126,14 +135,14 @@ static inline hipError_t hipMemset(void* d, int v, size_t n) {
   return hipSuccess;
 }
 static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) { return hipMemset(d, v, n); }
-static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)(uintptr_t)1; return hipSuccess; }
-static inline hipError_t hipStreamCreate(hipStream_t* s) { *s = (hipStream_t)(uintptr_t)1; return hipSuccess; }
-static inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
+static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)(uintptr_t)1; ++hip_emu::live_streams(); return hipSuccess; }
+static inline hipError_t hipStreamCreate(hipStream_t* s) { return hipStreamCreateWithFlags(s, 0); }
+static inline hipError_t hipStreamDestroy(hipStream_t) { --hip_emu::live_streams(); return hipSuccess; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hip_emu_event_{0.0}; return hipSuccess; }
+static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hip_emu_event_{0.0}; ++hip_emu::live_events(); return hipSuccess; }
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
-static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; --hip_emu::live_events(); return hipSuccess; }
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t = nullptr) { e->t_ms = hip_emu::now_ms(); return hipSuccess; }
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { *ms = (float)(b->t_ms - a->t_ms); return hipSuccess; }

@@ -11,6 +11,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <memory>
 #include <string>
@@ -94,10 +95,10 @@ struct jfgpu_table {
   uint64_t flushes_plain = 0, flushes_heavy = 0; // tile-kernel instantiation chosen per flush launch (jfgpu_get_counters)
   // which partition kernels ran since the last clear (jfgpu_get_counters 10..15): P2 launches by kind -- loader / storer
   // rings, shared rings, the sort-based single pass, the exact count + scatter -- and P1 launches: ring kernel, any other
+  uint64_t n_p2_roles = 0, n_p2_ring = 0, n_p2_sort = 0, n_p2_exact = 0, n_p1_ring = 0, n_p1_other = 0, n_tile_dense = 0;
   // count --bc: the cache of admitted k-mers (kernels_bloom.hip.hpp) -- 0 undecided, 1 on, -1 off; decided from the first
   // filtered batches (host_partition.inl: bloom_cache_decide), dropped when the counter is detached
   DevBuf<uint64_t> d_bcache; int bcache_state = 0; uint64_t mers_seen = 0;
-  uint64_t n_p2_roles = 0, n_p2_ring = 0, n_p2_sort = 0, n_p2_exact = 0, n_p1_ring = 0, n_p1_other = 0, n_tile_dense = 0;
   uint64_t ovf_failed_need = 0;                  // the side-table size whose allocation failed (not retried per batch)
   bool returning = false;
   uint32_t out_counter_len = 4;
@@ -426,6 +427,7 @@ int ensure_stage(jfgpu_table* t) {
 }
 
 
+#include "part_plan.inl"
 #include "host_partition.inl"
 
 // The view of the table for its key width (one, two, or three and four words), handed to a generic callable.

@@ -11,91 +11,89 @@
 // device copies: same routing, bookkeeping, rounds and insert code, no RCCL.  It exists so that the sharded path is
 // testable on a single GPU (and under tests/host/hip_emu) at world sizes 2 and 4.
 //
-// A third transport, "ipc", has one process per rank like RCCL but moves the messages with copies between the processes'
-// device allocations (hipIpcGetMemHandle / hipIpcOpenMemHandle) and keeps the small host-level agreements (counts,
-// barriers, allreduce / allgather) in a POSIX shared-memory block.  Every step ends on a host barrier, so nothing
+// A third transport, "ipc" (comm_ipc.inl), has one process per rank like RCCL but moves the messages with copies between
+// the processes' device allocations (hipIpcGetMemHandle / hipIpcOpenMemHandle) and keeps the small host-level agreements
+// (counts, barriers, allreduce / allgather) in a POSIX shared-memory block.  Every step ends on a host barrier, so nothing
 // overlaps: it exists so that the multi-PROCESS code around the exchange -- `count --gpus N`: rank start-up, rendezvous,
 // file parts, the collectives, the sharded writer, a failing rank -- runs and is tested on a box with a single GPU
 // (all ranks on device 0).  Chosen with JFGPU_COMM_TRANSPORT=ipc when the id is made (jfgpu_comm_unique_id).
+//
+// Every exchange goes through comm_exchange, which picks the transport.  The kernels are in kernels_comm.hip.hpp.
 #if !defined(JFGPU_EMU)
 #include <rccl/rccl.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <unistd.h>
-#include <atomic>
-#include <chrono>
-#include <thread>
+
+// the RCCL communicator of a rank, destroyed with it
+struct NcclComm {
+  ncclComm_t h = nullptr;
+  NcclComm() = default;
+  NcclComm(const NcclComm&) = delete;
+  NcclComm& operator=(const NcclComm&) = delete;
+  ~NcclComm() { if(h) ncclCommDestroy(h); }
+  operator ncclComm_t() const { return h; }
+};
 #endif
 
-namespace { struct IpcShared; }
+struct IpcAttachment;                             // comm_ipc.inl
 
+// What a communicator owns goes with it (hip_own.hpp), in the reverse of the order the members are declared in:
+//   1. the ranks' buffers and events   2. d_coll   3. the RCCL communicator   4. the ipc attachment (mappings closed, the
+//   shared block left and, by the last rank, unlinked)   5. the retired send buffers   6. the exchange stream
+// jfgpu_comm_destroy sets the device and drains the exchange stream and the ranks' table streams first.
 struct jfgpu_comm {
   int world = 1, rank = 0, device = 0;
   Tuning tun = Tuning::from_env();               // the JFGPU_* switches as they were at creation (tuning.hpp)
-  bool local = false;
-#if !defined(JFGPU_EMU)
-  ncclComm_t nccl = nullptr;
-#endif
-  hipStream_t xstream = nullptr;                 // exchange stream
-  uint64_t* d_coll = nullptr;                    // [512] staging of the small host-level collectives
+  bool local = false, ipc = false;
   uint64_t max_msg_keys = (uint64_t)1 << 27;     // 1 GiB per peer per round (a 6.9 GB self-message was dropped by RCCL 2.26)
   bool self_rccl = false;                        // JFGPU_COMM_SELF_RCCL=1: a rank's own share travels through ncclSend/ncclRecv as
                                                  // well (default: a device copy) -- lets a single-GPU box exercise every RCCL call
+  bool items_on = true; int items_mode = 1;      // JFGPU_COMM_ITEMS: 0 always send 8-byte keys, 1 items when the step is large enough, 2 items always
+  uint32_t strag_cap = 1u << 16;                 // stragglers per rank and step (JFGPU_COMM_STRAG)
+  uint64_t x_next = 0;                           // exchanges started so far
+  std::vector<std::pair<double, uint64_t>> x_log;   // (device ms, bytes this rank sent over the wires) per exchange, in order
   struct Rank {
     jfgpu_table* t = nullptr;
-    uint64_t* send[2] = {nullptr, nullptr}; size_t send_cap[2] = {0, 0};
-    uint64_t* recv[2] = {nullptr, nullptr}; size_t recv_cap[2] = {0, 0};
-    unsigned long long* d_cnt = nullptr;         // [world] device counters of the routing pass
-    uint64_t* d_xc = nullptr;                    // [2 * world] staging of the counts exchange (send | recv)
+    DevBuf<uint64_t> send[2], recv[2];
+    DevBuf<unsigned long long> d_cnt;            // [world] device counters of the routing pass
+    DevBuf<uint64_t> d_xc;                       // [2 * world] staging of the counts exchange (send | recv)
     std::vector<uint64_t> scount[2], soff[2], rcount[2], roff[2];
-    hipEvent_t routed[2] = {nullptr, nullptr}, exchanged[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
+    Event routed[2], exchanged[2], consumed[2];
     bool used[2] = {false, false};
     int turn = 0; bool inflight = false;
     uint64_t sent = 0, received = 0;
     // item path (see comm_route_items): this step's region capacity (0: the step went as 8-byte keys), the P1 cursors,
     // k-mers per input byte seen so far (sizes the regions)
     uint32_t icap[2] = {0, 0};
-    unsigned int* d_gcur = nullptr;              // gcur[2 * 1024] (u32) then tot[1024] (u64)
-    unsigned long long* d_claimed = nullptr;     // k-mers the senders said they sent here (item path), summed on the device
-    unsigned long long* d_arrived = nullptr;     // [2]: k-mers the receive side actually found in what arrived (regions split + direct inserts + stragglers kept); scratch word
+    DevBuf<unsigned int> d_gcur;                 // gcur[2 * 1024] (u32) then tot[1024] (u64)
+    DevBuf<unsigned long long> d_claimed;        // k-mers the senders said they sent here (item path), summed on the device
+    DevBuf<unsigned long long> d_arrived;        // [2]: k-mers the receive side actually found in what arrived (regions split + direct inserts + stragglers kept); scratch word
     double ipb = 0;
     uint64_t strag_seen = 0;
-    uint64_t* d_route = nullptr;                 // [2] items stored / stragglers of the routing pass in flight
-    uint64_t* h_route = nullptr;                 // ... pinned copy, read after route_done
-    hipEvent_t route_done = nullptr;
+    DevBuf<uint64_t> d_route;                    // [2] items stored / stragglers of the routing pass in flight
+    PinBuf<uint64_t> h_route;                    // ... pinned copy, read after route_done
+    Event route_done;
     size_t route_n = 0;                          // its input bytes
     const uint32_t* self_items[2] = {nullptr, nullptr};   // item path, RCCL transport: the rank's own share is read where the routing left it (send[turn]), not copied
     // exchange timing (jfgpu_comm_exchange_times): a pair of timing events per turn, open while its exchange may be running
-    hipEvent_t x_begin[2] = {nullptr, nullptr}, x_end[2] = {nullptr, nullptr};
+    Event x_begin[2], x_end[2];
     bool x_open[2] = {false, false}; uint64_t x_seq[2] = {0, 0}, x_bytes[2] = {0, 0};
   };
-  uint64_t x_next = 0;                           // exchanges started so far
-  std::vector<std::pair<double, uint64_t>> x_log;   // (device ms, bytes this rank sent over the wires) per exchange, in order
-#if !defined(JFGPU_EMU)
-  // "ipc" transport (see the head of this file)
-  IpcShared* shm = nullptr; std::string shm_name;
-  struct PeerMap { void* ptr = nullptr; uint64_t epoch = 0; };
-  std::vector<PeerMap> peer_send[2];             // peers' send buffers as mapped here, per turn
-  std::vector<void*> stale_maps;                 // mappings of send buffers the peers have replaced since (closed with the communicator)
-  uint64_t send_epoch[2] = {0, 0}; void* send_exported[2] = {nullptr, nullptr}; size_t send_exported_cap[2] = {0, 0};
-  uint32_t barrier_gen = 0;
-#endif
-  bool ipc = false;
+  Stream xstream;                                // exchange stream
   // ipc transport: send buffers given up while a peer may still have them mapped (freed after the next exchange of their turn,
   // by when every peer has let go of its mapping: see comm_reserve_send)
-  std::vector<void*> send_retired[2];
-  bool items_on = true; int items_mode = 1;      // JFGPU_COMM_ITEMS: 0 always send 8-byte keys, 1 items when the step is large enough, 2 items always
-  uint32_t strag_cap = 1u << 16;                 // stragglers per rank and step (JFGPU_COMM_STRAG)
-  std::vector<Rank> ranks;                       // RCCL transport: one; local transport: `world`
+  std::vector<DevBuf<uint64_t>> send_retired[2];
+  std::unique_ptr<IpcAttachment> att;            // "ipc" transport: the shared block and the peers' mappings
+#if !defined(JFGPU_EMU)
+  NcclComm nccl;
+#endif
+  DevBuf<uint64_t> d_coll;                       // [512] staging of the small host-level collectives, allocated at the first one
+  std::vector<Rank> ranks;                       // RCCL and ipc transports: one; local transport: `world`
+  ~jfgpu_comm();                                 // (defined below comm_ipc.inl, where the attachment is a complete type)
 };
 
 namespace {
 
 // JFGPU_COMM_TRACE=1: every rank says on stderr where it is in the exchange (a stuck run shows who waits for whom).
 #define IPC_TRACE(c, ...) do { if((c)->tun.comm_trace) { fprintf(stderr, "[comm rank %d] ", (c)->rank); fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while(0)
-
-int comm_reserve(uint64_t*& buf, size_t& cap, size_t need, hipStream_t s1, hipStream_t s2);
-int comm_reserve_send(jfgpu_comm* c, jfgpu_comm::Rank& R, int turn, size_t need, hipStream_t s1);
 
 // the communicator's share of the JFGPU_* switches (tuning.hpp), applied once at creation
 void comm_apply_tuning(jfgpu_comm* c) {
@@ -105,25 +103,19 @@ void comm_apply_tuning(jfgpu_comm* c) {
 }
 
 int comm_init_rank(jfgpu_comm* c, jfgpu_comm::Rank& R) {
+  int rc;
   for(int i = 0; i < 2; ++i) {
-    HIP_TRY(hipEventCreateWithFlags(&R.routed[i], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&R.exchanged[i], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&R.consumed[i], hipEventDisableTiming));
+    if((rc = R.routed[i].create(hipEventDisableTiming)) || (rc = R.exchanged[i].create(hipEventDisableTiming)) || (rc = R.consumed[i].create(hipEventDisableTiming))) return rc;
     R.scount[i].assign(c->world, 0); R.soff[i].assign(c->world + 1, 0); R.rcount[i].assign(c->world, 0); R.roff[i].assign(c->world + 1, 0);
-    HIP_TRY(hipEventCreate(&R.x_begin[i]));
-    HIP_TRY(hipEventCreate(&R.x_end[i]));
+    if((rc = R.x_begin[i].create()) || (rc = R.x_end[i].create())) return rc;
   }
-  HIP_TRY(hipMalloc((void**)&R.d_cnt, sizeof(unsigned long long) * c->world));
-  HIP_TRY(hipMalloc((void**)&R.d_xc, sizeof(uint64_t) * 2 * c->world));
-  HIP_TRY(hipMalloc((void**)&R.d_gcur, 1024 * 16));
-  HIP_TRY(hipMalloc((void**)&R.d_claimed, 8));
+  if((rc = R.d_cnt.alloc(c->world)) || (rc = R.d_xc.alloc(2 * (size_t)c->world)) || (rc = R.d_gcur.alloc(1024 * 4))) return rc;
+  if((rc = R.d_claimed.alloc(1))) return rc;
   HIP_TRY(hipMemset(R.d_claimed, 0, 8));
-  HIP_TRY(hipMalloc((void**)&R.d_arrived, 16));
+  if((rc = R.d_arrived.alloc(2))) return rc;
   HIP_TRY(hipMemset(R.d_arrived, 0, 16));
-  HIP_TRY(hipMalloc((void**)&R.d_route, 2 * sizeof(uint64_t)));
-  HIP_TRY(hipHostMalloc((void**)&R.h_route, 2 * sizeof(uint64_t), hipHostMallocDefault));
-  HIP_TRY(hipEventCreateWithFlags(&R.route_done, hipEventDisableTiming));
-  return JFGPU_OK;
+  if((rc = R.d_route.alloc(2)) || (rc = R.h_route.alloc(2))) return rc;
+  return R.route_done.create(hipEventDisableTiming);
 }
 
 // ---- the item path: 4 bytes per k-mer, already grouped for the receiver ------------------------------------------
@@ -135,11 +127,25 @@ int comm_init_rank(jfgpu_comm* c, jfgpu_comm::Rank& R) {
 // that looks like a hole) goes on a short list every rank receives.  A step falls back to 8-byte keys on all ranks when
 // any rank says so: geometry (2k - 10 > 32 bits, fewer than 2^23 slots per shard), steps too small for fixed regions,
 // or more stragglers than the list holds.
+//
+// The message's layout, the only place that knows it (the kernels are handed the pointers):
+//   send buffer: items[nbg * cap] | offs[2 * nbg] | claims[W] | strag[1 + S]
+//   recv buffer: items[nbg * cap] | offs[2 * nbg] | claims[W] | W x strag[1 + S]
+// (claims[p]: k-mers the sender says it sends to rank p: bookkeeping for sent == received.)  Peer p's piece of the first
+// three sits at the same place in both: in a send buffer what goes to p, in a receive buffer what came from p.
 struct ItemLayout {
   uint32_t cap, nbg, nbc, gbits, cbits, split_bits, S;
-  size_t items_bytes, offs_at, claims_at, strag_at, send_bytes;   // send buffer: items[nbg * cap] | offs[2 * nbg] | claims[W] | strag[1 + S]
-  size_t r_offs_at, r_claims_at, r_strag_at, recv_bytes;          // recv buffer: items[nbg * cap] | offs[2 * nbg] | claims[W] | W x strag[1 + S]
-};                                                                // (claims[p]: k-mers the sender says it sends to rank p: bookkeeping for sent == received)
+  size_t items_bytes, offs_at, claims_at, strag_at, send_bytes, recv_bytes;
+  size_t blk() const { return (size_t)nbc * cap; }                       // items of a (sender, receiver) message
+  size_t offs_n() const { return (size_t)2 * nbc; }                      // its offsets
+  size_t strag_n() const { return (size_t)1 + S; }                       // words of a straggler list
+  static uint8_t* at(const void* buf, size_t bytes) { return const_cast<uint8_t*>(static_cast<const uint8_t*>(buf)) + bytes; }
+  uint32_t* items(const void* buf, int p) const { return reinterpret_cast<uint32_t*>(at(buf, 0)) + (size_t)p * blk(); }
+  uint64_t* offs(const void* buf, int p) const { return reinterpret_cast<uint64_t*>(at(buf, offs_at)) + (size_t)p * offs_n(); }
+  uint64_t* claims(const void* buf, int p) const { return reinterpret_cast<uint64_t*>(at(buf, claims_at)) + p; }
+  uint64_t* send_strag(const void* sbuf) const { return reinterpret_cast<uint64_t*>(at(sbuf, strag_at)); }                        // the sender's one list
+  uint64_t* recv_strag(const void* rbuf, int p) const { return reinterpret_cast<uint64_t*>(at(rbuf, strag_at)) + (size_t)p * strag_n(); }   // the list that came from p
+};
 // nbg = 2^gbits sender buckets = W owners x nbc = 2^cbits coarse buckets each; the receiver splits a coarse bucket into
 // 2^split_bits of its own 2^b1 P1 buckets (b1 = cbits + split_bits).  gbits = min(10, shard_bits + b1).
 ItemLayout item_layout(const jfgpu_comm* c, const jfgpu_table* t, uint32_t cap) {
@@ -149,10 +155,25 @@ ItemLayout item_layout(const jfgpu_comm* c, const jfgpu_table* t, uint32_t cap) 
   L.cap = cap; L.nbg = 1u << L.gbits; L.nbc = 1u << L.cbits; L.S = c->strag_cap;
   L.items_bytes = align_up((size_t)L.nbg * cap * 4, 256);
   L.offs_at = L.items_bytes; L.claims_at = L.offs_at + (size_t)2 * L.nbg * 8; L.strag_at = L.claims_at + 1024 * 8;
-  L.send_bytes = L.strag_at + (size_t)(1 + L.S) * 8;
-  L.r_offs_at = L.items_bytes; L.r_claims_at = L.r_offs_at + (size_t)2 * L.nbg * 8; L.r_strag_at = L.r_claims_at + 1024 * 8;
-  L.recv_bytes = L.r_strag_at + (size_t)c->world * (1 + L.S) * 8;
+  L.send_bytes = L.strag_at + L.strag_n() * 8;
+  L.recv_bytes = L.strag_at + (size_t)c->world * L.strag_n() * 8;
   return L;
+}
+
+// Sender s's share for receiver d, out of s's send buffer into d's receive buffer on the exchange stream.  with_items
+// false: the regions stay where they are (the RCCL transport's own share, read from the send buffer).
+int comm_copy_share(jfgpu_comm* c, const ItemLayout& L, void* rbuf, int s, const void* sbuf, int d, bool with_items) {
+  if(with_items) {
+    HIP_TRY(hipMemcpyAsync(L.items(rbuf, s), L.items(sbuf, d), L.blk() * 4, hipMemcpyDeviceToDevice, c->xstream));
+    IPC_TRACE(c, "items: regions copy enqueued (%zu bytes)", L.blk() * 4);
+  }
+  HIP_TRY(hipMemcpyAsync(L.offs(rbuf, s), L.offs(sbuf, d), L.offs_n() * 8, hipMemcpyDeviceToDevice, c->xstream));
+  IPC_TRACE(c, "items: offsets copy enqueued");
+  HIP_TRY(hipMemcpyAsync(L.claims(rbuf, s), L.claims(sbuf, d), 8, hipMemcpyDeviceToDevice, c->xstream));
+  IPC_TRACE(c, "items: claims copy enqueued");
+  HIP_TRY(hipMemcpyAsync(L.recv_strag(rbuf, s), L.send_strag(sbuf), L.strag_n() * 8, hipMemcpyDeviceToDevice, c->xstream));
+  IPC_TRACE(c, "items: straggler list copy enqueued");
+  return JFGPU_OK;
 }
 
 bool items_geometry_ok(const jfgpu_comm* c, const jfgpu_table* t) {
@@ -182,32 +203,11 @@ uint32_t items_cap_wanted(const jfgpu_comm* c, const jfgpu_comm::Rank& R, size_t
   if(mean < 4 * strand && c->items_mode < 2) return 0;                      // regions would be mostly holes (2: forced, for tests)
   const uint64_t cap = ((uint64_t)((double)mean * (1.0 + slack)) + strand + kGran - 1) / kGran * kGran;
   if(cap > 0x7FFF0000ull) return 0;
-#if !defined(JFGPU_EMU)
   // (inter-process test transport, observed and not understood: with item-path send buffers of 2.6 GB and more the first
   //  hipIpcOpenMemHandle of a peer's buffer never returns -- 1.8 GB is fine, and so are 5 GB buffers of the key path and
   //  any size in tools/probes/r03_ipc_size_probe.hip.  Steps that large go as keys there.)
   if(c->ipc && (uint64_t)L.nbg * cap * 5 > ((uint64_t)1 << 31)) return 0;
-#endif
   return (uint32_t)cap;
-}
-
-// What every owner is being sent by this rank (its regions' items + its stragglers), written where the exchange takes it
-// from (claims[W] of the send buffer), and the two numbers the host wants back (items stored, stragglers): on the device,
-// so that the host has nothing to compute between the routing kernel and the exchange.
-__global__ __launch_bounds__(1024) void comm_claims_kernel(const unsigned long long* __restrict__ tot, uint32_t nbg, uint32_t nbc, const uint64_t* __restrict__ strag,
-                                                            uint32_t S, uint32_t world, uint64_t* __restrict__ claims, uint64_t* __restrict__ summary) {
-  __shared__ unsigned long long s_claims[512];
-  __shared__ unsigned long long s_stored;
-  for(uint32_t p = threadIdx.x; p < world; p += blockDim.x) s_claims[p] = 0;
-  if(threadIdx.x == 0) s_stored = 0;
-  lds_barrier();
-  for(uint32_t j = threadIdx.x; j < nbg; j += blockDim.x) { const unsigned long long v = tot[j]; if(v) { atomicAdd(&s_claims[j / nbc], v); atomicAdd(&s_stored, v); } }
-  const uint64_t ns = strag[0];
-  const uint64_t nl = ns < S ? ns : S;
-  for(uint64_t i = threadIdx.x; i < nl; i += blockDim.x) atomicAdd(&s_claims[(uint32_t)(strag[1 + i] >> 32) / nbc], 1ull);
-  lds_barrier();
-  for(uint32_t p = threadIdx.x; p < world; p += blockDim.x) claims[p] = s_claims[p];
-  if(threadIdx.x == 0) { summary[0] = s_stored; summary[1] = ns; }
 }
 
 // A Bloom counter attached to a shard (count --bc) is asked on the SENDING side, every rank holding the whole read-only
@@ -222,6 +222,32 @@ int comm_filter_ok(const jfgpu_table* t) {
   return JFGPU_OK;
 }
 
+// An exchange buffer of at least `need` words; its contents are not kept.  Not DevBuf::reserve: the head-room is this
+// path's own, and the old block goes only when nothing on the two streams can still touch it.
+int comm_reserve(DevBuf<uint64_t>& buf, size_t need, hipStream_t s1, hipStream_t s2) {
+  if(need <= buf.cap()) return JFGPU_OK;
+  HIP_TRY(hipStreamSynchronize(s1)); HIP_TRY(hipStreamSynchronize(s2));
+  return buf.alloc(need + need / 4 + 1024);        // steps differ in size: head-room, so that the buffers are not re-allocated mid-job
+}
+
+// A SEND buffer of the ipc transport is mapped by the peers.  Freeing it under their mappings and allocating the larger one
+// right away made the peers read stale memory through the handle of the new buffer (round 6: shards that grow with most of
+// their entries leaving -- the xor-shift family, world 4 -- re-allocate both send buffers inside comm_grow, and the pairs
+// arrived wrong: profiles/r06_ipc_realloc.log).  So the old buffer is only RETIRED here; it is freed after the next exchange
+// of its turn, whose import phase makes every peer close its mapping of it before the new handle is opened.
+int comm_reserve_send(jfgpu_comm* c, jfgpu_comm::Rank& R, int turn, size_t need, hipStream_t s1) {
+  if(need <= R.send[turn].cap()) return JFGPU_OK;
+  if(c->ipc && R.send[turn]) {
+    HIP_TRY(hipStreamSynchronize(s1)); HIP_TRY(hipStreamSynchronize(c->xstream));
+    c->send_retired[turn].push_back(std::move(R.send[turn]));
+  }
+  return comm_reserve(R.send[turn], need, s1, c->xstream);
+}
+void comm_free_retired(jfgpu_comm* c, int turn) {
+  if(c->tun.comm_ipc_keep) return;                             // (kept until the communicator goes: see tuning.hpp, JFGPU_IPC_KEEP)
+  c->send_retired[turn].clear();
+}
+
 // P1 over the global table into send[cur]: enqueued here, looked at in comm_route_items_complete -- between the two the
 // caller enqueues the insert of what arrived for the previous step, so the device has work while the host waits for the
 // two numbers it needs (stragglers, exact item count).
@@ -233,10 +259,10 @@ int comm_route_items_enqueue(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_b
   if(R.used[cur]) HIP_TRY(hipEventSynchronize(R.exchanged[cur]));       // send[cur] has left (step - 2)
   int rc = comm_reserve_send(c, R, cur, (L.send_bytes + 7) / 8, t->stream); if(rc) return rc;
   if(!R.used[cur ^ 1]) { rc = comm_reserve_send(c, R, cur ^ 1, (L.send_bytes + 7) / 8, t->stream); if(rc) return rc; }   // (both buffers of the pair at once)
-  uint8_t* sb = reinterpret_cast<uint8_t*>(R.send[cur]);
-  uint32_t* items = reinterpret_cast<uint32_t*>(sb);
-  uint64_t* offs = reinterpret_cast<uint64_t*>(sb + L.offs_at);
-  uint64_t* strag = reinterpret_cast<uint64_t*>(sb + L.strag_at);
+  const uint64_t* sb = R.send[cur];
+  uint32_t* items = L.items(sb, 0);
+  uint64_t* offs = L.offs(sb, 0);
+  uint64_t* strag = L.send_strag(sb);
   unsigned long long* tot = reinterpret_cast<unsigned long long*>(R.d_gcur + 2 * L.nbg);
   HIP_TRY(hipMemsetAsync(R.d_gcur, 0, 1024 * 16, t->stream));
   HIP_TRY(hipMemsetAsync(strag, 0, 8, t->stream));
@@ -253,20 +279,21 @@ int comm_route_items_enqueue(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_b
     const dim3 grid(t->n_cu), block(kPBlock);
     const size_t lds = ((size_t)1 << pg.b1) * 128 + 128;
     ProfScope ps(t, 2, n);
+    unsigned int* gcur = R.d_gcur;
     // the count path's ring P1 (kernels_p1ring.hip.hpp) over the global geometry; what it cannot store goes on the list
-#define PR(N, CN) hipLaunchKernelGGL((p1_ring_kernel<uint32_t, false, N, CN, RouteListDirect>), grid, block, lds, t->stream, gv, rd, pg, base, lo, hi, cap, R.d_gcur, tot, items, t->d_strag, t->d_strag_n)
+#define PR(N, CN) hipLaunchKernelGGL((p1_ring_kernel<uint32_t, false, N, CN, RouteListDirect>), grid, block, lds, t->stream, gv, rd, pg, base, lo, hi, cap, gcur, tot, items, t->d_strag, t->d_strag_n)
     if(t->dt.bloom.data)      // count --bc: the sender asks its copy of the Bloom counter (read-only: the same answer on every rank)
-      hipLaunchKernelGGL((p1_ring_kernel<uint32_t, true, 0, 2, RouteListDirect>), grid, block, lds, t->stream, gv, rd, pg, base, lo, hi, cap, R.d_gcur, tot, items, t->d_strag, t->d_strag_n);
+      hipLaunchKernelGGL((p1_ring_kernel<uint32_t, true, 0, 2, RouteListDirect>), grid, block, lds, t->stream, gv, rd, pg, base, lo, hi, cap, gcur, tot, items, t->d_strag, t->d_strag_n);
     else if(t->g.hash_xs && gv.g.lsize_g > 32 && gv.g.lsize_g < 64 && gv.g.lsize_g - pg.b1 < 32) { if(t->g.canonical) PR(kHashXS, 1); else PR(kHashXS, 0); }
     else if(t->g.hash_xs) PR(kHashXSLow, 2);
     else if(t->g.nbytes == 6) { if(t->g.canonical) PR(6, 1); else PR(6, 0); } else PR(0, 2);
 #undef PR
     hipLaunchKernelGGL((p1_stragglers_kernel<uint32_t, RouteListDirect>), dim3(t->n_cu), dim3(256), 0, t->stream, rd, (unsigned long long*)nullptr, (const uint64_t*)t->d_strag,
-                       (const uint32_t*)t->d_strag_n, (uint32_t)t->n_cu, cap, R.d_gcur, tot, items, kStragPerBlock);
+                       (const uint32_t*)t->d_strag_n, (uint32_t)t->n_cu, cap, gcur, tot, items, kStragPerBlock);
   }
-  hipLaunchKernelGGL(granule_finish_kernel, dim3(4), dim3(256), 0, t->stream, R.d_gcur, cap, L.nbg, offs);
+  hipLaunchKernelGGL(granule_finish_kernel, dim3(4), dim3(256), 0, t->stream, R.d_gcur.get(), cap, L.nbg, offs);
   hipLaunchKernelGGL(comm_claims_kernel, dim3(1), dim3(1024), 0, t->stream, tot, L.nbg, L.nbc, (const uint64_t*)strag, L.S, (uint32_t)c->world,
-                     reinterpret_cast<uint64_t*>(sb + L.claims_at), R.d_route);
+                     L.claims(sb, 0), R.d_route.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(R.h_route, R.d_route, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
   HIP_TRY(hipEventRecord(R.route_done, t->stream));
@@ -287,24 +314,6 @@ int comm_route_items_complete(jfgpu_comm* c, jfgpu_comm::Rank& R, uint32_t cap, 
   if(t->tun.flush_trace)
     fprintf(stderr, "[comm] item path: %zu bytes -> %llu items in %u regions of %u, %llu stragglers\n", R.route_n, (unsigned long long)stored, L.nbg, cap, (unsigned long long)ns);
   return JFGPU_OK;
-}
-
-__global__ void comm_add_claims_kernel(const uint64_t* __restrict__ claims, int n, unsigned long long* __restrict__ total) {
-  if(blockIdx.x == 0 && threadIdx.x == 0) { unsigned long long s = 0; for(int i = 0; i < n; ++i) s += claims[i]; *total += s; }
-}
-
-// The receiver's own count of what arrived (the claims above are the senders' word): before the split, remember the
-// table's direct-insert counter; after it, add what the split stored in its regions (tot[]) and what it inserted directly.
-__global__ void comm_mark_direct_kernel(const uint64_t* __restrict__ counters, unsigned long long* __restrict__ arrived) {
-  if(blockIdx.x == 0 && threadIdx.x == 0) arrived[1] = counters[CTR_DIRECT];
-}
-__global__ void comm_count_arrived_kernel(const unsigned long long* __restrict__ tot, uint32_t nb, const uint64_t* __restrict__ counters,
-                                          unsigned long long* __restrict__ arrived) {
-  unsigned long long s = 0;
-  for(uint32_t j = threadIdx.x; j < nb; j += blockDim.x) s += tot[j];
-  for(int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-  if((threadIdx.x & 63) == 0 && s) atomicAdd(&arrived[0], s);
-  if(threadIdx.x == 0) atomicAdd(&arrived[0], (unsigned long long)(counters[CTR_DIRECT] - arrived[1]));
 }
 
 // What arrived for the previous step (item path): one split of every coarse bucket into the shard's own P1 buckets, then
@@ -347,12 +356,11 @@ int comm_insert_prev_items(jfgpu_comm* c, jfgpu_comm::Rank& R, int rank) {
   if(!b.items || !b.off || !gcur) return fail(JFGPU_E_ALLOC, "partition workspace exhausted");
   b.gran_cap = cap2; b.tot = (unsigned long long*)(gcur + 2 * nb);
   HIP_TRY(hipMemsetAsync(gcur, 0, nb * 16, t->stream));
-  const uint8_t* rb = reinterpret_cast<const uint8_t*>(R.recv[prev]);
-  const uint32_t* r_items = reinterpret_cast<const uint32_t*>(rb);
-  const uint64_t* r_offs = reinterpret_cast<const uint64_t*>(rb + L.r_offs_at);
-  const uint64_t* r_strag = reinterpret_cast<const uint64_t*>(rb + L.r_strag_at);
-  hipLaunchKernelGGL(comm_add_claims_kernel, dim3(1), dim3(64), 0, t->stream, reinterpret_cast<const uint64_t*>(rb + L.r_claims_at), W, R.d_claimed);
-  hipLaunchKernelGGL(comm_mark_direct_kernel, dim3(1), dim3(64), 0, t->stream, t->dt.counters, R.d_arrived);
+  const uint64_t* rb = R.recv[prev];
+  const uint32_t* r_items = L.items(rb, 0);
+  const uint64_t* r_offs = L.offs(rb, 0);
+  hipLaunchKernelGGL(comm_add_claims_kernel, dim3(1), dim3(64), 0, t->stream, (const uint64_t*)L.claims(rb, 0), W, R.d_claimed.get());
+  hipLaunchKernelGGL(comm_mark_direct_kernel, dim3(1), dim3(64), 0, t->stream, t->dt.counters, R.d_arrived.get());
   // sender p's regions of my coarse buckets sit at r_items + p * nbc * cap, its offsets speak of its own whole output
   // (bucket j of 1024 at j * cap): bases shifted so that "bucket = rank * nbc + coarse" finds both
   SegList S; memset(&S, 0, sizeof S);
@@ -376,6 +384,7 @@ int comm_insert_prev_items(jfgpu_comm* c, jfgpu_comm::Rank& R, int rank) {
     unsigned int* gc_v = gcur - dshift; unsigned int* gs_v = gcur + nb - dshift;
     uint32_t* out_v = reinterpret_cast<uint32_t*>(b.items) - dshift * (int64_t)cap2;
     unsigned long long* tot_v = b.tot - dshift;
+    unsigned long long* arrived = R.d_arrived;
     // (fan-out 2^sb <= 16: the packed-counter ranking of p2_granule_kernel, with 1, 2 or 4 words of four destinations)
 #define SPLIT(RT, SW) hipLaunchKernelGGL((p2_granule_kernel<uint32_t, TableDirect<RT>, kP2PairPer, SW>), grid, block, lds, t->stream, \
                         TableDirect<RT>{t->d_dt, pd, (unsigned long long*)&t->dt.counters[CTR_DIRECT]}, sb, split_at, S, cap2, gc_v, gs_v, out_v, (uint32_t)first, tot_v, L.nbc - 1)
@@ -393,11 +402,11 @@ int comm_insert_prev_items(jfgpu_comm* c, jfgpu_comm::Rank& R, int rank) {
     else             { if(sb <= 2) SPLIT(false, 1); else if(sb == 3) SPLIT(false, 2); else SPLIT(false, 4); }
 #undef SPLIT
     hipLaunchKernelGGL(granule_finish_kernel, dim3(4), dim3(256), 0, t->stream, gcur, cap2, nb, b.off);
-    hipLaunchKernelGGL(comm_count_arrived_kernel, dim3(1), dim3(256), 0, t->stream, b.tot, nb, t->dt.counters, R.d_arrived);
+    hipLaunchKernelGGL(comm_count_arrived_kernel, dim3(1), dim3(256), 0, t->stream, b.tot, nb, t->dt.counters, arrived);
     for(int p = 0; p < W; ++p) {
-      const uint64_t* lst = r_strag + (size_t)p * (1 + L.S);
-      if(t->returning) hipLaunchKernelGGL(straggler_insert_kernel<true>, dim3(64), dim3(kBlock), 0, t->stream, t->dt, pd, lst + 1, (const unsigned long long*)lst, L.S, (uint32_t)rank, L.cbits, R.d_arrived);
-      else             hipLaunchKernelGGL(straggler_insert_kernel<false>, dim3(64), dim3(kBlock), 0, t->stream, t->dt, pd, lst + 1, (const unsigned long long*)lst, L.S, (uint32_t)rank, L.cbits, R.d_arrived);
+      const uint64_t* lst = L.recv_strag(rb, p);
+      if(t->returning) hipLaunchKernelGGL(straggler_insert_kernel<true>, dim3(64), dim3(kBlock), 0, t->stream, t->dt, pd, lst + 1, (const unsigned long long*)lst, L.S, (uint32_t)rank, L.cbits, arrived);
+      else             hipLaunchKernelGGL(straggler_insert_kernel<false>, dim3(64), dim3(kBlock), 0, t->stream, t->dt, pd, lst + 1, (const unsigned long long*)lst, L.S, (uint32_t)rank, L.cbits, arrived);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -418,37 +427,6 @@ int comm_insert_prev_items(jfgpu_comm* c, jfgpu_comm::Rank& R, int rank) {
   HIP_TRY(hipEventRecord(R.consumed[prev], t->stream));
   R.inflight = false;
   return JFGPU_OK;
-}
-
-int comm_reserve(uint64_t*& buf, size_t& cap, size_t need, hipStream_t s1, hipStream_t s2) {
-  if(need <= cap) return JFGPU_OK;
-  HIP_TRY(hipStreamSynchronize(s1)); HIP_TRY(hipStreamSynchronize(s2));
-  if(buf) hipFree(buf);
-  buf = nullptr; cap = 0;
-  const size_t want = need + need / 4 + 1024;      // steps differ in size: head-room, so that the buffers are not re-allocated mid-job
-  HIP_TRY(hipMalloc((void**)&buf, want * sizeof(uint64_t)));
-  cap = want;
-  return JFGPU_OK;
-}
-
-// A SEND buffer of the ipc transport is mapped by the peers.  Freeing it under their mappings and allocating the larger one
-// right away made the peers read stale memory through the handle of the new buffer (round 6: shards that grow with most of
-// their entries leaving -- the xor-shift family, world 4 -- re-allocate both send buffers inside comm_grow, and the pairs
-// arrived wrong: profiles/r06_ipc_realloc.log).  So the old buffer is only RETIRED here; it is freed after the next exchange
-// of its turn, whose import phase makes every peer close its mapping of it before the new handle is opened.
-int comm_reserve_send(jfgpu_comm* c, jfgpu_comm::Rank& R, int turn, size_t need, hipStream_t s1) {
-  if(need <= R.send_cap[turn]) return JFGPU_OK;
-  if(c->ipc && R.send[turn]) {
-    HIP_TRY(hipStreamSynchronize(s1)); HIP_TRY(hipStreamSynchronize(c->xstream));
-    c->send_retired[turn].push_back(R.send[turn]);
-    R.send[turn] = nullptr; R.send_cap[turn] = 0;
-  }
-  return comm_reserve(R.send[turn], R.send_cap[turn], need, s1, c->xstream);
-}
-void comm_free_retired(jfgpu_comm* c, int turn, bool closing = false) {
-  if(c->tun.comm_ipc_keep && !closing) return;                 // (kept until the communicator goes: see tuning.hpp, JFGPU_IPC_KEEP)
-  for(void* p : c->send_retired[turn]) hipFree(p);
-  c->send_retired[turn].clear();
 }
 
 // Route one contract buffer of rank R into send[cur], grouped by owner (route_buffer, jfgpu.hip); fills scount / soff from
@@ -475,7 +453,6 @@ int comm_route(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_bases, size_t n
 }
 
 // What arrived for the previous step goes into the table (P1 from keys: pending batch applied at the next flush).
-int comm_insert_prev_items(jfgpu_comm* c, jfgpu_comm::Rank& R, int rank);
 int comm_insert_prev(jfgpu_comm* c, jfgpu_comm::Rank& R) {
   if(!R.inflight) return JFGPU_OK;
   const int prev = R.turn ^ 1;
@@ -483,6 +460,7 @@ int comm_insert_prev(jfgpu_comm* c, jfgpu_comm::Rank& R) {
   jfgpu_table* t = R.t;
   HIP_TRY(hipStreamWaitEvent(t->stream, R.exchanged[prev], 0));
   const uint64_t n = R.roff[prev][c->world] / t->key_words;               // k-mers that arrived (the offsets are in words)
+  const uint64_t* arrived = R.recv[prev];
   int rc = JFGPU_OK;
   // what the table does with a k-mer (jfgpu_set_operation: the passes of count --if) holds for what arrives, too
   if(n && t->operation == 2) {
@@ -491,23 +469,18 @@ int comm_insert_prev(jfgpu_comm* c, jfgpu_comm::Rank& R) {
     const int grid = grid_for(t, (n + kBlock - 1) / kBlock);
     with_view(t, [&](const auto& T) {
       typedef std::decay_t<decltype(T)> Table;
-      if constexpr(KeyOps<Table>::kUpdateReturns) hipLaunchKernelGGL((update_keys_kernel<Table, true>), dim3(grid), dim3(kBlock), 0, t->stream, T, (const uint64_t*)R.recv[prev], (uint64_t)n, t->key_words);
-      else if(t->returning) hipLaunchKernelGGL((update_keys_kernel<Table, true>), dim3(grid), dim3(kBlock), 0, t->stream, T, (const uint64_t*)R.recv[prev], (uint64_t)n, t->key_words);
-      else hipLaunchKernelGGL((update_keys_kernel<Table, false>), dim3(grid), dim3(kBlock), 0, t->stream, T, (const uint64_t*)R.recv[prev], (uint64_t)n, t->key_words);
+      if constexpr(KeyOps<Table>::kUpdateReturns) hipLaunchKernelGGL((update_keys_kernel<Table, true>), dim3(grid), dim3(kBlock), 0, t->stream, T, arrived, (uint64_t)n, t->key_words);
+      else if(t->returning) hipLaunchKernelGGL((update_keys_kernel<Table, true>), dim3(grid), dim3(kBlock), 0, t->stream, T, arrived, (uint64_t)n, t->key_words);
+      else hipLaunchKernelGGL((update_keys_kernel<Table, false>), dim3(grid), dim3(kBlock), 0, t->stream, T, arrived, (uint64_t)n, t->key_words);
     });
     HIP_TRY(hipGetLastError());
-  } else if(n) rc = add_keys_piece(t, R.recv[prev], (size_t)n, t->operation == 1 ? 0 : 1, nullptr);
+  } else if(n) rc = add_keys_piece(t, arrived, (size_t)n, t->operation == 1 ? 0 : 1, nullptr);
   HIP_TRY(hipEventRecord(R.consumed[prev], t->stream));
   R.received += n;
   R.inflight = false;
   return rc;
 }
 
-#if !defined(JFGPU_EMU)
-#define NCCL_TRY(expr) do { ncclResult_t r_ = (expr); if(r_ != ncclSuccess) return fail(JFGPU_E_HIP, std::string(#expr) + ": " + ncclGetErrorString(r_)); } while(0)
-#endif
-
-// The exchange of the current step for the RCCL transport: counts (host-visible), then the keys in rounds.
 // exchange timing: harvest a turn's finished pair (the caller knows its exchange is over), open it for the next one
 void comm_x_harvest(jfgpu_comm* c, jfgpu_comm::Rank& R, int turn) {
   if(!R.x_open[turn]) return;
@@ -528,6 +501,38 @@ void comm_x_end(jfgpu_comm* c, jfgpu_comm::Rank& R, int turn, uint64_t wire_byte
   R.x_bytes[turn] = wire_bytes;
 }
 
+// ---- the key path's steps that every transport takes ---------------------------------------------------------------------
+// The receive side of rank R once rcount[cur] is known: where every sender's keys go, recv[cur] free (the insert of
+// step - 2 has read it) and large enough.  pair: on first use the buffer of the other turn is reserved with it.
+int comm_keys_recv_ready(jfgpu_comm* c, jfgpu_comm::Rank& R, bool pair) {
+  const int cur = R.turn, W = c->world;
+  uint64_t total = 0;
+  for(int p = 0; p < W; ++p) { R.roff[cur][p] = total; total += R.rcount[cur][p]; }
+  R.roff[cur][W] = total;
+  if(R.used[cur]) HIP_TRY(hipEventSynchronize(R.consumed[cur]));          // recv[cur] was read by the insert of step - 2
+  int rc = comm_reserve(R.recv[cur], total, R.t->stream, c->xstream); if(rc) return rc;
+  if(pair && !R.used[cur ^ 1]) { rc = comm_reserve(R.recv[cur ^ 1], total, R.t->stream, c->xstream); if(rc) return rc; }
+  return JFGPU_OK;
+}
+// Messages travel in rounds of at most max_msg_keys words per peer: what round r carries of a message of `count` words.
+uint64_t comm_round_len(const jfgpu_comm* c, uint64_t count, uint64_t r) {
+  const uint64_t lo = r * c->max_msg_keys;
+  return count > lo ? std::min(count - lo, c->max_msg_keys) : 0;
+}
+
+}  // namespace
+
+#include "comm_ipc.inl"
+
+jfgpu_comm::~jfgpu_comm() = default;
+
+namespace {
+
+#if !defined(JFGPU_EMU)
+#define NCCL_TRY(expr) do { ncclResult_t r_ = (expr); if(r_ != ncclSuccess) return fail(JFGPU_E_HIP, std::string(#expr) + ": " + ncclGetErrorString(r_)); } while(0)
+#endif
+
+// The exchange of the current step for the RCCL transport: counts (host-visible), then the keys in rounds.
 int comm_exchange_rccl(jfgpu_comm* c) {
 #if defined(JFGPU_EMU)
   (void)c;
@@ -553,13 +558,8 @@ int comm_exchange_rccl(jfgpu_comm* c) {
     HIP_TRY(hipStreamSynchronize(c->xstream));
     for(int p = 0; p < W; ++p) if(p != skip) R.rcount[cur][p] = got[p];
   }
-  uint64_t total = 0, gmax = 0;
-  for(int p = 0; p < W; ++p) { R.roff[cur][p] = total; total += R.rcount[cur][p]; gmax = std::max(gmax, std::max(R.rcount[cur][p], R.scount[cur][p])); }
-  R.roff[cur][W] = total;
-  IPC_TRACE(c, "keys: %llu to pull; waiting for recv[%d] to be consumed", (unsigned long long)total, cur);
-  if(R.used[cur]) HIP_TRY(hipEventSynchronize(R.consumed[cur]));          // recv[cur] was read by the insert of step - 2
-  int rc = comm_reserve(R.recv[cur], R.recv_cap[cur], total, R.t->stream, c->xstream); if(rc) return rc;
-  if(!R.used[cur ^ 1]) { rc = comm_reserve(R.recv[cur ^ 1], R.recv_cap[cur ^ 1], total, R.t->stream, c->xstream); if(rc) return rc; }
+  IPC_TRACE(c, "keys: %llu to pull; waiting for recv[%d] to be consumed", (unsigned long long)std::accumulate(R.rcount[cur].begin(), R.rcount[cur].end(), (uint64_t)0), cur);
+  int rc = comm_keys_recv_ready(c, R, true); if(rc) return rc;
   HIP_TRY(hipEventRecord(R.routed[cur], R.t->stream));
   HIP_TRY(hipStreamWaitEvent(c->xstream, R.routed[cur], 0));
   comm_x_begin(c, R, cur);
@@ -569,7 +569,7 @@ int comm_exchange_rccl(jfgpu_comm* c) {
                            hipMemcpyDeviceToDevice, c->xstream));
   if(via_rccl) {
     // every rank runs the same number of rounds: the largest peer-to-peer message of this step decides
-    unsigned long long lmax = 0, *d_m = (unsigned long long*)R.d_xc;
+    unsigned long long lmax = 0, *d_m = (unsigned long long*)R.d_xc.get();
     for(int p = 0; p < W; ++p) if(p != skip) lmax = std::max<unsigned long long>(lmax, std::max(R.rcount[cur][p], R.scount[cur][p]));
     HIP_TRY(hipMemcpyAsync(d_m, &lmax, sizeof lmax, hipMemcpyHostToDevice, c->xstream));
     NCCL_TRY(ncclAllReduce(d_m, d_m, 1, ncclUint64, ncclMax, c->nccl, c->xstream));
@@ -581,8 +581,7 @@ int comm_exchange_rccl(jfgpu_comm* c) {
       NCCL_TRY(ncclGroupStart());
       for(int p = 0; p < W; ++p) {
         if(p == skip) continue;
-        const uint64_t sc = R.scount[cur][p] > lo ? std::min(R.scount[cur][p] - lo, c->max_msg_keys) : 0;
-        const uint64_t rcn = R.rcount[cur][p] > lo ? std::min(R.rcount[cur][p] - lo, c->max_msg_keys) : 0;
+        const uint64_t sc = comm_round_len(c, R.scount[cur][p], r), rcn = comm_round_len(c, R.rcount[cur][p], r);
         if(sc) NCCL_TRY(ncclSend(R.send[cur] + R.soff[cur][p] + lo, sc, ncclUint64, p, c->nccl, c->xstream));
         if(rcn) NCCL_TRY(ncclRecv(R.recv[cur] + R.roff[cur][p] + lo, rcn, ncclUint64, p, c->nccl, c->xstream));
       }
@@ -601,12 +600,8 @@ int comm_exchange_local(jfgpu_comm* c) {
   const int W = c->world;
   for(int d = 0; d < W; ++d) {                    // receive side bookkeeping of rank d
     jfgpu_comm::Rank& D = c->ranks[d];
-    const int cur = D.turn;
-    uint64_t total = 0;
-    for(int s = 0; s < W; ++s) { D.rcount[cur][s] = c->ranks[s].scount[c->ranks[s].turn][d]; D.roff[cur][s] = total; total += D.rcount[cur][s]; }
-    D.roff[cur][W] = total;
-    if(D.used[cur]) HIP_TRY(hipEventSynchronize(D.consumed[cur]));
-    int rc = comm_reserve(D.recv[cur], D.recv_cap[cur], total, D.t->stream, c->xstream); if(rc) return rc;
+    for(int s = 0; s < W; ++s) D.rcount[D.turn][s] = c->ranks[s].scount[c->ranks[s].turn][d];
+    int rc = comm_keys_recv_ready(c, D, false); if(rc) return rc;
   }
   for(int s = 0; s < W; ++s) {
     jfgpu_comm::Rank& S = c->ranks[s];
@@ -621,7 +616,7 @@ int comm_exchange_local(jfgpu_comm* c) {
     for(int s = 0; s < W; ++s)
       for(int d = 0; d < W; ++d) {
         jfgpu_comm::Rank &S = c->ranks[s], &D = c->ranks[d];
-        const uint64_t n = S.scount[S.turn][d] > lo ? std::min(S.scount[S.turn][d] - lo, c->max_msg_keys) : 0;
+        const uint64_t n = comm_round_len(c, S.scount[S.turn][d], r);
         if(n) HIP_TRY(hipMemcpyAsync(D.recv[D.turn] + D.roff[D.turn][s] + lo, S.send[S.turn] + S.soff[S.turn][d] + lo, n * sizeof(uint64_t),
                                      hipMemcpyDeviceToDevice, c->xstream));
       }
@@ -644,33 +639,22 @@ int comm_exchange_items_rccl(jfgpu_comm* c) {
   const int cur = R.turn, W = c->world;
   const ItemLayout L = item_layout(c, R.t, R.icap[cur]);
   if(R.used[cur]) HIP_TRY(hipEventSynchronize(R.consumed[cur]));          // recv[cur] was read by the insert of step - 2
-  int rc = comm_reserve(R.recv[cur], R.recv_cap[cur], (L.recv_bytes + 7) / 8, R.t->stream, c->xstream); if(rc) return rc;
-  if(!R.used[cur ^ 1]) { rc = comm_reserve(R.recv[cur ^ 1], R.recv_cap[cur ^ 1], (L.recv_bytes + 7) / 8, R.t->stream, c->xstream); if(rc) return rc; }
+  int rc = comm_reserve(R.recv[cur], (L.recv_bytes + 7) / 8, R.t->stream, c->xstream); if(rc) return rc;
+  if(!R.used[cur ^ 1]) { rc = comm_reserve(R.recv[cur ^ 1], (L.recv_bytes + 7) / 8, R.t->stream, c->xstream); if(rc) return rc; }
   HIP_TRY(hipEventRecord(R.routed[cur], R.t->stream));
   HIP_TRY(hipStreamWaitEvent(c->xstream, R.routed[cur], 0));
   comm_x_begin(c, R, cur);
-  uint8_t* sb = reinterpret_cast<uint8_t*>(R.send[cur]);
-  uint8_t* rb = reinterpret_cast<uint8_t*>(R.recv[cur]);
-  const size_t blk = (size_t)L.nbc * L.cap;                               // items per (sender, receiver) message
+  const uint64_t* sb = R.send[cur];
+  uint64_t* rb = R.recv[cur];
+  const size_t blk = L.blk();
   const int skip = c->self_rccl ? -1 : c->rank;
-  auto s_items = [&](int p) { return reinterpret_cast<uint32_t*>(sb) + (size_t)p * blk; };
-  auto r_items = [&](int p) { return reinterpret_cast<uint32_t*>(rb) + (size_t)p * blk; };
-  auto s_offs = [&](int p) { return reinterpret_cast<uint64_t*>(sb + L.offs_at) + (size_t)p * 2 * L.nbc; };
-  auto r_offs = [&](int p) { return reinterpret_cast<uint64_t*>(rb + L.r_offs_at) + (size_t)p * 2 * L.nbc; };
-  uint64_t* s_claims = reinterpret_cast<uint64_t*>(sb + L.claims_at);
-  uint64_t* r_claims = reinterpret_cast<uint64_t*>(rb + L.r_claims_at);
-  uint64_t* s_strag = reinterpret_cast<uint64_t*>(sb + L.strag_at);
-  auto r_strag = [&](int p) { return reinterpret_cast<uint64_t*>(rb + L.r_strag_at) + (size_t)p * (1 + L.S); };
   R.self_items[cur] = nullptr;
   if(skip >= 0) {
-    const int p = c->rank;
     // The rank's own share does not move: the split reads it from the send buffer (stream order keeps it there: the next
     // routing into send[cur] is enqueued behind that split, on the table's stream).  At world 8 an eighth of the items, on
     // one GPU all of them (a 3.5 GB copy per step that ran beside the next step's routing kernel and slowed it).
-    R.self_items[cur] = reinterpret_cast<const uint32_t*>(sb);
-    HIP_TRY(hipMemcpyAsync(r_offs(p), s_offs(p), (size_t)2 * L.nbc * 8, hipMemcpyDeviceToDevice, c->xstream));
-    HIP_TRY(hipMemcpyAsync(r_claims + p, s_claims + p, 8, hipMemcpyDeviceToDevice, c->xstream));
-    HIP_TRY(hipMemcpyAsync(r_strag(p), s_strag, (size_t)(1 + L.S) * 8, hipMemcpyDeviceToDevice, c->xstream));
+    R.self_items[cur] = L.items(sb, 0);
+    rc = comm_copy_share(c, L, rb, c->rank, sb, c->rank, false); if(rc) return rc;
   }
   if(W > 1 || c->self_rccl) {
     // the regions in rounds of at most max_msg_keys * 8 bytes per peer (sizes are the same everywhere: nothing to agree on)
@@ -680,27 +664,27 @@ int comm_exchange_items_rccl(jfgpu_comm* c) {
       for(int p = 0; p < W; ++p) {
         if(p == skip) continue;
         const size_t len = std::min(per, blk - lo);
-        NCCL_TRY(ncclSend(s_items(p) + lo, len, ncclUint32, p, c->nccl, c->xstream));
-        NCCL_TRY(ncclRecv(r_items(p) + lo, len, ncclUint32, p, c->nccl, c->xstream));
+        NCCL_TRY(ncclSend(L.items(sb, p) + lo, len, ncclUint32, p, c->nccl, c->xstream));
+        NCCL_TRY(ncclRecv(L.items(rb, p) + lo, len, ncclUint32, p, c->nccl, c->xstream));
       }
       NCCL_TRY(ncclGroupEnd());
     }
     NCCL_TRY(ncclGroupStart());
     for(int p = 0; p < W; ++p) {
       if(p == skip) continue;
-      NCCL_TRY(ncclSend(s_items(p), std::min(per, blk), ncclUint32, p, c->nccl, c->xstream));
-      NCCL_TRY(ncclRecv(r_items(p), std::min(per, blk), ncclUint32, p, c->nccl, c->xstream));
-      NCCL_TRY(ncclSend(s_offs(p), (size_t)2 * L.nbc, ncclUint64, p, c->nccl, c->xstream));
-      NCCL_TRY(ncclRecv(r_offs(p), (size_t)2 * L.nbc, ncclUint64, p, c->nccl, c->xstream));
-      NCCL_TRY(ncclSend(s_claims + p, 1, ncclUint64, p, c->nccl, c->xstream));
-      NCCL_TRY(ncclRecv(r_claims + p, 1, ncclUint64, p, c->nccl, c->xstream));
-      NCCL_TRY(ncclSend(s_strag, (size_t)(1 + L.S), ncclUint64, p, c->nccl, c->xstream));
-      NCCL_TRY(ncclRecv(r_strag(p), (size_t)(1 + L.S), ncclUint64, p, c->nccl, c->xstream));
+      NCCL_TRY(ncclSend(L.items(sb, p), std::min(per, blk), ncclUint32, p, c->nccl, c->xstream));
+      NCCL_TRY(ncclRecv(L.items(rb, p), std::min(per, blk), ncclUint32, p, c->nccl, c->xstream));
+      NCCL_TRY(ncclSend(L.offs(sb, p), L.offs_n(), ncclUint64, p, c->nccl, c->xstream));
+      NCCL_TRY(ncclRecv(L.offs(rb, p), L.offs_n(), ncclUint64, p, c->nccl, c->xstream));
+      NCCL_TRY(ncclSend(L.claims(sb, p), 1, ncclUint64, p, c->nccl, c->xstream));
+      NCCL_TRY(ncclRecv(L.claims(rb, p), 1, ncclUint64, p, c->nccl, c->xstream));
+      NCCL_TRY(ncclSend(L.send_strag(sb), L.strag_n(), ncclUint64, p, c->nccl, c->xstream));
+      NCCL_TRY(ncclRecv(L.recv_strag(rb, p), L.strag_n(), ncclUint64, p, c->nccl, c->xstream));
     }
     NCCL_TRY(ncclGroupEnd());
   }
   { const int peers = (W > 1 || c->self_rccl) ? W - (skip >= 0 ? 1 : 0) : 0;
-    comm_x_end(c, R, cur, (uint64_t)peers * (blk * 4 + (uint64_t)2 * L.nbc * 8 + 8 + (uint64_t)(1 + L.S) * 8)); }
+    comm_x_end(c, R, cur, (uint64_t)peers * (blk * 4 + (uint64_t)L.offs_n() * 8 + 8 + (uint64_t)L.strag_n() * 8)); }
   HIP_TRY(hipEventRecord(R.exchanged[cur], c->xstream));
   R.used[cur] = true;
   return JFGPU_OK;
@@ -714,22 +698,16 @@ int comm_exchange_items_local(jfgpu_comm* c) {
   for(int d = 0; d < W; ++d) {
     jfgpu_comm::Rank& D = c->ranks[d];
     if(D.used[D.turn]) HIP_TRY(hipEventSynchronize(D.consumed[D.turn]));
-    int rc = comm_reserve(D.recv[D.turn], D.recv_cap[D.turn], (L.recv_bytes + 7) / 8, D.t->stream, c->xstream); if(rc) return rc;
+    int rc = comm_reserve(D.recv[D.turn], (L.recv_bytes + 7) / 8, D.t->stream, c->xstream); if(rc) return rc;
   }
   for(int s = 0; s < W; ++s) {
     jfgpu_comm::Rank& S = c->ranks[s];
     HIP_TRY(hipEventRecord(S.routed[S.turn], S.t->stream));
     HIP_TRY(hipStreamWaitEvent(c->xstream, S.routed[S.turn], 0));
   }
-  const size_t blk = (size_t)L.nbc * L.cap;
   for(int s = 0; s < W; ++s)
     for(int d = 0; d < W; ++d) {
-      const uint8_t* sb = reinterpret_cast<const uint8_t*>(c->ranks[s].send[c->ranks[s].turn]);
-      uint8_t* rb = reinterpret_cast<uint8_t*>(c->ranks[d].recv[c->ranks[d].turn]);
-      HIP_TRY(hipMemcpyAsync(rb + (size_t)s * blk * 4, sb + (size_t)d * blk * 4, blk * 4, hipMemcpyDeviceToDevice, c->xstream));
-      HIP_TRY(hipMemcpyAsync(rb + L.r_offs_at + (size_t)s * 2 * L.nbc * 8, sb + L.offs_at + (size_t)d * 2 * L.nbc * 8, (size_t)2 * L.nbc * 8, hipMemcpyDeviceToDevice, c->xstream));
-      HIP_TRY(hipMemcpyAsync(rb + L.r_claims_at + (size_t)s * 8, sb + L.claims_at + (size_t)d * 8, 8, hipMemcpyDeviceToDevice, c->xstream));
-      HIP_TRY(hipMemcpyAsync(rb + L.r_strag_at + (size_t)s * (1 + L.S) * 8, sb + L.strag_at, (size_t)(1 + L.S) * 8, hipMemcpyDeviceToDevice, c->xstream));
+      int rc = comm_copy_share(c, L, c->ranks[d].recv[c->ranks[d].turn].get(), s, c->ranks[s].send[c->ranks[s].turn].get(), d, true); if(rc) return rc;
     }
   for(int d = 0; d < W; ++d) {
     jfgpu_comm::Rank& D = c->ranks[d];
@@ -739,233 +717,15 @@ int comm_exchange_items_local(jfgpu_comm* c) {
   return JFGPU_OK;
 }
 
-
-#if !defined(JFGPU_EMU)
-// ---- the "ipc" transport -----------------------------------------------------------------------------------------
-constexpr int kIpcMaxWorld = 16;
-struct IpcShared {
-  std::atomic<uint32_t> arrived, generation, failed, attached;
-  uint64_t coll[kIpcMaxWorld][64];                          // a rank's contribution to the running collective
-  struct Pub {
-    hipIpcMemHandle_t send[2]; uint64_t send_epoch[2];      // send buffers of both turns (epoch changes when one is re-allocated)
-    uint64_t scount[kIpcMaxWorld], soff[kIpcMaxWorld + 1];  // key path: what this rank holds for every owner, and where
-  } pub[kIpcMaxWorld];
-};
-
-int ipc_fail(jfgpu_comm* c, const char* what) {
-  if(c->shm) c->shm->failed.store(1);
-  return fail(JFGPU_E_HIP, std::string("ipc transport: ") + what);
+// The exchange of the current step (every rank's send[turn] into the owners' recv[turn]) on the communicator's transport:
+// the one way in, for the count steps, comm_grow and comm_bc_merge.  items: an item-path step (fixed regions), else keys.
+int comm_exchange(jfgpu_comm* c, bool items) {
+  if(c->local) return items ? comm_exchange_items_local(c) : comm_exchange_local(c);
+  if(c->ipc) return items ? comm_exchange_items_ipc(c) : comm_exchange_ipc(c);
+  return items ? comm_exchange_items_rccl(c) : comm_exchange_rccl(c);
 }
 
-// Sense-reversing barrier over the shared block; gives up when a rank reported a failure or nobody moves for 10 minutes.
-int ipc_barrier(jfgpu_comm* c) {
-  IpcShared* S = c->shm;
-  const uint32_t gen = S->generation.load();
-  if(S->arrived.fetch_add(1) + 1 == (uint32_t)c->world) { S->arrived.store(0); S->generation.fetch_add(1); return JFGPU_OK; }
-  const auto t0 = std::chrono::steady_clock::now();
-  for(uint64_t spins = 0; S->generation.load() == gen; ++spins) {
-    if(S->failed.load()) return fail(JFGPU_E_HIP, "ipc transport: another rank failed");
-    if(spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(50)); else std::this_thread::yield();
-    if((spins & 0xFFFF) == 0xFFFF && std::chrono::steady_clock::now() - t0 > std::chrono::minutes(10)) return ipc_fail(c, "barrier timed out");
-  }
-  return JFGPU_OK;
-}
-
-// (Re-)publish this rank's send buffer of turn `cur` if it was re-allocated since.
-int ipc_publish_send(jfgpu_comm* c, int cur) {
-  jfgpu_comm::Rank& R = c->ranks[0];
-  IpcShared::Pub& P = c->shm->pub[c->rank];
-  // (pointer AND capacity: comm_reserve frees and allocates, and the allocator likes to hand the same address back for the
-  //  larger buffer -- peers would go on copying through their mapping of the freed one.  Round-3 advisor finding.)
-  if(R.send[cur] && (c->send_exported[cur] != (void*)R.send[cur] || c->send_exported_cap[cur] != R.send_cap[cur])) {
-    if(hipIpcGetMemHandle(&P.send[cur], R.send[cur]) != hipSuccess) return ipc_fail(c, "hipIpcGetMemHandle");
-    c->send_exported[cur] = R.send[cur]; c->send_exported_cap[cur] = R.send_cap[cur];
-    P.send_epoch[cur] = ++c->send_epoch[cur];
-  }
-  return JFGPU_OK;
-}
-
-// Peer p's send buffer of turn `cur`, mapped into this process.
-int ipc_peer_send(jfgpu_comm* c, int p, int cur, uint8_t** out) {
-  jfgpu_comm::PeerMap& M = c->peer_send[cur][p];
-  const IpcShared::Pub& P = c->shm->pub[p];
-  if(M.epoch != P.send_epoch[cur]) {
-    if(M.ptr) { if(c->tun.comm_ipc_keep) c->stale_maps.push_back(M.ptr); else hipIpcCloseMemHandle(M.ptr); M.ptr = nullptr; }
-    if(hipIpcOpenMemHandle(&M.ptr, P.send[cur], hipIpcMemLazyEnablePeerAccess) != hipSuccess) return ipc_fail(c, "hipIpcOpenMemHandle");
-    M.epoch = P.send_epoch[cur];
-  }
-  *out = reinterpret_cast<uint8_t*>(M.ptr);
-  return JFGPU_OK;
-}
-
-// Map every peer's send buffer of turn `cur` (only those re-allocated since they were last mapped), ONE RANK AT A TIME.
-// Two processes importing each other's allocations at the same moment stalled in hipIpcOpenMemHandle for good with
-// buffers of 2.6 GB and more (1.8 GB: fine; one process importing while the other idles: fine at any size,
-// tools/probes/r03_ipc_size_probe.hip) -- so the imports take turns, with nothing of this exchange in flight yet.
-int ipc_open_peers(jfgpu_comm* c, int cur) {
-  for(int turn = 0; turn < c->world; ++turn) {
-    int rc = JFGPU_OK;
-    if(turn == c->rank)
-      for(int p = 0; p < c->world && rc == JFGPU_OK; ++p) { uint8_t* unused; if(p != c->rank) rc = ipc_peer_send(c, p, cur, &unused); }
-    if(rc) return rc;
-    rc = ipc_barrier(c); if(rc) return rc;
-  }
-  return JFGPU_OK;
-}
-
-// Key path: every rank publishes its per-owner counts and offsets, then PULLS what is meant for it out of the peers'
-// send buffers into its own receive buffer.
-int comm_exchange_ipc(jfgpu_comm* c) {
-  jfgpu_comm::Rank& R = c->ranks[0];
-  const int cur = R.turn, W = c->world;
-  IPC_TRACE(c, "keys: waiting for the routing kernels (turn %d)", cur);
-  HIP_TRY(hipStreamSynchronize(R.t->stream));                // the routed keys are in send[cur]
-  int rc = ipc_publish_send(c, cur); if(rc) return rc;
-  IPC_TRACE(c, "keys: published, barrier 1");
-  IpcShared::Pub& mine = c->shm->pub[c->rank];
-  for(int p = 0; p < W; ++p) { mine.scount[p] = R.scount[cur][p]; mine.soff[p] = R.soff[cur][p]; }
-  rc = ipc_barrier(c); if(rc) return rc;
-  rc = ipc_open_peers(c, cur); if(rc) return rc;
-  uint64_t total = 0;
-  for(int p = 0; p < W; ++p) { R.rcount[cur][p] = c->shm->pub[p].scount[c->rank]; R.roff[cur][p] = total; total += R.rcount[cur][p]; }
-  R.roff[cur][W] = total;
-  if(R.used[cur]) HIP_TRY(hipEventSynchronize(R.consumed[cur]));
-  rc = comm_reserve(R.recv[cur], R.recv_cap[cur], total, R.t->stream, c->xstream); if(rc) return rc;
-  for(int p = 0; p < W; ++p) {
-    if(!R.rcount[cur][p]) continue;
-    uint8_t* src = reinterpret_cast<uint8_t*>(R.send[cur]);
-    if(p != c->rank) { rc = ipc_peer_send(c, p, cur, &src); if(rc) return rc; }
-    HIP_TRY(hipMemcpyAsync(R.recv[cur] + R.roff[cur][p], src + c->shm->pub[p].soff[c->rank] * 8, R.rcount[cur][p] * 8, hipMemcpyDeviceToDevice, c->xstream));
-  }
-  HIP_TRY(hipEventRecord(R.exchanged[cur], c->xstream));
-  IPC_TRACE(c, "keys: copies enqueued, waiting for them");
-  HIP_TRY(hipStreamSynchronize(c->xstream));
-  IPC_TRACE(c, "keys: pulled, barrier 2");
-  rc = ipc_barrier(c); if(rc) return rc;                     // everybody has pulled: the send buffers may be written again
-  IPC_TRACE(c, "keys: step exchanged");
-  comm_free_retired(c, cur);                                 // (every peer has re-imported send[cur]: nobody maps the old ones)
-  R.used[cur] = true;
-  return JFGPU_OK;
-}
-
-// Item path: fixed layout, nothing to publish but the buffers.
-int comm_exchange_items_ipc(jfgpu_comm* c) {
-  jfgpu_comm::Rank& R = c->ranks[0];
-  const int cur = R.turn, W = c->world, me = c->rank;
-  const ItemLayout L = item_layout(c, R.t, R.icap[cur]);
-  IPC_TRACE(c, "items: waiting for the routing kernels (turn %d, cap %u)", cur, R.icap[cur]);
-  HIP_TRY(hipStreamSynchronize(R.t->stream));
-  int rc = ipc_publish_send(c, cur); if(rc) return rc;
-  IPC_TRACE(c, "items: published; waiting for recv[%d] to be consumed", cur);
-  if(R.used[cur]) HIP_TRY(hipEventSynchronize(R.consumed[cur]));
-  rc = comm_reserve(R.recv[cur], R.recv_cap[cur], (L.recv_bytes + 7) / 8, R.t->stream, c->xstream); if(rc) return rc;
-  IPC_TRACE(c, "items: recv buffer of %zu bytes ready, barrier 1", L.recv_bytes);
-  rc = ipc_barrier(c); if(rc) return rc;
-  rc = ipc_open_peers(c, cur); if(rc) return rc;
-  IPC_TRACE(c, "items: peers' send buffers mapped");
-  uint8_t* rb = reinterpret_cast<uint8_t*>(R.recv[cur]);
-  const size_t blk = (size_t)L.nbc * L.cap;
-  for(int p = 0; p < W; ++p) {                               // sender p's share for me
-    uint8_t* sb = reinterpret_cast<uint8_t*>(R.send[cur]);
-    if(p != me) { rc = ipc_peer_send(c, p, cur, &sb); if(rc) return rc; }
-    IPC_TRACE(c, "items: rank %d's send buffer is at %p here", p, (void*)sb);
-    HIP_TRY(hipMemcpyAsync(rb + (size_t)p * blk * 4, sb + (size_t)me * blk * 4, blk * 4, hipMemcpyDeviceToDevice, c->xstream));
-    IPC_TRACE(c, "items: regions copy enqueued (%zu bytes)", blk * 4);
-    HIP_TRY(hipMemcpyAsync(rb + L.r_offs_at + (size_t)p * 2 * L.nbc * 8, sb + L.offs_at + (size_t)me * 2 * L.nbc * 8, (size_t)2 * L.nbc * 8, hipMemcpyDeviceToDevice, c->xstream));
-    IPC_TRACE(c, "items: offsets copy enqueued");
-    HIP_TRY(hipMemcpyAsync(rb + L.r_claims_at + (size_t)p * 8, sb + L.claims_at + (size_t)me * 8, 8, hipMemcpyDeviceToDevice, c->xstream));
-    IPC_TRACE(c, "items: claims copy enqueued");
-    HIP_TRY(hipMemcpyAsync(rb + L.r_strag_at + (size_t)p * (1 + L.S) * 8, sb + L.strag_at, (size_t)(1 + L.S) * 8, hipMemcpyDeviceToDevice, c->xstream));
-    IPC_TRACE(c, "items: straggler list copy enqueued");
-  }
-  HIP_TRY(hipEventRecord(R.exchanged[cur], c->xstream));
-  IPC_TRACE(c, "items: copies enqueued, waiting for them");
-  HIP_TRY(hipStreamSynchronize(c->xstream));
-  IPC_TRACE(c, "items: pulled, barrier 2");
-  rc = ipc_barrier(c); if(rc) return rc;
-  IPC_TRACE(c, "items: step exchanged");
-  comm_free_retired(c, cur);
-  R.used[cur] = true;
-  return JFGPU_OK;
-}
-
-int ipc_collective(jfgpu_comm* c, uint64_t* values, int n, int op /* 0 sum, 1 max, 2 gather of values[0] into values[0..world) */) {
-  IpcShared* S = c->shm;
-  for(int i = 0; i < (op == 2 ? 1 : n); ++i) S->coll[c->rank][i] = values[i];
-  int rc = ipc_barrier(c); if(rc) return rc;
-  if(op == 2) { for(int p = 0; p < c->world; ++p) values[p] = S->coll[p][0]; }
-  else for(int i = 0; i < n; ++i) {
-    uint64_t v = op == 0 ? 0 : S->coll[0][i];
-    for(int p = 0; p < c->world; ++p) v = op == 0 ? v + S->coll[p][i] : std::max(v, S->coll[p][i]);
-    values[i] = v;
-  }
-  return ipc_barrier(c);                                     // (the slots are free again)
-}
-
-int ipc_attach(jfgpu_comm* c, const uint8_t* id128) {
-  if(c->world > kIpcMaxWorld) return fail(JFGPU_E_INVALID, "ipc transport: at most 16 ranks");
-  c->shm_name.assign(reinterpret_cast<const char*>(id128) + 8);
-  const int fd = shm_open(c->shm_name.c_str(), O_CREAT | O_RDWR, 0600);       // created zero-filled by whoever comes first
-  if(fd < 0) return fail(JFGPU_E_HIP, "ipc transport: shm_open failed");
-  if(ftruncate(fd, sizeof(IpcShared)) != 0) { close(fd); return fail(JFGPU_E_HIP, "ipc transport: ftruncate failed"); }
-  void* m = mmap(nullptr, sizeof(IpcShared), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-  close(fd);
-  if(m == MAP_FAILED) return fail(JFGPU_E_HIP, "ipc transport: mmap failed");
-  c->shm = reinterpret_cast<IpcShared*>(m);
-  c->ipc = true;
-  for(int i = 0; i < 2; ++i) c->peer_send[i].assign(c->world, jfgpu_comm::PeerMap());
-  c->shm->attached.fetch_add(1);
-  return ipc_barrier(c);                                     // everybody is here
-}
-
-void ipc_detach(jfgpu_comm* c) {
-  if(!c->shm) return;
-  for(int i = 0; i < 2; ++i) for(auto& M : c->peer_send[i]) if(M.ptr) hipIpcCloseMemHandle(M.ptr);
-  for(void* p : c->stale_maps) hipIpcCloseMemHandle(p);
-  c->stale_maps.clear();
-  const bool last = c->shm->attached.fetch_sub(1) == 1;
-  munmap(c->shm, sizeof(IpcShared));
-  if(last) shm_unlink(c->shm_name.c_str());
-  c->shm = nullptr;
-}
-#else
-int comm_exchange_ipc(jfgpu_comm*) { return fail(JFGPU_E_UNSUPPORTED, "no inter-process transport in the emulated build"); }
-int comm_exchange_items_ipc(jfgpu_comm*) { return fail(JFGPU_E_UNSUPPORTED, "no inter-process transport in the emulated build"); }
-#endif
-
-// ---- the shards of a table grow together -------------------------------------------------------------------------------
-// hash_counter::double_size (hash_counter.hpp:200-238) for a table spread over ranks.  The doubled table has a new matrix
-// (the next one of the reference's random() stream, the same on every rank), so an entry's owner changes: every rank
-// walks its old shard, puts what stays with it into its new shard and sends the rest -- (key, count) pairs, grouped by
-// new owner -- through the key path's exchange, twice (keys, then counts, same grouping).  Every key width (KeyOps): a
-// pair is kw key words (low first) and a count.
-//   pass 0: how many pairs for every owner;  pass 1: the pairs, at the cursors (= offsets), and the local inserts
-template <class Table>
-__global__ __launch_bounds__(kBlock) void reshard_kernel(Table old, Table neu, int have_ovf, int pass, uint32_t kw, unsigned long long* __restrict__ cursors,
-                                                         uint64_t* __restrict__ keys_out, uint64_t* __restrict__ cnts_out) {
-  typedef KeyOps<Table> K;
-  const TableGeom& g = K::geom(old);
-  const uint64_t n = 1ull << g.lsize_l;
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    typename K::Slot s;
-    if(!K::load(old, i, s)) continue;                    // (a claim that was never completed holds no key)
-    const typename K::Key key = K::key(old, s, i & ~g.tile_mask);
-    const uint32_t owner = K::owner(neu, neu.fwd_tbl, key);
-    if(owner == K::geom(neu).shard_id) { if(pass) K::add_val(neu, neu.fwd_tbl, key, K::count(old, s, i, have_ovf)); }
-    else {
-      const unsigned long long at = atomicAdd(&cursors[owner], 1ull);
-      if(pass) { K::store_key(keys_out + (uint64_t)kw * at, key, kw); cnts_out[at] = K::count(old, s, i, have_ovf); }
-    }
-  }
-}
-template <class Table>
-__global__ __launch_bounds__(kBlock) void add_pairs_kernel(Table T, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ cnts, uint64_t n, uint32_t kw) {
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    KeyOps<Table>::add_val(T, T.fwd_tbl, KeyOps<Table>::load_key(T, keys, i, kw, false), cnts[i]);      // (keys as they come: made by store_key or by the caller)
-}
-
-int comm_exchange_rccl(jfgpu_comm* c); int comm_exchange_local(jfgpu_comm* c); int comm_exchange_ipc(jfgpu_comm* c);
-
+// ---- the shards of a table grow together (kernels_comm.hip.hpp: reshard_kernel, add_pairs_kernel) -----------------------
 // Collective (every rank of the communicator; the local transport: all its ranks here).
 int comm_grow(jfgpu_comm* c) {
   const int W = c->world;
@@ -1015,12 +775,13 @@ int comm_grow(jfgpu_comm* c) {
     HIP_TRY(hipStreamSynchronize(c->xstream));
     const int have_ovf = (int)(N[q].ctr[CTR_OVF_USED] != 0);
     const dim3 grid(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), block(kBlock);
-    HIP_TRY(hipMemsetAsync(R.d_cnt, 0, sizeof(unsigned long long) * W, t->stream));
+    unsigned long long* d_cnt = R.d_cnt;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * W, t->stream));
     with_view(t, N[q], [&](const auto& old, const auto& neu) {
-      hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, old, neu, have_ovf, 0, (uint32_t)kw, R.d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
+      hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, old, neu, have_ovf, 0, (uint32_t)kw, d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
     });
     std::vector<unsigned long long> h(W);
-    HIP_TRY(hipMemcpyAsync(h.data(), R.d_cnt, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), d_cnt, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     if(c->tun.comm_trace) {
       uint64_t ms = 0; for(uint64_t col : N[q].m2.columns) ms = ms * 0x9E3779B97F4A7C15ull + col;
@@ -1033,9 +794,10 @@ int comm_grow(jfgpu_comm* c) {
     R.soff[1][W] = total; R.soff[0][W] = total * kw;
     rc = comm_reserve_send(c, R, 0, std::max<uint64_t>(total * kw, 1), t->stream); if(rc) return rc;
     rc = comm_reserve_send(c, R, 1, std::max<uint64_t>(total, 1), t->stream); if(rc) return rc;
-    HIP_TRY(hipMemcpyAsync(R.d_cnt, h.data(), sizeof(unsigned long long) * W, hipMemcpyHostToDevice, t->stream));   // cursors = offsets
+    HIP_TRY(hipMemcpyAsync(d_cnt, h.data(), sizeof(unsigned long long) * W, hipMemcpyHostToDevice, t->stream));   // cursors = offsets
+    uint64_t *keys_out = R.send[0], *cnts_out = R.send[1];
     with_view(t, N[q], [&](const auto& old, const auto& neu) {
-      hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, old, neu, have_ovf, 1, (uint32_t)kw, R.d_cnt, R.send[0], R.send[1]);
+      hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, old, neu, have_ovf, 1, (uint32_t)kw, d_cnt, keys_out, cnts_out);
     });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(t->stream));
@@ -1045,7 +807,7 @@ int comm_grow(jfgpu_comm* c) {
   // keys (turn 0), then counts (turn 1): the key path's exchange, as it is
   for(int turn = 0; turn < 2; ++turn) {
     for(auto& R : c->ranks) R.turn = turn;
-    int rc = c->local ? comm_exchange_local(c) : c->ipc ? comm_exchange_ipc(c) : comm_exchange_rccl(c);
+    int rc = comm_exchange(c, false);
     if(rc) return rc;
   }
   for(size_t q = 0; q < c->ranks.size(); ++q) {
@@ -1070,8 +832,9 @@ int comm_grow(jfgpu_comm* c) {
       }
       IPC_TRACE(c, "grow: shard %u, arrived/not mine per sender:%s", t->g.shard_id, hs.c_str());
     }
+    const uint64_t *keys_in = R.recv[0], *cnts_in = R.recv[1];
     if(n) with_view(t, N[q], [&](const auto&, const auto& neu) {
-      hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, neu, (const uint64_t*)R.recv[0], (const uint64_t*)R.recv[1], n, t->key_words);
+      hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, neu, keys_in, cnts_in, n, t->key_words);
     });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(R.consumed[0], t->stream));
@@ -1084,35 +847,15 @@ int comm_grow(jfgpu_comm* c) {
   return JFGPU_OK;
 }
 
-extern "C" int jfgpu_comm_allreduce_u64(jfgpu_comm* c, uint64_t* values, int n, int op);
-
 // ---- `jellyfish bc` over several GPUs: the ranks' counters merged ----------------------------------------------------------
 // Every rank inserts ITS part of the input into its own Bloom counter (same size, same matrices).  A cell of the counter
 // of the whole input is min(2, sum of the ranks' cells): the increments commute and saturate at 2 (bloom_counter2.hpp:56-107),
 // so the merged array is byte for byte the array one counter fed with everything holds -- what `bc` writes, what
-// `count --bc` asks.  The merge is two rounds of the key path's exchange (comm_exchange_*: an all-to-all of 64-bit words,
+// `count --bc` asks.  The merge is two rounds of the key path's exchange (comm_exchange: an all-to-all of 64-bit words,
 // whatever the transport): the array is cut into W ranges of words; round one sends range p of every rank to rank p, which
-// adds them digit by digit (reduce-scatter); round two sends the merged range to everybody (all-gather).  Every rank ends
-// up with the whole merged counter -- the filtered count over shards wants exactly that (every rank asks before it routes).
-__device__ __forceinline__ uint32_t bloom_byte_add(uint32_t a, uint32_t b) {     // five base-3 digits a byte, digit-wise min(2, a + b)
-  uint32_t r = 0, w = 1;
-#pragma unroll
-  for(int d = 0; d < 5; ++d) { const uint32_t s = a % 3u + b % 3u; r += (s > 2u ? 2u : s) * w; w *= 3u; a /= 3u; b /= 3u; }
-  return r;
-}
-__global__ __launch_bounds__(kBlock) void bloom_merge_kernel(uint64_t* __restrict__ dst, const uint64_t* __restrict__ src, uint64_t n_words) {
-  for(uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t a = dst[i], b = src[i];
-    if(b == 0) continue;
-    uint64_t r = 0;
-#pragma unroll
-    for(int k = 0; k < 8; ++k) r |= (uint64_t)bloom_byte_add((uint32_t)(a >> (8 * k)) & 0xFFu, (uint32_t)(b >> (8 * k)) & 0xFFu) << (8 * k);
-    dst[i] = r;
-  }
-}
-
-int comm_exchange_rccl(jfgpu_comm* c); int comm_exchange_local(jfgpu_comm* c); int comm_exchange_ipc(jfgpu_comm* c);
-
+// adds them digit by digit (reduce-scatter, bloom_merge_kernel); round two sends the merged range to everybody (all-gather).
+// Every rank ends up with the whole merged counter -- the filtered count over shards wants exactly that (every rank asks
+// before it routes).
 // blooms[q]: the counter of local rank q (RCCL / ipc transport: one; local transport: all W).  Collective.
 int comm_bc_merge(jfgpu_comm* c, jfgpu_bloom** blooms) {
   const int W = c->world;
@@ -1139,7 +882,6 @@ int comm_bc_merge(jfgpu_comm* c, jfgpu_bloom** blooms) {
     c->ranks[q].t = shim[q].get();
   }
   auto restore = [&]() { for(size_t q = 0; q < nr; ++q) c->ranks[q].t = saved[q]; };
-  auto exchange = [&]() { return c->local ? comm_exchange_local(c) : c->ipc ? comm_exchange_ipc(c) : comm_exchange_rccl(c); };
   auto rank_of = [&](size_t q) { return c->local ? (int)q : c->rank; };
   // Before every exchange the ranks agree that all of them got this far (round-5 advisor finding: a rank with a local error
   // skipped the exchange and left the others waiting in it): a failure anywhere ends the merge on every rank.
@@ -1160,7 +902,7 @@ int comm_bc_merge(jfgpu_comm* c, jfgpu_bloom** blooms) {
     R.soff[0][W] = words;
   }
   rc = all_fine(); if(rc) { restore(); return rc; }
-  rc = exchange();
+  rc = comm_exchange(c, false);
   for(size_t q = 0; q < nr && !rc; ++q) {
     jfgpu_comm::Rank& R = c->ranks[q]; jfgpu_bloom* b = blooms[q];
     const int me = rank_of(q);
@@ -1181,7 +923,7 @@ int comm_bc_merge(jfgpu_comm* c, jfgpu_bloom** blooms) {
     R.soff[1][W] = n;
   }
   rc = all_fine(); if(rc) { restore(); return rc; }
-  rc = exchange();
+  rc = comm_exchange(c, false);
   unsigned long long mers_sum = 0;
   for(size_t q = 0; q < nr && !rc; ++q) {
     jfgpu_comm::Rank& R = c->ranks[q]; jfgpu_bloom* b = blooms[q];
@@ -1201,28 +943,6 @@ int comm_bc_merge(jfgpu_comm* c, jfgpu_bloom** blooms) {
   for(size_t q = 0; q < nr; ++q) HIP_TRY(hipMemcpy(blooms[q]->d_mers, &mers_sum, sizeof mers_sum, hipMemcpyHostToDevice));
   return JFGPU_OK;
 }
-
-void comm_free_rank(jfgpu_comm::Rank& R) {
-  for(int i = 0; i < 2; ++i) {
-    if(R.send[i]) hipFree(R.send[i]);
-    if(R.recv[i]) hipFree(R.recv[i]);
-    if(R.routed[i]) hipEventDestroy(R.routed[i]);
-    if(R.exchanged[i]) hipEventDestroy(R.exchanged[i]);
-    if(R.consumed[i]) hipEventDestroy(R.consumed[i]);
-    if(R.x_begin[i]) hipEventDestroy(R.x_begin[i]);
-    if(R.x_end[i]) hipEventDestroy(R.x_end[i]);
-  }
-  if(R.d_cnt) hipFree(R.d_cnt);
-  if(R.d_xc) hipFree(R.d_xc);
-  if(R.d_gcur) hipFree(R.d_gcur);
-  if(R.d_claimed) hipFree(R.d_claimed);
-  if(R.d_arrived) hipFree(R.d_arrived);
-  if(R.d_route) hipFree(R.d_route);
-  if(R.h_route) hipHostFree(R.h_route);
-  if(R.route_done) hipEventDestroy(R.route_done);
-}
-
-extern "C" int jfgpu_comm_allreduce_u64(jfgpu_comm* c, uint64_t* values, int n, int op);
 
 // The size question of a step.  The size given at creation is a hint (doc/Readme.md:67-72) for a sharded table too: a
 // shard keeps an upper bound of its occupancy (what it measured last + the largest piece any rank fed in every exchange
@@ -1249,38 +969,37 @@ uint64_t comm_piece_cap(const jfgpu_comm* c, const jfgpu_table* t) {
   return std::max<uint64_t>(budget / (8ull * t->key_words), 2ull * t->g.k);
 }
 
-// One piece of this rank's step through routing, exchange and the insert of the previous piece (cap: the agreed region
-// capacity of the item path, 0: keys).
-int comm_piece_rccl(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_bases, size_t n, uint32_t cap) {
-  jfgpu_table* t = R.t;
-  int rc = ensure_ovf(t, (uint64_t)n * (uint64_t)c->world, 0); if(rc) return rc;      // (what may arrive for this shard: about a world's worth of one rank's input)
-  uint64_t routed = 0;
-  // the routing of this piece is enqueued, then the insert of what arrived for the previous one (it only waits for that
-  // piece's exchange, on the device): the host's look at the routing pass and the agreement below happen beside device work
-  if(cap) { rc = comm_route_items_enqueue(c, R, d_bases, n, cap); if(rc) return rc; }
-  rc = comm_insert_prev(c, R); if(rc) return rc;
+// One piece of a step through routing, exchange and the insert of the previous piece, for the ranks of this process (RCCL
+// and ipc transports: one; local: all): at[q], n[q] are rank q's input.  cap: the agreed region capacity of the item path,
+// 0: keys.  ovf_bound: what may arrive for a shard, the caller's bound.
+int comm_piece(jfgpu_comm* c, const char* const* at, const size_t* n, uint32_t cap, uint64_t ovf_bound) {
+  const size_t nr = c->ranks.size();
+  int rc;
+  for(auto& R : c->ranks) { rc = ensure_ovf(R.t, ovf_bound, 0); if(rc) return rc; }
+  // every routing of this piece is enqueued, then the inserts of what arrived for the previous one (they only wait for that
+  // piece's exchange, on the device): the host's look at the routing passes and the agreement below happen beside device work
+  if(cap) for(size_t q = 0; q < nr; ++q) { rc = comm_route_items_enqueue(c, c->ranks[q], at[q], n[q], cap); if(rc) return rc; }
+  for(auto& R : c->ranks) { rc = comm_insert_prev(c, R); if(rc) return rc; }
   if(cap) {
-    bool overflow = false;
-    rc = comm_route_items_complete(c, R, cap, &overflow, &routed); if(rc) return rc;
-    IPC_TRACE(c, "step: routed %llu items%s", (unsigned long long)routed, overflow ? " (straggler list overflow)" : "");
-    uint64_t o = overflow ? 1 : 0;
-    rc = jfgpu_comm_allreduce_u64(c, &o, 1, 1); if(rc) return rc;
+    std::vector<uint64_t> routed(nr, 0);
+    uint64_t o = 0;
+    for(size_t q = 0; q < nr; ++q) {
+      bool overflow = false;
+      rc = comm_route_items_complete(c, c->ranks[q], cap, &overflow, &routed[q]); if(rc) return rc;
+      IPC_TRACE(c, "step: routed %llu items%s", (unsigned long long)routed[q], overflow ? " (straggler list overflow)" : "");
+      if(overflow) o = 1;
+    }
+    if(!c->local) { rc = jfgpu_comm_allreduce_u64(c, &o, 1, 1); if(rc) return rc; }
     if(o) cap = 0;                                           // somebody has more stragglers than the list holds: this piece goes as keys
+    else for(size_t q = 0; q < nr; ++q) c->ranks[q].sent += routed[q];
   }
-  R.icap[R.turn] = cap;
-  if(cap) { R.sent += routed; rc = c->ipc ? comm_exchange_items_ipc(c) : comm_exchange_items_rccl(c); if(rc) return rc; }
-  else {
-#if !defined(JFGPU_EMU)
-    // (the one-box test transport: importing a peer's send buffer of 10 GB never returned -- bench.py --gpus 2 --steps 4 on one
-    //  device, a 1.26 GB step as keys; 5 GB buffers are fine -- so such a step fails here, loudly and on every rank, instead
-    //  of standing in a barrier for ten minutes)
-    if(c->ipc && (uint64_t)n * t->key_words * 8 > ((uint64_t)6 << 30))
-      return ipc_fail(c, "a step of this size travels as keys in send buffers of more than 6 GiB, which this runtime does not import: feed smaller steps");
-#endif
-    rc = comm_route(c, R, d_bases, n); if(rc) return rc;
-    rc = c->ipc ? comm_exchange_ipc(c) : comm_exchange_rccl(c); if(rc) return rc;
+  for(auto& R : c->ranks) R.icap[R.turn] = cap;
+  if(!cap) {
+    rc = ipc_keys_step_ok(c, (uint64_t)n[0] * c->ranks[0].t->key_words * 8); if(rc) return rc;
+    for(size_t q = 0; q < nr; ++q) { rc = comm_route(c, c->ranks[q], at[q], n[q]); if(rc) return rc; }
   }
-  R.inflight = true; R.turn ^= 1;
+  rc = comm_exchange(c, cap != 0); if(rc) return rc;
+  for(auto& R : c->ranks) { R.inflight = true; R.turn ^= 1; }
   return JFGPU_OK;
 }
 
@@ -1320,17 +1039,18 @@ int jfgpu_comm_create(int world, int rank, const uint8_t* id128, int device, jfg
 #else
   if(device < 0) HIP_TRY(hipGetDevice(&device));
   HIP_TRY(hipSetDevice(device));
-  std::unique_ptr<jfgpu_comm> c(new jfgpu_comm);
+  std::unique_ptr<jfgpu_comm> c(new jfgpu_comm);       // (a return below takes everything made so far with it)
   c->world = world; c->rank = rank; c->device = device; c->local = false;
-  if(!memcmp(id128, "JFGPUIPC", 8)) { int rc = ipc_attach(c.get(), id128); if(rc) return rc; }
+  int rc;
+  if(!memcmp(id128, "JFGPUIPC", 8)) { rc = ipc_attach(c.get(), id128); if(rc) return rc; }
   else {
     ncclUniqueId id;
     memcpy(&id, id128, 128);
-    NCCL_TRY(ncclCommInitRank(&c->nccl, world, id, rank));
+    NCCL_TRY(ncclCommInitRank(&c->nccl.h, world, id, rank));
   }
-  HIP_TRY(hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
+  rc = c->xstream.create(); if(rc) return rc;
   c->ranks.resize(1);
-  int rc = comm_init_rank(c.get(), c->ranks[0]); if(rc) return rc;
+  rc = comm_init_rank(c.get(), c->ranks[0]); if(rc) return rc;
   comm_apply_tuning(c.get());
   if(c->tun.comm_self_rccl >= 0) c->self_rccl = c->tun.comm_self_rccl != 0;
   *out = c.release();
@@ -1344,11 +1064,11 @@ int jfgpu_comm_create_local(int world, int device, jfgpu_comm** out) {
   if(world < 1 || (world & (world - 1)) || world > 256) return fail(JFGPU_E_INVALID, "world size must be a power of two");
   if(device < 0) HIP_TRY(hipGetDevice(&device));
   HIP_TRY(hipSetDevice(device));
-  std::unique_ptr<jfgpu_comm> c(new jfgpu_comm);
+  std::unique_ptr<jfgpu_comm> c(new jfgpu_comm);       // (a return below takes everything made so far with it)
   c->world = world; c->rank = -1; c->device = device; c->local = true;
-  HIP_TRY(hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
+  int rc = c->xstream.create(); if(rc) return rc;
   c->ranks.resize(world);
-  for(auto& R : c->ranks) { int rc = comm_init_rank(c.get(), R); if(rc) return rc; }
+  for(auto& R : c->ranks) { rc = comm_init_rank(c.get(), R); if(rc) return rc; }
   comm_apply_tuning(c.get());
   *out = c.release();
   return JFGPU_OK;
@@ -1357,15 +1077,8 @@ int jfgpu_comm_create_local(int world, int device, jfgpu_comm** out) {
 void jfgpu_comm_destroy(jfgpu_comm* c) {
   if(!c) return;
   hipSetDevice(c->device);
-  if(c->xstream) hipStreamSynchronize(c->xstream);
-  for(auto& R : c->ranks) { if(R.t && R.t->stream) hipStreamSynchronize(R.t->stream); comm_free_rank(R); }
-  if(c->d_coll) hipFree(c->d_coll);
-#if !defined(JFGPU_EMU)
-  if(c->nccl) ncclCommDestroy(c->nccl);
-  ipc_detach(c);
-#endif
-  comm_free_retired(c, 0, true); comm_free_retired(c, 1, true);
-  if(c->xstream) hipStreamDestroy(c->xstream);
+  c->xstream.sync();
+  for(auto& R : c->ranks) if(R.t) R.t->stream.sync();
   delete c;
 }
 
@@ -1379,6 +1092,11 @@ int jfgpu_comm_count_ascii_dev(jfgpu_comm* c, jfgpu_table* t, const char* d_base
   const uint64_t k = t->g.k;
   const uint64_t piece_cap = comm_piece_cap(c, t);          // (keys of three and four words: a step goes in pieces of at most this)
   size_t off = 0;
+  // This loop and the one of jfgpu_comm_local_step are not the same computation, and stay two on purpose:
+  //   - the item path's capacity is asked (items_cap_wanted) for min(left, this rank's OWN head-room) here, before the
+  //     agreement; there for the final piece, after the common head-room, the piece cap and the 2k floor;
+  //   - fed_since is charged comm_charge(min(largest left, max(agreed, 2k))) here, comm_charge(largest piece) there.
+  // Merging them changes what one of the transports does.
   for(bool first = true;; first = false) {
     const size_t left = n - off;
     const bool growing = comm_growing(t);
@@ -1408,7 +1126,8 @@ int jfgpu_comm_count_ascii_dev(jfgpu_comm* c, jfgpu_table* t, const char* d_base
     if(piece < left && piece < 2 * k) piece = (size_t)std::min<uint64_t>(left, 2 * k);      // (a piece holds a window and moves forward)
     const uint32_t cap = v[0] ? 0u : (uint32_t)v[1];
     IPC_TRACE(c, "step: piece of %zu bytes, agreed cap %u (0: keys)", piece, cap);
-    rc = comm_piece_rccl(c, R, d_bases + off, piece, cap); if(rc) return rc;
+    const char* at = d_bases + off;
+    rc = comm_piece(c, &at, &piece, cap, (uint64_t)piece * (uint64_t)c->world); if(rc) return rc;      // (what may arrive for this shard: about a world's worth of one rank's input)
     if(growing) t->fed_since += comm_charge(std::min<uint64_t>(v[2], std::max<uint64_t>(agreed, 2 * k)));
     if(off + piece >= n) off = n; else off += piece - (size_t)(k - 1);      // the next piece re-reads the last k-1 characters: every window exactly once
     if(!growing && !piece_cap) break;                        // (no pieces without growth or a cap: the step is one exchange, as the caller counts them)
@@ -1433,8 +1152,13 @@ int jfgpu_comm_local_step(jfgpu_comm* c, jfgpu_table** tables, const char* const
   const uint64_t piece_cap = comm_piece_cap(c, tables[0]);    // (the cut of jfgpu_comm_count_ascii_dev)
   std::vector<size_t> off(W, 0), piece(W, 0);
   std::vector<const char*> at(W);
+  // The agreement of jfgpu_comm_count_ascii_dev, with every rank in this process -- but not the same computation, and the
+  // two loops stay two on purpose:
+  //   - the item path's capacity is asked (items_cap_wanted) for the final piece here, after the common head-room, the
+  //     piece cap and the 2k floor; there for min(left, the rank's OWN head-room), before the agreement;
+  //   - fed_since is charged comm_charge(largest piece) here, comm_charge(min(largest left, max(agreed, 2k))) there.
+  // Merging them changes what one of the transports does.
   for(bool first = true;; first = false) {
-    // the agreement of jfgpu_comm_count_ascii_dev, with every rank in this process
     uint64_t max_left = 0, head = ~0ull >> 1; bool bound_out = false;
     for(int r = 0; r < W; ++r) {
       const uint64_t left = n[r] - off[r];
@@ -1458,6 +1182,7 @@ int jfgpu_comm_local_step(jfgpu_comm* c, jfgpu_table** tables, const char* const
       continue;
     }
     uint32_t cap = 0xFFFFFFFFu, want_max = 0;
+    uint64_t all = 0, max_piece = 0;
     for(int r = 0; r < W; ++r) {
       const uint64_t left = n[r] - off[r];
       piece[r] = (size_t)std::min<uint64_t>(left, piece_cap ? std::min<uint64_t>(head, piece_cap) : head);
@@ -1466,37 +1191,11 @@ int jfgpu_comm_local_step(jfgpu_comm* c, jfgpu_table** tables, const char* const
       const uint32_t w = items_cap_wanted(c, c->ranks[r], piece[r]);
       if(!items_geometry_ok(c, tables[r]) || (!w && piece[r] >= k)) cap = 0;      // (a rank without input has no preference)
       want_max = std::max(want_max, w);
+      all += piece[r]; max_piece = std::max<uint64_t>(max_piece, piece[r]);
     }
     if(cap) cap = want_max;                                // (0 when nobody has input: the key path with nothing to send)
-    for(int r = 0; r < W; ++r) { uint64_t all = 0; for(int q = 0; q < W; ++q) all += piece[q]; int rc = ensure_ovf(tables[r], all, 0); if(rc) return rc; }
-    // (same order as the RCCL piece: routing enqueued, the previous piece's insert enqueued, then the host's look at the routing)
-    if(cap) for(int r = 0; r < W; ++r) { int rc = comm_route_items_enqueue(c, c->ranks[r], at[r], piece[r], cap); if(rc) return rc; }
-    for(int r = 0; r < W; ++r) { int rc = comm_insert_prev(c, c->ranks[r]); if(rc) return rc; }
-    if(cap) {
-      bool any_overflow = false;
-      std::vector<uint64_t> routed(W, 0);
-      for(int r = 0; r < W; ++r) {
-        bool overflow = false;
-        int rc = comm_route_items_complete(c, c->ranks[r], cap, &overflow, &routed[r]); if(rc) return rc;
-        any_overflow = any_overflow || overflow;
-      }
-      if(any_overflow) cap = 0;
-      else for(int r = 0; r < W; ++r) c->ranks[r].sent += routed[r];
-    }
-    for(int r = 0; r < W; ++r) c->ranks[r].icap[c->ranks[r].turn] = cap;
-    int rc = JFGPU_OK;
-    if(cap) rc = comm_exchange_items_local(c);
-    else {
-      for(int r = 0; r < W; ++r) { rc = comm_route(c, c->ranks[r], at[r], piece[r]); if(rc) return rc; }
-      rc = comm_exchange_local(c);
-    }
-    if(rc) return rc;
-    uint64_t max_piece = 0;
-    for(int r = 0; r < W; ++r) {
-      c->ranks[r].inflight = true; c->ranks[r].turn ^= 1;
-      max_piece = std::max<uint64_t>(max_piece, piece[r]);
-      if(off[r] + piece[r] >= n[r]) off[r] = n[r]; else off[r] += piece[r] - (size_t)(k - 1);
-    }
+    int rc = comm_piece(c, at.data(), piece.data(), cap, all); if(rc) return rc;      // (what may arrive for a shard: all the pieces)
+    for(int r = 0; r < W; ++r) { if(off[r] + piece[r] >= n[r]) off[r] = n[r]; else off[r] += piece[r] - (size_t)(k - 1); }
     if(growing) for(int r = 0; r < W; ++r) tables[r]->fed_since += comm_charge(max_piece);
     if(!growing && !piece_cap) break;
   }
@@ -1516,7 +1215,7 @@ int jfgpu_comm_allreduce_u64(jfgpu_comm* c, uint64_t* values, int n, int op) {
   HIP_TRY(hipSetDevice(c->device));
   if(c->ipc) return ipc_collective(c, values, n, op);
   if(c->world == 1 && !c->self_rccl) return JFGPU_OK;
-  if(!c->d_coll) HIP_TRY(hipMalloc((void**)&c->d_coll, sizeof(uint64_t) * 512));
+  if(!c->d_coll) { int rc = c->d_coll.alloc(512); if(rc) return rc; }
   HIP_TRY(hipMemcpyAsync(c->d_coll, values, sizeof(uint64_t) * n, hipMemcpyHostToDevice, c->xstream));
   NCCL_TRY(ncclAllReduce(c->d_coll, c->d_coll, n, ncclUint64, op == 0 ? ncclSum : ncclMax, c->nccl, c->xstream));
   HIP_TRY(hipMemcpyAsync(values, c->d_coll, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, c->xstream));
@@ -1536,7 +1235,7 @@ int jfgpu_comm_allgather_u64(jfgpu_comm* c, uint64_t mine, uint64_t* all) {
   if(c->ipc) { all[0] = mine; return ipc_collective(c, all, 1, 2); }
   if(c->world == 1 && !c->self_rccl) { all[0] = mine; return JFGPU_OK; }
   if(c->world > 256) return fail(JFGPU_E_INVALID, "allgather: world too large");
-  if(!c->d_coll) HIP_TRY(hipMalloc((void**)&c->d_coll, sizeof(uint64_t) * 512));
+  if(!c->d_coll) { int rc = c->d_coll.alloc(512); if(rc) return rc; }
   HIP_TRY(hipMemcpyAsync(c->d_coll + 256, &mine, sizeof(uint64_t), hipMemcpyHostToDevice, c->xstream));
   NCCL_TRY(ncclAllGather(c->d_coll + 256, c->d_coll, 1, ncclUint64, c->nccl, c->xstream));
   HIP_TRY(hipMemcpyAsync(all, c->d_coll, sizeof(uint64_t) * c->world, hipMemcpyDeviceToHost, c->xstream));
@@ -1591,41 +1290,6 @@ int jfgpu_comm_finish(jfgpu_comm* c, uint64_t* sent, uint64_t* received) {
   if(sent) *sent = s;
   if(received) *received = r;
   return JFGPU_OK;
-}
-
-// hash_counter::add(key, val) for a batch with one value per key (large_hash_array.hpp:741-752 add_val with an arbitrary
-// increment): what loads a binary/sorted file back into a table -- `query -s` answers from the device that way
-// (sub_commands/query_main.cc:44-51).  Host arrays, staged; the growth / spill rules of jfgpu_add_keys.
-int jfgpu_add_key_vals(jfgpu_table* t, const uint64_t* keys, const uint64_t* vals, size_t n) {
-  int rc = use(t); if(rc) return rc;
-  if(!n) return JFGPU_OK;
-  if(!keys || !vals) return fail(JFGPU_E_INVALID, "null argument");
-  if(t->g.shard_bits) return fail(JFGPU_E_UNSUPPORTED, "add_key_vals: not for a shard (route the keys first)");
-  const size_t kw = t->key_words;
-  DevBuf<uint64_t> d_k, d_v;
-  rc = d_k.alloc(n * kw); if(rc) return rc;
-  if(!d_v.try_alloc(n)) return fail(JFGPU_E_ALLOC, "hipMalloc values");
-  auto done = [&](int r) { hipStreamSynchronize(t->stream); return r; };
-  if(hipMemcpyAsync(d_k, keys, n * kw * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream) != hipSuccess ||
-     hipMemcpyAsync(d_v, vals, n * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream) != hipSuccess) return done(fail(JFGPU_E_HIP, "add_key_vals: copy"));
-  size_t off = 0;
-  while(off < n) {
-    uint64_t take = n - off;
-    if(capacity_managed(t)) { rc = ensure_capacity(t, n - off, &take); if(rc) return done(rc); }
-    uint64_t small = 0, big = 0;                              // what the overflow side table has to be ready for (ensure_ovf's two bounds)
-    for(size_t i = off; i < off + take; ++i) { if(t->g.cnt_bits < 64 && (vals[i] >> t->g.cnt_bits)) ++big; else small += vals[i]; }
-    rc = ensure_ovf(t, small, big); if(rc) return done(rc);
-    rc = part_flush(t); if(rc) return done(rc);
-    t->pristine = false;
-    const dim3 grid(grid_for(t, take / kBlock + 1)), block(kBlock);
-    with_view(t, [&](const auto& T) {
-      hipLaunchKernelGGL(add_pairs_kernel, grid, block, 0, t->stream, T, (const uint64_t*)(d_k + off * kw), (const uint64_t*)(d_v + off), (uint64_t)take, t->key_words);
-    });
-    if(hipGetLastError() != hipSuccess) return done(fail(JFGPU_E_HIP, "add_key_vals: launch"));
-    off += (size_t)take;
-  }
-  rc = done(JFGPU_OK);
-  return rc ? rc : check_deferred(t);
 }
 
 int jfgpu_comm_exchange_times(jfgpu_comm* c, double* ms, uint64_t* wire_bytes, size_t cap, size_t* n) {

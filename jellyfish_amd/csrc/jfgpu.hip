@@ -14,6 +14,7 @@
 #include <array>
 #include <chrono>
 #include <memory>
+#include <numeric>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -35,6 +36,7 @@
 #include "kernels_stream.hip.hpp"
 #include "kernels_merge.hip.hpp"
 #include "kernels_text.hip.hpp"
+#include "kernels_comm.hip.hpp"
 
 using namespace jfgpu;
 
@@ -1057,6 +1059,41 @@ int jfgpu_add_keys(jfgpu_table* t, const uint64_t* keys, size_t n, uint64_t val,
   if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
   if(rc) return rc;
   return check_deferred(t);
+}
+
+// hash_counter::add(key, val) for a batch with one value per key (large_hash_array.hpp:741-752 add_val with an arbitrary
+// increment): what loads a binary/sorted file back into a table -- `query -s` answers from the device that way
+// (sub_commands/query_main.cc:44-51).  Host arrays, staged; the growth / spill rules of jfgpu_add_keys.
+int jfgpu_add_key_vals(jfgpu_table* t, const uint64_t* keys, const uint64_t* vals, size_t n) {
+  int rc = use(t); if(rc) return rc;
+  if(!n) return JFGPU_OK;
+  if(!keys || !vals) return fail(JFGPU_E_INVALID, "null argument");
+  if(t->g.shard_bits) return fail(JFGPU_E_UNSUPPORTED, "add_key_vals: not for a shard (route the keys first)");
+  const size_t kw = t->key_words;
+  DevBuf<uint64_t> d_k, d_v;
+  rc = d_k.alloc(n * kw); if(rc) return rc;
+  if(!d_v.try_alloc(n)) return fail(JFGPU_E_ALLOC, "hipMalloc values");
+  auto done = [&](int r) { hipStreamSynchronize(t->stream); return r; };
+  if(hipMemcpyAsync(d_k, keys, n * kw * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream) != hipSuccess ||
+     hipMemcpyAsync(d_v, vals, n * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream) != hipSuccess) return done(fail(JFGPU_E_HIP, "add_key_vals: copy"));
+  size_t off = 0;
+  while(off < n) {
+    uint64_t take = n - off;
+    if(capacity_managed(t)) { rc = ensure_capacity(t, n - off, &take); if(rc) return done(rc); }
+    uint64_t small = 0, big = 0;                              // what the overflow side table has to be ready for (ensure_ovf's two bounds)
+    for(size_t i = off; i < off + take; ++i) { if(t->g.cnt_bits < 64 && (vals[i] >> t->g.cnt_bits)) ++big; else small += vals[i]; }
+    rc = ensure_ovf(t, small, big); if(rc) return done(rc);
+    rc = part_flush(t); if(rc) return done(rc);
+    t->pristine = false;
+    const dim3 grid(grid_for(t, take / kBlock + 1)), block(kBlock);
+    with_view(t, [&](const auto& T) {
+      hipLaunchKernelGGL(add_pairs_kernel, grid, block, 0, t->stream, T, (const uint64_t*)(d_k + off * kw), (const uint64_t*)(d_v + off), (uint64_t)take, t->key_words);
+    });
+    if(hipGetLastError() != hipSuccess) return done(fail(JFGPU_E_HIP, "add_key_vals: launch"));
+    off += (size_t)take;
+  }
+  rc = done(JFGPU_OK);
+  return rc ? rc : check_deferred(t);
 }
 
 int jfgpu_lookup_dev(jfgpu_table* t, const uint64_t* d_keys, size_t n, uint64_t* d_vals, uint8_t* d_found) {

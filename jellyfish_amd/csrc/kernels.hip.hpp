@@ -285,7 +285,7 @@ __device__ inline bool table_add_val(const DevTable& T, const uint64_t* fwd_lds,
 // ---- slot access per key width ------------------------------------------------------
 // What a kernel needs from its view (DevTable here, WideTable in kernels_wide.hip.hpp, NTable in kernels_nword.hip.hpp), so
 // that it is written once.  The kernels that walk a whole table: rehash_kernel, scan_kernel and dump_tiles_words_kernel
-// below, reshard_kernel and add_pairs_kernel in abi_comm.inl.  The kernels that are handed a list of keys: add_keys_kernel,
+// below, reshard_kernel and add_pairs_kernel in kernels_comm.hip.hpp.  The kernels that are handed a list of keys: add_keys_kernel,
 // update_keys_kernel and lookup_kernel below.  A specialisation has
 //   Key, Slot                        a key, and what was read of a slot
 //   geom(T)                          the table's TableGeom

@@ -66,33 +66,46 @@ void check_create(const char* what, std::function<int(H**)> create, std::functio
 typedef std::vector<uint8_t> Bytes;
 void put(Bytes& out, const void* p, size_t n) { out.insert(out.end(), (const uint8_t*)p, (const uint8_t*)p + n); }
 
-// make() -> handle, job(handle, result) -> rc, destroy(handle); check(result): the undisturbed run's result is right
+// make() -> handle, job(handle, result) -> rc, destroy(handle); check(result): the undisturbed run's result is right;
+// every: which allocations are failed -- all of them (1), or the first and every `every`-th after it;
+// took_path(handle): after every run that is meant to succeed, the handle shows that the job went the way this check is about;
+// absorbed(handle): the job is one the engine may finish without the memory (shards that cannot double carry on as they
+// are): a failed allocation may then end without an error, if the handle shows that this is what happened and the result
+// is the undisturbed one.  Everything else that returns no error after a failed allocation fails the check.
 template <class H>
 void check_run(const char* what, std::function<H*()> make, std::function<int(H*, Bytes&)> job, std::function<void(H*)> destroy,
-               std::function<bool(const Bytes&)> check) {
+               std::function<bool(const Bytes&)> check, long every = 1, std::function<bool(H*)> took_path = nullptr,
+               std::function<bool(H*)> absorbed = nullptr) {
   g_n = 0;
   const Live before = live();
   Bytes ref;
-  { H* h = make(); CHECK(h != nullptr, what); CHECK(job(h, ref) == JFGPU_OK, what); destroy(h); }
+  { H* h = make(); CHECK(h != nullptr, what); CHECK(job(h, ref) == JFGPU_OK, what); CHECK(!took_path || took_path(h), what); destroy(h); }
   CHECK(same(before, live()), what);
   CHECK(check(ref), what);
-  for(g_n = 1;; ++g_n) {
+  long n_absorbed = 0;
+  for(g_n = 1;; g_n += every) {
     CHECK(g_n < 1000, what);
     H* h = make(); CHECK(h != nullptr, what);
     Bytes got;
     bool fired = false;
     const int rc = with_failure(g_n, &fired, [&] { return job(h, got); });
+    const bool was_absorbed = fired && rc == JFGPU_OK && absorbed && absorbed(h);
+    if(!fired) CHECK(!took_path || took_path(h), what);
     destroy(h);
     CHECK(same(before, live()), what);
     if(!fired) {
       CHECK(rc == JFGPU_OK && got == ref, what);
-      printf("own_check: %-28s %3ld allocations, each failed once: error, nothing left behind, a fresh handle is right\n", what, g_n - 1);
+      if(every == 1) printf("own_check: %-28s %3ld allocations, each failed once: error, nothing left behind, a fresh handle is right\n", what, g_n - 1);
+      else printf("own_check: %-28s fewer than %ld allocations, every %ld-th failed once: error, nothing left behind, a fresh handle is right\n", what, g_n, every);
+      if(absorbed) printf("own_check: %-28s     of them %ld were absorbed: no error, growth off, the undisturbed result\n", what, n_absorbed);
       return;
     }
+    if(was_absorbed) { CHECK(got == ref, what); ++n_absorbed; continue; }
     CHECK(rc != JFGPU_OK, what);
     Bytes again;
     h = make(); CHECK(h != nullptr, what);
     CHECK(job(h, again) == JFGPU_OK && again == ref, what);
+    CHECK(!took_path || took_path(h), what);
     destroy(h);
     CHECK(same(before, live()), what);
   }
@@ -257,6 +270,117 @@ void bloom_run_check() {
   });
 }
 
+// ---- the communicator, local transport (the one the emulated build has) --------------------------------------------------
+// `world` shards of one table, a local communicator over them and a device buffer of input per rank.
+struct Shards {
+  jfgpu_comm* c = nullptr;
+  std::vector<jfgpu_table*> t;
+  std::vector<char*> d_in; std::vector<size_t> n;
+};
+void shards_destroy(Shards* s) {
+  jfgpu_comm_destroy(s->c);
+  for(jfgpu_table* t : s->t) jfgpu_destroy(t);
+  for(char* d : s->d_in) (void)hipFree(d);
+  delete s;
+}
+// rank r's input: bytes[r] random bases (one N in the middle); `items`: JFGPU_COMM_ITEMS, read when the handles are made
+Shards* shards_make(int world, uint32_t k, uint64_t size, int mode, const char* items, const std::vector<size_t>& bytes) {
+  setenv("JFGPU_COMM_ITEMS", items, 1);
+  std::unique_ptr<Shards> s(new Shards);
+  uint32_t sb = 0; while((1 << sb) < world) ++sb;
+  uint64_t x = 0x2545F4914F6CDD1Dull + world;
+  bool ok = true;
+  for(int r = 0; r < world && ok; ++r) {
+    jfgpu_params p; memset(&p, 0, sizeof p);
+    p.k = k; p.canonical = 1; p.size = size; p.device = -1; p.shard_bits = sb; p.shard_id = (uint32_t)r;
+    jfgpu_table* t = nullptr;
+    ok = jfgpu_create(&p, &t) == JFGPU_OK;
+    if(ok) { s->t.push_back(t); ok = !mode || jfgpu_set_mode(t, mode) == JFGPU_OK; }
+    std::string seq(bytes[r], 'A');
+    for(char& ch : seq) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; ch = "ACGT"[x >> 62]; }
+    if(!seq.empty()) seq[seq.size() / 2] = 'N';
+    char* d = nullptr;
+    ok = ok && hipMalloc((void**)&d, seq.size() + 64) == hipSuccess;
+    if(ok) { s->d_in.push_back(d); s->n.push_back(seq.size()); ok = seq.empty() || hipMemcpy(d, seq.data(), seq.size(), hipMemcpyHostToDevice) == hipSuccess; }
+  }
+  ok = ok && jfgpu_comm_create_local(world, -1, &s->c) == JFGPU_OK;
+  Shards* out = s.release();
+  if(!ok) { shards_destroy(out); out = nullptr; }
+  return out;
+}
+// one step, the end of the exchange, every shard applied; the result: sent, received and the content of the whole table
+// (records, sum of counts, sum and xor of the records' hashes over the shards: whatever the geometry the shards end with)
+int shards_step(Shards* s, Bytes& out) {
+  uint64_t sent = 0, received = 0, whole[4] = {0, 0, 0, 0};
+  int rc = jfgpu_comm_local_step(s->c, s->t.data(), s->d_in.data(), s->n.data());
+  if(!rc) rc = jfgpu_comm_finish(s->c, &sent, &received);
+  for(jfgpu_table* t : s->t) {
+    uint64_t d[4] = {0, 0, 0, 0};
+    if(!rc) rc = jfgpu_sync(t);
+    if(!rc) rc = jfgpu_digest(t, 0, ~0ull, d);
+    whole[0] += d[0]; whole[1] += d[1]; whole[2] += d[2]; whole[3] ^= d[3];
+  }
+  put(out, &sent, 8); put(out, &received, 8); put(out, whole, sizeof whole);
+  return rc;
+}
+void comm_create_check(int world) {
+  char what[64]; snprintf(what, sizeof what, "jfgpu_comm_create_local W = %d", world);
+  check_create<jfgpu_comm>(what, [world](jfgpu_comm** out) { return jfgpu_comm_create_local(world, -1, out); }, jfgpu_comm_destroy);
+}
+
+// every: only every `every`-th allocation of the run is failed (1: all of them)
+void comm_step_check(const char* what, int world, uint32_t k, uint64_t size, int mode, const char* items, const std::vector<size_t>& bytes, long every,
+                     std::function<bool(Shards*)> took_path, std::function<bool(Shards*)> absorbed = nullptr) {
+  uint64_t mers = 0;                                                           // the N at b / 2 cuts an input in two runs
+  for(size_t b : bytes) for(size_t run : {b / 2, b - b / 2 - (b ? 1 : 0)}) mers += run >= k ? run - k + 1 : 0;
+  check_run<Shards>(what, [&] { return shards_make(world, k, size, mode, items, bytes); }, shards_step, shards_destroy,
+                    [mers](const Bytes& out) {                                 // what was sent arrived, and the table counts every k-mer of the input
+    uint64_t v[6]; memcpy(v, out.data(), sizeof v);
+    return v[0] == mers && v[1] == mers && v[3] == mers;
+  }, every, took_path, absorbed);
+}
+// how the step just made travelled: every rank's region capacity of that step (0: as keys); as items, every rank was
+// also sent some (the claims summed by the receive side)
+bool step_went_as_items(Shards* s) {
+  for(auto& R : s->c->ranks) {
+    unsigned long long claimed = 0;
+    if(!R.icap[R.turn ^ 1] || hipMemcpy(&claimed, R.d_claimed, 8, hipMemcpyDeviceToHost) != hipSuccess || !claimed) return false;
+  }
+  return true;
+}
+bool step_went_as_keys(Shards* s) {
+  for(auto& R : s->c->ranks) if(R.icap[R.turn ^ 1]) return false;
+  return true;
+}
+
+// two counters filled with different keys, merged: both hold the cells of both
+struct Blooms { jfgpu_comm* c = nullptr; jfgpu_bloom* b[2] = {nullptr, nullptr}; };
+void blooms_destroy(Blooms* s) { jfgpu_comm_destroy(s->c); for(jfgpu_bloom* b : s->b) jfgpu_bc_destroy(b); delete s; }
+void comm_bc_merge_check() {
+  check_run<Blooms>("jfgpu_comm_bc_merge_local", [] {
+    Blooms* s = new Blooms;
+    bool ok = true;
+    for(int r = 0; r < 2 && ok; ++r) {
+      jfgpu_bloom_params p; memset(&p, 0, sizeof p);
+      p.k = 21; p.canonical = 0; p.m = 100003; p.nb_hashes = 3; p.device = -1;
+      const uint64_t keys[3] = {5, 6 + (uint64_t)r, 7 + 2 * (uint64_t)r};
+      uint8_t before[3];
+      ok = jfgpu_bc_create(&p, &s->b[r]) == JFGPU_OK && jfgpu_bc_keys(s->b[r], keys, 3, before, 1) == JFGPU_OK;
+    }
+    ok = ok && jfgpu_comm_create_local(2, -1, &s->c) == JFGPU_OK;
+    if(!ok) { blooms_destroy(s); s = nullptr; }
+    return s;
+  }, [](Blooms* s, Bytes& out) {
+    int rc = jfgpu_comm_bc_merge_local(s->c, s->b);
+    const uint64_t keys[5] = {5, 6, 7, 9, 8};                 // seen twice, once, twice (rank 0's 7, rank 1's 7), once, never
+    for(jfgpu_bloom* b : s->b) { uint8_t got[5] = {9, 9, 9, 9, 9}; if(!rc) rc = jfgpu_bc_keys(b, keys, 5, got, 0); put(out, got, 5); }
+    return rc;
+  }, blooms_destroy, [](const Bytes& out) {
+    const uint8_t want[5] = {2, 1, 2, 1, 0};
+    return out.size() == 10 && !memcmp(out.data(), want, 5) && !memcmp(out.data() + 5, want, 5);
+  });
+}
+
 }  // namespace
 
 int main() {
@@ -279,6 +403,18 @@ int main() {
   text_run_check();
   table_run_check();
   bloom_run_check();
+  comm_create_check(2); comm_create_check(4);
+  comm_step_check("comm step, keys", 2, 16, 1ull << 20, 2, "0", {90000, 40000}, 1, step_went_as_keys);
+  // a shape of test_comm_item_path_equals_single_table (k = 16, world 2, 2^26 slots, partitioned mode: a shard has its two
+  // partition levels, which the item path needs); steps of 90000 and 40000 bytes
+  comm_step_check("comm step, items", 2, 16, 1ull << 26, 2, "2", {90000, 40000}, 1, step_went_as_items);
+  // shards of 2^11 slots for 10^5 distinct k-mers: the first step doubles them, more than once.  A doubled shard that cannot
+  // be allocated is no error (comm_grow: "if anybody cannot, nobody grows"): growth goes off on every shard
+  comm_step_check("comm step, comm_grow", 2, 21, 1ull << 12, 0, "0", {60000, 20000}, 1, [](Shards* s) {
+    jfgpu_info a, b;
+    return jfgpu_get_info(s->t[0], &a) == JFGPU_OK && jfgpu_get_info(s->t[1], &b) == JFGPU_OK && a.lsize > 15 && a.lsize == b.lsize;
+  }, [](Shards* s) { return !s->t[0]->grow_on && !s->t[1]->grow_on; });
+  comm_bc_merge_check();
   const Live end = live();
   if(end.mem || end.streams || end.events) { fprintf(stderr, "own_check: at exit %zu bytes, %ld streams, %ld events are still held\n", end.mem, end.streams, end.events); return 1; }
   printf("own_check: ok\n");

@@ -2,7 +2,9 @@
 tests/host/own_check.cc -- the engine's translation unit under the host emulation, built here with AddressSanitizer into a
 stand-alone program and run as a plain child process.  Every allocation of every create function and of a small merge,
 text, table and Bloom run is made to fail once: the call must report it, hand nothing half-built out and leave nothing
-allocated; LeakSanitizer's report at exit covers what the emulation's counters do not see.
+allocated; LeakSanitizer's report at exit covers what the emulation's counters do not see.  The same for the multi-GPU
+communicator on its in-process transport: its create at world 2 and 4, a key-path step, an item-path step, a step whose
+shards double and the merge of two Bloom counters.
 
 The build takes about as long as the emulated engine's own (tests/host/build_emu.sh)."""
 import os
@@ -28,5 +30,7 @@ def test_failed_allocations_leave_nothing_behind(tmp_path):
     # every family of entry points was reached
     for what in ("jfgpu_create k = 21", "jfgpu_create k = 40", "jfgpu_create k = 100", "jfgpu_bc_create k = 21", "jfgpu_bc_create k = 100",
                  "jfgpu_bf_create", "jfgpu_parser_create + bgzf", "jfgpu_merge_create", "jfgpu_text_create", "jfgpu_merge_run",
-                 "jfgpu_text_run", "add_keys / lookup / query", "jfgpu_bc_keys"):
+                 "jfgpu_text_run", "add_keys / lookup / query", "jfgpu_bc_keys", "jfgpu_comm_create_local W = 2",
+                 "jfgpu_comm_create_local W = 4", "comm step, keys", "comm step, items", "comm step, comm_grow",
+                 "jfgpu_comm_bc_merge_local"):
         assert what in r.stdout, what

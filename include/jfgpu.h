@@ -279,6 +279,19 @@ int  jfgpu_bc_load(jfgpu_bloom* b, const uint8_t* data);
  * it).  keys: ceil(2k / 64) little-endian words per k-mer, mer_dna::data()'s layout, key after key -- one word for
  * k <= 32, two for k <= 64, three for k <= 96, four for k <= 128; bits beyond 2k are ignored. */
 int  jfgpu_bc_keys(jfgpu_bloom* b, const uint64_t* keys, size_t n, uint8_t* out, int do_insert);
+/* query_from_sequence (sub_commands/query_main.cc:44-51) when the database is a Bloom counter (:99-104): check() of every
+ * k-mer of one parser-contract buffer, in one kernel and for every mer length.  The contract is jfgpu_query_ascii(_dev)'s:
+ * both outputs have n entries indexed by the position of the k-mer's LAST base, every entry is written and nothing beyond
+ * n, flags is optional.
+ *   vals[p]   check() of the k-mer (of its canonical form when the counter is canonical): 0, 1 or 2; 0 where no k-mer ends
+ *   flags[p]  JFGPU_Q_MER: a k-mer ends at p; JFGPU_Q_FOUND: vals[p] != 0; JFGPU_Q_REVCOMP: the counter is canonical and the key
+ *             asked is the reverse complement of the text (never set for a palindrome)
+ * The counter is only read and its k-mer tally (jfgpu_bc_sync) stays; pending partitioned increments are applied first, as
+ * by jfgpu_bc_keys.  A one-pass filter (jfgpu_bf_create) holds no counts: JFGPU_E_UNSUPPORTED.  The _dev form is asynchronous
+ * on the counter's stream; the host form stages the buffer in pieces that overlap by k - 1 bytes and reports every
+ * position once. */
+int  jfgpu_bc_query_ascii_dev(jfgpu_bloom* b, const char* d_bases, size_t n, uint64_t* d_vals, uint8_t* d_flags);
+int  jfgpu_bc_query_ascii(jfgpu_bloom* b, const char* bases, size_t n, uint64_t* vals, uint8_t* flags);
 /* count --bf-size N --bf-fp F (count_main.cc:121-131,321-323; bloom_filter.hpp:44-68): a Bloom filter of m = opt_m(F, N)
  * BITS with opt_k(F) hashes, filled by the count itself -- attached with jfgpu_attach_bloom, every k-mer sets its bits
  * and is counted only if all of them were set before (its first sighting only marks it).  Same params struct; the
@@ -540,6 +553,43 @@ int  jfgpu_text_counts(jfgpu_text* x, uint64_t out4[4]);
  * jfgpu_dump_begin; x's applies to the chunk as well (leave it at [0, 2^64 - 1] to write every record).  x's k and
  * counter_len must be the table's k and out_counter_len and both must live on one device: JFGPU_E_INVALID otherwise. */
 int  jfgpu_dump_next_text(jfgpu_table* t, jfgpu_text* x, char* out, uint64_t capacity_bytes, uint64_t* n_records, uint64_t* n_bytes);
+
+/* ---- query text: the lines of `query -s` built on the device ----
+ * Replaces the line loop of query_from_sequence (sub_commands/query_main.cc:44-51): for every position p of a contract
+ * buffer with JFGPU_Q_MER set, in increasing p, one line
+ *   KMER COUNT\n
+ * KMER the k bytes ending at p in upper case (byte & 0xDF), with JFGPU_Q_REVCOMP their reverse complement -- the form that
+ * was looked up, as mer_dna::to_str prints it -- and COUNT the decimal vals[p].  vals and flags are trusted to be the answer
+ * of jfgpu_query_ascii(_dev) or jfgpu_bc_query_ascii(_dev) for the same buffer; a JFGPU_Q_MER at p < k - 1 makes no line. */
+typedef struct jfgpu_qtext jfgpu_qtext;
+typedef struct jfgpu_qtext_params {
+  uint32_t k;                /* 1..128 */
+  int32_t  device;           /* -1 = current */
+  uint64_t piece_positions;  /* positions looked up and formatted in one go by the host forms, at least k; 0 = the engine's
+                                default (JFGPU_QUERY_PIECE, else kQueryTextPiecePositions) */
+} jfgpu_qtext_params;
+int  jfgpu_qtext_create(const jfgpu_qtext_params* p, jfgpu_qtext** out);
+void jfgpu_qtext_destroy(jfgpu_qtext* x);
+/* The longest line: k + 2 + 20. */
+int  jfgpu_qtext_line_max(const jfgpu_qtext* x, uint32_t* bytes);
+/* Device to device, synchronous at return like jfgpu_text_format_dev.  d_bases, d_flags and d_text at any alignment, d_vals
+ * on 8 bytes; nothing outside their first n entries is read, nothing outside d_text[0, *n_bytes) written.  *n_bytes /
+ * *n_lines: the text's bytes and lines.  JFGPU_E_INVALID, with nothing written to d_text and *n_bytes the bytes needed, when
+ * they exceed capacity_bytes. */
+int  jfgpu_qtext_format_dev(jfgpu_qtext* x, const char* d_bases, size_t n, const uint64_t* d_vals, const uint8_t* d_flags,
+                            char* d_text, uint64_t capacity_bytes, uint64_t* n_bytes, uint64_t* n_lines);
+/* Host forms: look-up and formatting of a host buffer (any alignment), the text handed to the sink in order, whole lines.
+ * Pieces of piece_positions positions that overlap by k - 1 bytes, every line once: piece i + 1 is uploaded and looked up
+ * while the text of piece i comes down and goes to the sink.  A piece without a line does not reach the sink; a sink that
+ * returns non-zero stops the run (JFGPU_E_INVALID).  x's k must be the table's or counter's and both must live on one
+ * device: JFGPU_E_INVALID otherwise.  A table that is a shard, a one-pass filter: JFGPU_E_UNSUPPORTED. */
+int  jfgpu_query_text(jfgpu_table* t, jfgpu_qtext* x, const char* bases, size_t n, jfgpu_text_sink sink, void* user);
+int  jfgpu_bc_query_text(jfgpu_bloom* b, jfgpu_qtext* x, const char* bases, size_t n, jfgpu_text_sink sink, void* user);
+/* Milliseconds of the last run: upload (staging + host-to-device copies), kernels (look-up and format, HIP events),
+ * download, sink. */
+int  jfgpu_qtext_last_ms(jfgpu_qtext* x, double out4[4]);
+/* The last run's pieces, positions, lines and bytes. */
+int  jfgpu_qtext_counts(jfgpu_qtext* x, uint64_t out4[4]);
 
 /* ---- measurement helpers (bench.py; not part of the reference surface) -- */
 /* Per-kernel HIP-event timing on the table's stream.  which: 0 count (direct), 1 add_keys,

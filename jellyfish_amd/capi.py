@@ -66,6 +66,10 @@ class TextParams(C.Structure):
                 ("window_records", C.c_uint64)]
 
 
+class QTextParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("device", C.c_int32), ("piece_positions", C.c_uint64)]
+
+
 TEXT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64)
 TEXT_COLUMN, TEXT_FASTA = 0, 1
 MERGE_SUM, MERGE_MIN, MERGE_MAX, MERGE_JACCARD = range(4)
@@ -130,6 +134,8 @@ SIGNATURES = {
     "jfgpu_bc_read": (C.c_int, [_P, _P]),
     "jfgpu_bc_load": (C.c_int, [_P, _P]),
     "jfgpu_bc_keys": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int]),
+    "jfgpu_bc_query_ascii_dev": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "jfgpu_bc_query_ascii": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "jfgpu_bc_set_mode": (C.c_int, [_P, C.c_int]),
     "jfgpu_bc_reserve": (C.c_int, [_P, C.c_uint64]),
     "jfgpu_bc_profile_enable": (C.c_int, [_P, C.c_int]),
@@ -171,6 +177,14 @@ SIGNATURES = {
     "jfgpu_text_last_ms": (C.c_int, [_P, _P]),
     "jfgpu_text_counts": (C.c_int, [_P, _P]),
     "jfgpu_dump_next_text": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "jfgpu_qtext_create": (C.c_int, [C.POINTER(QTextParams), C.POINTER(_P)]),
+    "jfgpu_qtext_destroy": (None, [_P]),
+    "jfgpu_qtext_line_max": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "jfgpu_qtext_format_dev": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "jfgpu_query_text": (C.c_int, [_P, _P, _P, C.c_size_t, TEXT_SINK, _P]),
+    "jfgpu_bc_query_text": (C.c_int, [_P, _P, _P, C.c_size_t, TEXT_SINK, _P]),
+    "jfgpu_qtext_last_ms": (C.c_int, [_P, _P]),
+    "jfgpu_qtext_counts": (C.c_int, [_P, _P]),
     "jfgpu_set_growth": (C.c_int, [_P, C.c_int]),
     "jfgpu_reference_matrix": (C.c_int, [C.c_uint32, C.c_uint32, _P]),
     "jfgpu_table_bytes": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -693,6 +707,20 @@ class Bloom:
         """Launches of the ring P2 kernel (p2_ring_kernel<BloomRingDirect>) since the last profile_reset: profile slot 4."""
         return self.profile_get(4)[1]
 
+    def query_ascii(self, seq: bytes):
+        """check() of every k-mer of a contract buffer, indexed by the position of the k-mer's last base:
+        (vals uint64[n] of 0, 1 or 2, flags uint8[n] of Q_MER | Q_FOUND | Q_REVCOMP)."""
+        buf = np.frombuffer(seq, dtype=np.uint8)
+        vals = np.zeros(len(seq), dtype=np.uint64)
+        flags = np.zeros(len(seq), dtype=np.uint8)
+        _check(self._lib.jfgpu_bc_query_ascii(self._h, buf.ctypes.data if len(seq) else None, len(seq),
+                                              vals.ctypes.data if len(seq) else None, flags.ctypes.data if len(seq) else None))
+        return vals, flags
+
+    def query_ascii_dev(self, d_bases, n, d_vals, d_flags=None):
+        """Asynchronous on the counter's stream: sync() (or any call that reads the counter) before the outputs are read."""
+        _check(self._lib.jfgpu_bc_query_ascii_dev(self._h, _ptr(d_bases), n, _ptr(d_vals), _ptr(d_flags)))
+
     def keys(self, keys, insert=False):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         out = np.zeros(len(keys), dtype=np.uint8)
@@ -879,6 +907,88 @@ class Text:
         """(windows, records read, records kept, bytes written) of the last run."""
         out = np.zeros(4, dtype=np.uint64)
         _check(self._lib.jfgpu_text_counts(self._h, out.ctypes.data))
+        return tuple(int(x) for x in out)
+
+
+class QueryText:
+    """The lines of `query -s` built on the device (jfgpu_qtext_*): "KMER COUNT\n" for every position of a contract buffer
+    at which a k-mer ends, from the answer of Table.query_ascii / Bloom.query_ascii or with the look-up in front."""
+
+    def __init__(self, k, device=-1, piece_positions=0):
+        self._lib = load()
+        self.k = k
+        p = QTextParams(k=k, device=device, piece_positions=piece_positions)
+        h = _P()
+        _check(self._lib.jfgpu_qtext_create(C.byref(p), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.jfgpu_qtext_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def line_max(self):
+        out = C.c_uint32()
+        _check(self._lib.jfgpu_qtext_line_max(self._h, C.byref(out)))
+        return out.value
+
+    def format_dev(self, d_bases, n, d_vals, d_flags, d_text, capacity_bytes):
+        """Device to device (pointers as _ptr takes them).  Returns (bytes, lines); JfgpuError when capacity_bytes is short
+        (its .needed is then the bytes the text takes)."""
+        nb, nl = C.c_uint64(), C.c_uint64()
+        rc = self._lib.jfgpu_qtext_format_dev(self._h, _ptr(d_bases), n, _ptr(d_vals), _ptr(d_flags), _ptr(d_text), capacity_bytes,
+                                              C.byref(nb), C.byref(nl))
+        if rc != OK:
+            err = JfgpuError(rc, load().jfgpu_last_error().decode(errors="replace"))
+            err.needed = nb.value
+            raise err
+        return nb.value, nl.value
+
+    def _run(self, fn, handle, seq, sink):
+        buf = np.frombuffer(seq, dtype=np.uint8)
+        chunks = []
+
+        def on_chunk(_user, text, n_bytes, n_lines):
+            data = C.string_at(text, int(n_bytes))
+            if sink is not None:
+                rc = sink(data, int(n_lines))
+                if rc:
+                    return int(rc)
+            chunks.append(data)
+            return 0
+
+        cb = TEXT_SINK(on_chunk)
+        _check(fn(handle, self._h, buf.ctypes.data if len(seq) else None, len(seq), cb, None))
+        return b"".join(chunks)
+
+    def run_table(self, table, seq: bytes, sink=None):
+        """jfgpu_query_text: the text of `seq` answered by a Table, as bytes.  sink(text: bytes, n_lines) -> int, when given,
+        sees every chunk first; a non-zero answer stops the run (JfgpuError)."""
+        return self._run(self._lib.jfgpu_query_text, table._h, seq, sink)
+
+    def run_bloom(self, bloom, seq: bytes, sink=None):
+        """jfgpu_bc_query_text: the same, answered by a Bloom counter."""
+        return self._run(self._lib.jfgpu_bc_query_text, bloom._h, seq, sink)
+
+    def last_ms(self):
+        """(upload, kernels, download, sink) milliseconds of the last run."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(self._lib.jfgpu_qtext_last_ms(self._h, out.ctypes.data))
+        return tuple(float(x) for x in out)
+
+    def counts(self):
+        """(pieces, positions, lines, bytes) of the last run."""
+        out = np.zeros(4, dtype=np.uint64)
+        _check(self._lib.jfgpu_qtext_counts(self._h, out.ctypes.data))
         return tuple(int(x) for x in out)
 
 

@@ -1205,56 +1205,99 @@ int query_main(int argc, char* argv[]) {
   struct { binary_query* b; bloom_query* f; uint64_t check(const mer_dna& m) const { return b ? b->check(m) : f->check(m); } } bq{bin.get(), bloom.get()};
   const bool canonical = header.canonical();
   const unsigned k = mer_dna::k();
-  // query_from_sequence (query_main.cc:44-51) answered by the device: the file's records go back into a
-  // table under the header's own matrix (jfgpu_add_key_vals), and the contract buffers of the -s files are handed to
-  // jfgpu_query_ascii as they are -- the k-mers are rolled, made canonical and looked up in one kernel, for every mer
-  // length.  What comes back is a count and three flag bits per position; the k-mer's text is taken from the buffer.
-  // Binary/sorted databases; a Bloom counter, JFGPU_QUERY_HOST=1 or no device take the host's binary search below, and so
-  // does a device that fails before anything was written (no room for the table, ...).
+  // query_from_sequence (query_main.cc:44-51) answered by the device.  A binary/sorted file's records go
+  // back into a table under the header's own matrix (jfgpu_add_key_vals); a bloomcounter file's body goes into a counter
+  // under the header's two matrices (jfgpu_bc_load).  The contract buffers of the -s files are handed over as they are:
+  // the k-mers are rolled, made canonical and looked up in one kernel, for every mer length, and the lines are built on
+  // the device from the answer (jfgpu_query_text / jfgpu_bc_query_text), whose sink writes them to the output stream.
+  // JFGPU_QUERY_FORMAT_HOST=1 keeps the look-up on the device and builds the lines here, from a count and three flag bits
+  // per position.  JFGPU_QUERY_HOST=1, no device or a Bloom counter body of another length than its header's size take the
+  // host loop below, and so does a device that fails before anything was written (no room for the table, ...).
   // JFGPU_QUERY_TRACE: one line on stderr saying which of the two answered.
   const bool trace = getenv("JFGPU_QUERY_TRACE") != nullptr;
   bool on_device = false;
-  if(!sequences.empty() && bin && !getenv("JFGPU_QUERY_HOST") && jfgpu_device_count() > 0) {
-    jfgpu_params p; memset(&p, 0, sizeof p);
-    p.k = k; p.canonical = canonical; p.size = header.size(); p.device = -1; p.out_counter_len = 8;
-    const header_matrix hm = header.matrix();
-    if(!hm.identity) p.matrix_columns = hm.columns.data();
+  const bool bloom_fits = bloom && map.length() - header.offset() == header.size() / 5 + (header.size() % 5 != 0);
+  if(!sequences.empty() && (bin || bloom_fits) && !getenv("JFGPU_QUERY_HOST") && jfgpu_device_count() > 0) {
     jfgpu_table* t = nullptr;
+    jfgpu_bloom* bc = nullptr;
+    jfgpu_qtext* qx = nullptr;
+    auto release = [&]() {
+      if(qx) jfgpu_qtext_destroy(qx);
+      if(t) jfgpu_destroy(t);
+      if(bc) jfgpu_bc_destroy(bc);
+      qx = nullptr; t = nullptr; bc = nullptr;
+    };
     auto to_host = [&](const char* what) {                   // nothing has been written yet: the host path answers
       if(!getenv("JFGPU_QUIET")) std::cerr << "jellyfish-amd query: " << what << " (" << jfgpu_last_error() << "): answering on the host\n";
-      if(t) jfgpu_destroy(t);
-      t = nullptr;
+      release();
     };
-    if(jfgpu_create(&p, &t) != JFGPU_OK) { t = nullptr; to_host("device table not created"); }
-    if(t) {
-      const unsigned kw = (2 * k + 63) / 64, kb = (2 * k + 7) / 8, vb = header.counter_len();
-      const size_t rec = kb + vb, n_rec = (map.length() - header.offset()) / rec;
-      const unsigned char* body = reinterpret_cast<const unsigned char*>(map.base() + header.offset());
-      const size_t kBatch = (size_t)1 << 20;
-      std::vector<uint64_t> keys(kBatch * kw), vals(kBatch);
-      for(size_t r0 = 0; r0 < n_rec && t; r0 += kBatch) {
-        const size_t n = std::min(kBatch, n_rec - r0);
-        std::fill(keys.begin(), keys.begin() + n * kw, 0); std::fill(vals.begin(), vals.begin() + n, 0);
-        for(size_t i = 0; i < n; ++i) { memcpy(&keys[i * kw], body + (r0 + i) * rec, kb); memcpy(&vals[i], body + (r0 + i) * rec + kb, vb); }
-        if(jfgpu_add_key_vals(t, keys.data(), vals.data(), n) != JFGPU_OK) to_host("database not loaded into the device table");
+    const auto load_t0 = std::chrono::steady_clock::now();    // (the trace says what bringing the database to the device took)
+    if(bin) {
+      jfgpu_params p; memset(&p, 0, sizeof p);
+      p.k = k; p.canonical = canonical; p.size = header.size(); p.device = -1; p.out_counter_len = 8;
+      const header_matrix hm = header.matrix();
+      if(!hm.identity) p.matrix_columns = hm.columns.data();
+      if(jfgpu_create(&p, &t) != JFGPU_OK) { t = nullptr; to_host("device table not created"); }
+      if(t) {
+        const unsigned kw = (2 * k + 63) / 64, kb = (2 * k + 7) / 8, vb = header.counter_len();
+        const size_t rec = kb + vb, n_rec = (map.length() - header.offset()) / rec;
+        const unsigned char* body = reinterpret_cast<const unsigned char*>(map.base() + header.offset());
+        const size_t kBatch = (size_t)1 << 20;
+        std::vector<uint64_t> keys(kBatch * kw), vals(kBatch);
+        for(size_t r0 = 0; r0 < n_rec && t; r0 += kBatch) {
+          const size_t n = std::min(kBatch, n_rec - r0);
+          std::fill(keys.begin(), keys.begin() + n * kw, 0); std::fill(vals.begin(), vals.begin() + n, 0);
+          for(size_t i = 0; i < n; ++i) { memcpy(&keys[i * kw], body + (r0 + i) * rec, kb); memcpy(&vals[i], body + (r0 + i) * rec + kb, vb); }
+          if(jfgpu_add_key_vals(t, keys.data(), vals.data(), n) != JFGPU_OK) to_host("database not loaded into the device table");
+        }
       }
+    } else {
+      const header_matrix m1 = header.matrix(1), m2 = header.matrix(2);
+      jfgpu_bloom_params p; memset(&p, 0, sizeof p);
+      p.k = k; p.canonical = canonical; p.m = header.size(); p.nb_hashes = (uint32_t)header.nb_hashes(); p.device = -1;
+      p.matrix1 = m1.columns.data(); p.matrix2 = m2.columns.data();
+      if(m1.columns.size() != 2 * k || m2.columns.size() != 2 * k) to_host("the header's matrices are not 64 x 2k");
+      else if(jfgpu_bc_create(&p, &bc) != JFGPU_OK) { bc = nullptr; to_host("device Bloom counter not created"); }
+      if(bc && jfgpu_bc_load(bc, reinterpret_cast<const uint8_t*>(map.base() + header.offset())) != JFGPU_OK) to_host("database not loaded into the device Bloom counter");
     }
-    if(t) {
+    const double load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - load_t0).count();
+    const bool format_host = getenv("JFGPU_QUERY_FORMAT_HOST") != nullptr;
+    if((t || bc) && !format_host) {
+      jfgpu_qtext_params qp; memset(&qp, 0, sizeof qp);
+      qp.k = k; qp.device = -1;
+      if(jfgpu_qtext_create(&qp, &qx) != JFGPU_OK) { qx = nullptr; to_host("device formatter not created"); }
+    }
+    if(t || bc) {
       std::vector<uint64_t> vals; std::vector<uint8_t> flags;
       std::string text;
       uint64_t positions = 0, n_mers = 0;
+      double ms[4] = {0, 0, 0, 0};
+      struct sink_t { std::ostream* out; uint64_t lines; bool wrote; } sk{&out, 0, false};
+      auto sink_write = [](void* user, const char* data, uint64_t n_bytes, uint64_t n_lines) -> int {
+        sink_t* s = static_cast<sink_t*>(user);
+        s->out->write(data, (std::streamsize)n_bytes);
+        s->lines += n_lines; s->wrote = true;
+        return s->out->good() ? 0 : 1;
+      };
       bool wrote = false;
+      auto failed = [&](const char* what) {                   // after the first byte there is no way back
+        if(wrote || sk.wrote) { const std::string e = jfgpu_last_error(); release(); die("query: " + e); }
+        to_host(what);
+      };
       for(const auto& path : sequences) {
-        if(!t) break;
+        if(!t && !bc) break;
         sequence_parser parser(k, (size_t)8 << 20);
         parser.parse_file(path.c_str(), [&](const char* buf, size_t n) {
-          if(!t || !n) return;
-          vals.resize(n); flags.resize(n);
-          if(jfgpu_query_ascii(t, buf, n, vals.data(), flags.data()) != JFGPU_OK) {
-            if(wrote) { const std::string e = jfgpu_last_error(); jfgpu_destroy(t); die("query: " + e); }
-            to_host("device query failed");
+          if((!t && !bc) || !n) return;
+          if(qx) {
+            if((t ? jfgpu_query_text(t, qx, buf, n, sink_write, &sk) : jfgpu_bc_query_text(bc, qx, buf, n, sink_write, &sk)) != JFGPU_OK) { failed("device query failed"); return; }
+            double m4[4];
+            if(jfgpu_qtext_last_ms(qx, m4) == JFGPU_OK) for(int i = 0; i < 4; ++i) ms[i] += m4[i];
+            positions += n;
             return;
           }
+          vals.resize(n); flags.resize(n);
+          if((t ? jfgpu_query_ascii(t, buf, n, vals.data(), flags.data()) : jfgpu_bc_query_ascii(bc, buf, n, vals.data(), flags.data())) != JFGPU_OK) { failed("device query failed"); return; }
           text.clear();
           for(size_t i = 0; i < n; ++i) {
             if(!(flags[i] & JFGPU_Q_MER)) continue;
@@ -1269,11 +1312,17 @@ int query_main(int argc, char* argv[]) {
           positions += n; wrote = true;
         });
       }
-      if(t) {
-        jfgpu_destroy(t);
+      if(t || bc) {
+        const bool device_lines = qx != nullptr;
+        release();
         sequences.clear();
         on_device = true;
-        if(trace) std::cerr << "query: device k=" << k << " positions=" << positions << " mers=" << n_mers << "\n";
+        if(trace) {
+          char times[160];
+          snprintf(times, sizeof times, " load_ms=%.3f upload_ms=%.3f kernels_ms=%.3f download_ms=%.3f sink_ms=%.3f", load_ms, ms[0], ms[1], ms[2], ms[3]);
+          std::cerr << "query: device k=" << k << " positions=" << positions << " db=" << (bin ? "binary" : "bloomcounter")
+                    << " format=" << (device_lines ? "device" : "host") << times << " mers=" << (device_lines ? sk.lines : n_mers) << "\n";
+        }
       }
     }
   }

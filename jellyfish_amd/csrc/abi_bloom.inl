@@ -254,6 +254,52 @@ int jfgpu_bc_keys(jfgpu_bloom* b, const uint64_t* keys, size_t n, uint8_t* out, 
   return JFGPU_OK;
 }
 
+// query_from_sequence (query_main.cc:44-51) against a Bloom counter (:99-104) over one contract buffer:
+// bloom_query_ascii_kernel, the contract of jfgpu_query_ascii_dev
+int jfgpu_bc_query_ascii_dev(jfgpu_bloom* b, const char* d_bases, size_t n, uint64_t* d_vals, uint8_t* d_flags) {
+  int rc = use_b(b); if(rc) return rc;
+  if(b->kind != 0) return fail(JFGPU_E_UNSUPPORTED, "query_ascii: a one-pass Bloom filter holds bits, not counts");
+  rc = bloom_flush(b); if(rc) return rc;
+  if(!n) return JFGPU_OK;
+  if(!d_bases || !d_vals) return fail(JFGPU_E_INVALID, "null argument");
+  const uint8_t* base; int64_t lo, hi;
+  align_buffer(d_bases, n, base, lo, hi);
+  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_tiles, (int64_t)b->n_cu * 8));
+  if(b->nword) hipLaunchKernelGGL(bloom_query_ascii_kernel<NGeom>, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->ng, base, lo, hi, d_vals, d_flags);
+  else if(b->wide) hipLaunchKernelGGL(bloom_query_ascii_kernel<WideGeom>, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->wg, base, lo, hi, d_vals, d_flags);
+  else hipLaunchKernelGGL(bloom_query_ascii_kernel<TableGeom>, dim3(grid), dim3(kBlock), 0, b->stream, b->view(), b->g, base, lo, hi, d_vals, d_flags);
+  HIP_TRY(hipGetLastError());
+  return JFGPU_OK;
+}
+
+// Host arrays, staged like jfgpu_bc_insert_ascii: pieces overlap by k - 1 bytes, and the first k - 1 outputs of every piece
+// after the first (windows the piece before has answered) are not copied back.
+int jfgpu_bc_query_ascii(jfgpu_bloom* b, const char* bases, size_t n, uint64_t* vals, uint8_t* flags) {
+  int rc = use_b(b); if(rc) return rc;
+  if(b->kind != 0) return fail(JFGPU_E_UNSUPPORTED, "query_ascii: a one-pass Bloom filter holds bits, not counts");
+  if(!n) return JFGPU_OK;
+  if(!bases || !vals) return fail(JFGPU_E_INVALID, "null argument");
+  const size_t piece = std::min(kStageBytes, n), seam = b->g.k - 1;
+  if(!b->d_stage) { rc = b->d_stage.alloc(kStageBytes); if(rc) return rc; }
+  DevBuf<uint64_t> d_v; DevBuf<uint8_t> d_f;
+  rc = d_v.alloc(piece); if(rc) return rc;
+  if(flags && !d_f.try_alloc(piece)) return fail(JFGPU_E_ALLOC, "hipMalloc query flags");
+  hipError_t e = hipSuccess;
+  for(size_t o = 0; o < n && e == hipSuccess && !rc; o += kStageBytes - seam) {
+    const size_t len = std::min(kStageBytes, n - o), skip = o ? seam : 0;
+    e = hipMemcpyAsync(b->d_stage, bases + o, len, hipMemcpyHostToDevice, b->stream);
+    if(e == hipSuccess) rc = jfgpu_bc_query_ascii_dev(b, (const char*)b->d_stage.get(), len, d_v, d_f);
+    if(e == hipSuccess && !rc) e = hipMemcpyAsync(vals + o + skip, d_v + skip, (len - skip) * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream);
+    if(e == hipSuccess && !rc && flags) e = hipMemcpyAsync(flags + o + skip, d_f + skip, len - skip, hipMemcpyDeviceToHost, b->stream);
+    if(e == hipSuccess && !rc) e = hipStreamSynchronize(b->stream);      // (the stage, d_v and d_f are the next piece's too)
+    if(o + len >= n) break;
+  }
+  hipStreamSynchronize(b->stream);
+  if(e != hipSuccess) return fail(JFGPU_E_HIP, hipGetErrorString(e));
+  return rc;
+}
+
 int jfgpu_bc_set_mode(jfgpu_bloom* b, int mode) {
   int rc = use_b(b); if(rc) return rc;
   if(mode < 0 || mode > 2) return fail(JFGPU_E_INVALID, "mode must be 0 (auto), 1 (direct) or 2 (partitioned)");

@@ -153,8 +153,9 @@ int use_dev(const H* h, const char* null_text) {
 
 static double wall_ms(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
-// The two-deep pipeline of jfgpu_merge_run and jfgpu_text_run: window i is staged in pinned memory and uploaded on s_up
-// while the kernels of window i - 1 run on s_k and the output of window i - 2 .. i - 1 is downloaded on s_down and sunk.
+// The two-deep pipeline of jfgpu_merge_run, jfgpu_text_run and jfgpu_query_text / jfgpu_bc_query_text: window i is staged in
+// pinned memory and uploaded on s_up while the kernels of window i - 1 run on s_k and the output of window i - 2 .. i - 1 is
+// downloaded on s_down and sunk.
 // A slot (i & 1) is a window's buffers and events.  The callers cut the windows, fill h_in, launch their kernels between
 // kernels_begin and kernels_end, and read what their status block means; the steps they share are here.
 struct WindowPipe {

@@ -31,11 +31,13 @@
 #include "kernels_wide.hip.hpp"
 #include "kernels_wide_part.hip.hpp"
 #include "kernels_nword.hip.hpp"
+#include "kernels_bloom_query.hip.hpp"
 #include "kernels_parse.hip.hpp"
 #include "kernels_bgzf.hip.hpp"
 #include "kernels_stream.hip.hpp"
 #include "kernels_merge.hip.hpp"
 #include "kernels_text.hip.hpp"
+#include "kernels_qtext.hip.hpp"
 #include "kernels_comm.hip.hpp"
 
 using namespace jfgpu;
@@ -1540,3 +1542,4 @@ int jfgpu_memcpy_d2h(jfgpu_table* t, void* dst, const void* d_src, size_t bytes)
 #include "abi_comm.inl"
 #include "abi_merge.inl"
 #include "abi_text.inl"
+#include "abi_qtext.inl"

@@ -38,6 +38,14 @@ constexpr uint64_t kMergeWindowRecords = 1ull << 22;
 // line: 158 MB each at k = 128, 35 MB at k = 21) and as much again on the device, a quarter of what 2^22 takes.
 constexpr uint64_t kTextWindowRecords = 1ull << 20;
 
+// query -s with its lines built on the device (abi_qtext.inl): positions looked up and formatted in one piece when the
+// caller names no size (JFGPU_QUERY_PIECE).  A piece's text buffer is sized for the worst case, a line of k + 22 bytes at
+// every position, on the device and twice (the double buffer): 2^21 positions are 2 x 90 MB at k = 21 and 2 x 315 MB at
+// k = 128, beside 9 bytes a position of answer.  The pinned buffer the text comes down into grows to the bytes a piece
+// really has (k + 3 a line for counts below ten: 50 MB at k = 21).  That is the size class kTextWindowRecords settled on for
+// dump, where larger pinned buffers cost more to allocate inside the run than longer windows saved; not measured for query.
+constexpr uint64_t kQueryTextPiecePositions = 1ull << 21;
+
 // `dump` (jellyfish_amd/cli/jellyfish_amd.cc, which includes this header for it): files with fewer records than this are
 // formatted by the host loop (JFGPU_DUMP_DEVICE_MIN overrides).  The smallest power of two in the sweep of
 // profiles/dump_bench.txt from which the device path's wall time -- process start and HIP initialisation, 0.25 - 0.3 s,
@@ -69,8 +77,10 @@ struct Tuning {
   int bloom_mode = 0;            // JFGPU_BLOOM_MODE=direct|partitioned      0: not set
   int bloom_p1_two = 1;          // JFGPU_BLOOM_P1_TWO     P1b as two workgroups per CU (rounds of 5 cells, nibble tables); 0: one, rounds of 10 (A/B)
   int bloom_p1_ring = 1;         // JFGPU_BLOOM_P1_RING    P1b through rings of 256 bytes where the filter gives it >= 200 buckets of at most 512 (0: the sort-based kernels; A/B)
+  // ---- query formatters (jfgpu_qtext_create)
+  uint64_t query_piece = 0;      // JFGPU_QUERY_PIECE      positions of a piece of jfgpu_query_text / jfgpu_bc_query_text when the caller names none (0: kQueryTextPiecePositions)
   // ---- communicators (jfgpu_comm_create*)
-  bool comm_trace = false;       // JFGPU_COMM_TRACE       every rank reports where it is in a step
+  bool comm_trace = false;      // JFGPU_COMM_TRACE       every rank reports where it is in a step
   bool comm_ipc = false;         // JFGPU_COMM_TRANSPORT=ipc   rank processes exchange through hipIpc* copies instead of RCCL
   int comm_ipc_keep = 1;         // JFGPU_IPC_KEEP         ipc transport: 1 = re-allocated send buffers and the peers' mappings of them live until the communicator goes (0: closed / freed as soon as replaced; A/B)
   uint64_t comm_max_msg = 0;     // JFGPU_COMM_MAX_MSG     keys per message round (0: default)
@@ -107,6 +117,7 @@ struct Tuning {
     if(const char* e = str("JFGPU_BLOOM_P1_TWO")) u.bloom_p1_two = atoi(e);
     if(const char* e = str("JFGPU_BLOOM_P1_RING")) u.bloom_p1_ring = atoi(e);
     if(const char* e = str("JFGPU_BLOOM_MODE")) u.bloom_mode = !strcmp(e, "direct") ? 1 : !strcmp(e, "partitioned") ? 2 : 0;
+    if(const char* e = str("JFGPU_QUERY_PIECE")) u.query_piece = strtoull(e, 0, 10);
     u.comm_trace = str("JFGPU_COMM_TRACE") != nullptr;
     if(const char* e = str("JFGPU_COMM_TRANSPORT")) u.comm_ipc = !strcmp(e, "ipc");
     if(const char* e = str("JFGPU_IPC_KEEP")) u.comm_ipc_keep = atoi(e);

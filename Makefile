@@ -2,6 +2,7 @@
 #   make            -> engine + CLI + oracle
 #   make engine     -> jellyfish_amd/lib/libjfgpu.so   (hipcc cross-compiles without a GPU)
 #   make kernel-harness -> tests/kernels/_build/libjfgpu_kt.so   (the stage tests' library; not product)
+#   make kernel-harness-nword -> tests/kernels/_build/libjfgpu_ktn.so   (the same for the keys of three and four words)
 HIPCC    ?= hipcc
 CXX      ?= g++
 ARCH     ?= gfx950
@@ -26,6 +27,14 @@ $(KTDIR)/libjfgpu_kt.so: tests/kernels/stage_harness.hip $(wildcard $(CSRC)/*.hi
 	@mkdir -p $(KTDIR)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ tests/kernels/stage_harness.hip -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
+# ... and the stages of the partitioned insert of three- and four-word keys (tests/kernels/stage_harness_nword.hip;
+# tests/test_gpu_stage_nword.py)
+kernel-harness-nword: $(KTDIR)/libjfgpu_ktn.so
+
+$(KTDIR)/libjfgpu_ktn.so: tests/kernels/stage_harness_nword.hip $(wildcard $(CSRC)/*.hip) $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/*.inl) include/jfgpu.h
+	@mkdir -p $(KTDIR)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ tests/kernels/stage_harness_nword.hip -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+
 cli: bin/jellyfish-amd
 
 bin/jellyfish-amd: $(wildcard jellyfish_amd/cli/*.cc) $(wildcard jellyfish_amd/include/jellyfish_amd/*.hpp) include/jfgpu.h $(LIBDIR)/libjfgpu.so
@@ -39,4 +48,4 @@ oracle:
 
 clean:
 	rm -rf $(LIBDIR) bin oracle/_build $(KTDIR)
-.PHONY: all engine cli oracle clean kernel-harness
+.PHONY: all engine cli oracle clean kernel-harness kernel-harness-nword

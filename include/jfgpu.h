@@ -363,7 +363,14 @@ int  jfgpu_set_spill(jfgpu_table* t, int (*fn)(void* user), void* user);
 /* Insert strategy.  0 auto (default), 1 direct (global 64-bit atomics, kernels.hip.hpp),
  * 2 partitioned (radix partition + LDS-resident tiles, kernels_part.hip.hpp; large batches
  * are buffered on the device and applied at the next jfgpu_sync / read).  Results are
- * bit-identical; the environment variable JFGPU_MODE=direct|partitioned sets the default. */
+ * bit-identical; the environment variable JFGPU_MODE=direct|partitioned (or 1|2) sets the default.
+ * Every key width has the partitioned path: one word, two words (kernels_wide_part.hip.hpp) and three and four words
+ * (65 <= k <= 128, kernels_nword_part.hip.hpp, tables of up to 2^32 slots).  For keys of three and four words auto takes
+ * it only where it was measured faster than the direct kernel (device batches of 1 GiB and more, k <= 100, at most 2^30
+ * slots: profiles/nword_part_rate.txt), and in either mode the direct kernel
+ * still inserts while a Bloom counter or one-pass filter is attached, on a shard, and for the PRIME / UPDATE operations.
+ * Mode 2 is refused (JFGPU_E_UNSUPPORTED) for a geometry without the path: tiny one- and two-word tables, keys of three and
+ * four words in more than 2^32 slots. */
 int  jfgpu_set_mode(jfgpu_table* t, int mode);
 /* Optional: pre-size the partitioned path's device workspace for `input_bytes` of sequence
  * between two syncs (what `-s` is to the table, hash_counter.hpp:56-64: a hint that moves
@@ -610,8 +617,9 @@ int  jfgpu_profile_spans(jfgpu_table* t, int* which, double* ms, size_t cap, siz
  * sampled (host_partition.inl), 8 flushes that ran the plain tile kernel, 9 flushes that ran the HEAVY one, 10-13 launches
  * of the second partition level by kernel (loader / storer rings, shared rings, sort-based single pass, exact count +
  * scatter), 14 / 15 launches of the first level (ring kernel / any other), 16 launches of the tile kernel's instantiation
- * for hole-free regions (the output of the loader / storer rings). */
-#define JFGPU_N_COUNTERS 17
+ * for hole-free regions (the output of the loader / storer rings), 17 launches of the tile kernel of three- and four-word
+ * keys (tile_insert_nword_kernel). */
+#define JFGPU_N_COUNTERS 18
 int  jfgpu_get_counters(jfgpu_table* t, uint64_t* out, uint32_t n);
 /* Synthetic reads: n_reads records of read_len uniform iid bases, each followed by
  * one 'N' separator (the contract buffer the parser would produce for a FASTA of

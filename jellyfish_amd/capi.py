@@ -506,7 +506,7 @@ class Table:
         return list(zip(which[:k].tolist(), ms[:k].tolist()))
 
     COUNTER_NAMES = ("full", "mers", "ovf_full", "ovf_used", "misrouted", "direct", "t_items", "t_queued", "flushes_plain", "flushes_heavy",
-                     "p2_roles", "p2_ring", "p2_sort", "p2_exact", "p1_ring", "p1_other", "tile_dense")
+                     "p2_roles", "p2_ring", "p2_sort", "p2_exact", "p1_ring", "p1_other", "tile_dense", "tile_nword")
 
     def counters(self):
         """jfgpu_get_counters: which paths the work since the last clear took."""

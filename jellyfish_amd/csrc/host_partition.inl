@@ -6,12 +6,21 @@
 // a PartFacts; part_ingest and part_flush_t gather the facts, ask for the plan and carry it out.
 constexpr uint64_t kPartMinBytes = 1u << 20;   // AUTO: smaller device batches take the direct kernel
 
+// Keys of three and four words, AUTO: the partitioned path exactly where profiles/nword_part_rate.txt shows it faster than the
+// direct kernel by more than the spread of five runs -- one batch of 1 GiB of reads, k = 65 / 96 / 100, 2^30 slots (a flush
+// streams every tile that gets an item, and a batch's bucket regions hold a stranded reservation per workgroup: smaller
+// batches lose, as does k = 128 in its 2^31 slots).  k between 100 and 128 and larger tables were not measured: never there.
+// JFGPU_MODE=partitioned / jfgpu_set_mode(t, 2) take the path for every batch.
+constexpr uint64_t kNWordPartMinBytes = 1ull << 30;
+constexpr uint32_t kNWordPartMaxK = 100, kNWordPartMaxLsize = 30;
+bool nword_auto_partitioned(const TableGeom& g, size_t nbytes) { return nbytes >= kNWordPartMinBytes && g.k <= kNWordPartMaxK && g.lsize_l <= kNWordPartMaxLsize; }
+
 void part_geom_init(jfgpu_table* t) {
   const uint32_t bits = t->g.lsize_l - t->g.tile_bits;   // tile-index bits to resolve
-  t->part_ok = false; t->item32 = false; t->item128 = false;
-  if(t->g.tile_bits < kMaxTileBits) return;               // tiny table: one partial tile
+  t->part_ok = false; t->item32 = false; t->item128 = false; t->item256 = false;
+  if(!t->nword && t->g.tile_bits < kMaxTileBits) return;  // tiny table: one partial tile (keys of three and four words: tiles of 2^11 slots, all whole)
   uint32_t b1, b2;
-  const uint32_t one_level = t->wide ? 10 : 11;           // two-word keys only have the single-pass P1 (<= 1024 buckets)
+  const uint32_t one_level = t->wide || t->nword ? 10 : 11;   // keys of two and more words only have the single-pass P1 (<= 1024 buckets)
   if(bits <= one_level) { b1 = bits; b2 = 0; }
   else { b2 = std::min<uint32_t>(11, (bits + 1) / 2); b1 = bits - b2; }
   if(b1 > one_level) return;
@@ -19,21 +28,25 @@ void part_geom_init(jfgpu_table* t) {
   t->pg.rest_shift = t->g.lsize_l - b1;
   t->pg.item_bits = t->pg.rest_shift + t->g.rem_bits;
   if(t->wide) { t->item128 = true; t->part_ok = t->pg.item_bits <= 128; return; }
+  // 256-bit items: all ones is the hole, so an item must never be all ones -- it cannot be while it has fewer than 256 bits
+  // (bit 255 is clear).  It has 2k - b1 of them, and k = 128 forces lsize >= 31, hence b1 >= 1: no geometry is refused here
+  // today (tests/test_nword_part_emu.py walks them all), but a hole that is an item drops k-mers silently.
+  if(t->nword) { t->item256 = true; t->part_ok = t->pg.item_bits < 256; return; }
   if(t->pg.item_bits > 64) return;
   t->item32 = t->pg.item_bits <= 32;
   t->part_ok = true;
 }
 
-size_t item_size(const jfgpu_table* t) { return t->item128 ? 16 : t->item32 ? 4 : 8; }
+size_t item_size(const jfgpu_table* t) { return t->item256 ? 32 : t->item128 ? 16 : t->item32 ? 4 : 8; }
 
 // what the plans may know of a table (part_plan.inl)
 PartFacts part_facts(const jfgpu_table* t) {
   PartFacts f;
-  const DevBloom& bloom = t->wide ? t->wt.bloom : t->dt.bloom;
+  const DevBloom& bloom = t->nword ? t->nt.bloom : t->wide ? t->wt.bloom : t->dt.bloom;
   f.pg = t->pg; f.item_bytes = (uint32_t)item_size(t); f.slot32 = t->g.slot32; f.mode = t->mode; f.n_cu = t->n_cu; f.g1 = t->g1; f.n_tiles = n_tiles_of(t);
-  f.returning = t->returning; f.wide = t->wide; f.filter = bloom.data != nullptr; f.filter_kind = (int)bloom.kind;
+  f.returning = t->returning; f.wide = t->wide; f.nword = t->nword; f.filter = bloom.data != nullptr; f.filter_kind = (int)bloom.kind;
   f.nbytes = t->g.nbytes; f.hash_xs = t->g.hash_xs; f.canonical = t->g.canonical; f.lsize_g = t->g.lsize_g; f.lsize_l = t->g.lsize_l; f.tile_bits = t->g.tile_bits;
-  f.tag_bits = t->item128 ? t->wt.W.tag_full : t->g.tag_bits;
+  f.tag_bits = t->item256 ? t->nt.N.tag_full : t->item128 ? t->wt.W.tag_full : t->g.tag_bits;
   f.items_per_byte = t->items_per_byte; f.ws_cap = t->ws_cap; f.ws_used = t->ws_used; f.reserved_input = t->reserved_input; f.tun = t->tun;
   return f;
 }
@@ -179,10 +192,10 @@ int bloom_cache_decide(jfgpu_table* t) {
 // What the next batch's plan reads and only the device knows, while batches are pending.
 int refresh_estimates(jfgpu_table* t, bool from_keys) {
   if(t->pending.empty() || from_keys) return JFGPU_OK;
-  // 16-byte items: before the first flush the bucket regions are sized for one item per input byte; reads of length L give
+  // 16- and 32-byte items: before the first flush the bucket regions are sized for one item per input byte; reads of length L give
   // (L - k + 1) / (L + 1) (0.58 at k = 63), so the first batch's exact count is read back once (one early wait for its P1)
   // to size the others.
-  if(t->item128 && t->items_per_byte <= 0) {
+  if((t->item128 || t->item256) && t->items_per_byte <= 0) {
     const uint32_t nb = 1u << t->pg.b1;
     const PendingBatch& pb = t->pending.front();
     if(pb.gran_cap && pb.input_bytes >= (1u << 20)) {
@@ -203,7 +216,12 @@ int run_p1(jfgpu_table* t, const P1Plan& p, const uint8_t* base, int64_t lo, int
   const uint32_t nb = 1u << t->pg.b1, gcap = p.gran_cap;
   bool found = false;
   ++(p.kind == kP1Ring ? t->n_p1_ring : t->n_p1_other);
-  if(p.kind == kP1WideGranule) {
+  if(p.kind == kP1NWordGranule) {
+    if(t->tun.flush_trace) fprintf(stderr, "[jfgpu flush] P1: p1_nword_granule_kernel, %u buckets, regions of %u items\n", nb, gcap);
+    found = pick<Inst<1>, Inst<0>>(p.targs, [&](auto I) {
+      hipLaunchKernelGGL((p1_nword_granule_kernel<decltype(I)::v[0] != 0>), grid, block, p.lds, t->stream, t->nt, t->pg, base, lo, hi, gcap, gcur, b.tot, (u256*)b.items);
+    });
+  } else if(p.kind == kP1WideGranule) {
     found = pick<Inst<1, 0, 1>, Inst<0, 0, 1>, Inst<1, 1, 0>, Inst<1, 0, 0>, Inst<0, 1, 0>, Inst<0, 0, 0>>(p.targs, [&](auto I) {
       constexpr auto& A = decltype(I)::v;
       hipLaunchKernelGGL((p1_wide_granule_kernel<A[0] != 0, A[1] != 0, A[2] != 0>), grid, block, p.lds, t->stream, t->wt, t->pg, base, lo, hi, gcap, gcur, b.tot, (u128*)b.items);
@@ -399,7 +417,14 @@ void launch_tile_rank(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t
 // the tile insert of one item array (or of the pending batches themselves), on stream `ts`
 template <typename ITEM>
 void launch_tile_kernel(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, uint32_t sample, hipStream_t ts, bool pair) {
-  if constexpr(sizeof(ITEM) == 16) {
+  if constexpr(sizeof(ITEM) == 32) {
+    // keys of three and four words: 256-bit items, 256-bit slots; 64 KiB of LDS: two blocks per CU
+    const size_t tile_lds = (size_t)32 << t->g.tile_bits;
+    const dim3 block(kNTileBlock), grid((unsigned)std::min<uint64_t>(ntile, (uint64_t)t->n_cu * 8));
+    ++t->n_tile_nword;
+    if(t->tun.flush_trace) fprintf(stderr, "[jfgpu flush] T: tile_insert_nword_kernel, %u tiles from %llu, %u segment(s)\n", ntile, (unsigned long long)tile0, S.n);
+    with_flags(t->returning, [&](auto RT) { hipLaunchKernelGGL(tile_insert_nword_kernel<decltype(RT)::value>, grid, block, tile_lds, ts, t->nt, S, tile0, ntile); });
+  } else if constexpr(sizeof(ITEM) == 16) {
     // two-word keys: 128-bit items, 128-bit slots; 128 KiB of LDS: one block per CU
     const size_t tile_lds = (size_t)16 << t->g.tile_bits;
     const bool pipe = S.n == 1 && t->tun.wide_pipe;        // one item array (a flush's P2 output): the pipelined kernel
@@ -427,13 +452,14 @@ void run_items_direct(jfgpu_table* t, const FlushSizes& fs) {
     const uint64_t span = gc ? (uint64_t)nb1 * gc : n;
     const dim3 grid((unsigned)grid_for(t, (span + kBlock - 1) / kBlock)), block(kBlock);
     with_flags(t->returning, [&](auto RT) {
-      if constexpr(sizeof(ITEM) == 16) hipLaunchKernelGGL(items_direct_wide_kernel<decltype(RT)::value>, grid, block, 0, t->stream, t->wt, t->pg, (const u128*)pb.items, (const uint64_t*)pb.off, gc);
+      if constexpr(sizeof(ITEM) == 32) hipLaunchKernelGGL(items_direct_nword_kernel<decltype(RT)::value>, grid, block, 0, t->stream, t->nt, t->pg, (const u256*)pb.items, (const uint64_t*)pb.off, gc);
+      else if constexpr(sizeof(ITEM) == 16) hipLaunchKernelGGL(items_direct_wide_kernel<decltype(RT)::value>, grid, block, 0, t->stream, t->wt, t->pg, (const u128*)pb.items, (const uint64_t*)pb.off, gc);
       else hipLaunchKernelGGL((items_direct_kernel<ITEM, decltype(RT)::value>), grid, block, 0, t->stream, t->dt, t->pg, (const ITEM*)pb.items, (const uint64_t*)pb.off, gc);
     });
   }
 }
 
-// kRouteSingleLevel: the P1 buckets are the tiles; two-word keys take all batches in one pass, one-word keys one pass a batch
+// kRouteSingleLevel: the P1 buckets are the tiles; keys of two and more words take all batches in one pass, one-word keys one pass a batch
 template <typename ITEM>
 void run_single_level(jfgpu_table* t, const PartFacts& f, const FlushSizes& fs, const SegList& S1) {
   const uint32_t nb1 = 1u << t->pg.b1;
@@ -441,7 +467,7 @@ void run_single_level(jfgpu_table* t, const PartFacts& f, const FlushSizes& fs, 
     ProfScope ps(t, 6, units);
     launch_tile_kernel<ITEM>(t, S, 0, nb1, tile_sample_units(f, nb1, S.n), t->stream, false);
   };
-  if constexpr(sizeof(ITEM) == 16) launch_tiles(S1, fs.total);
+  if constexpr(sizeof(ITEM) >= 16) launch_tiles(S1, fs.total);
   else for(size_t s = 0; s < S1.n; ++s) {
     const uint64_t n = fs.offs[s * (nb1 + 1) + nb1];
     if(!n) continue;
@@ -492,7 +518,7 @@ int run_p2(jfgpu_table* t, const FlushPlan& p, const GroupPlan& q, const SegList
     };
     bool found;
     if constexpr(sizeof(ITEM) == 4) found = pick<Inst<kP2PairPer>, Inst<16>>(q.p2_targs, scatter);
-    else found = pick<Inst<sizeof(ITEM) == 8 ? 14 : 7>>(q.p2_targs, scatter);
+    else found = pick<Inst<sizeof(ITEM) == 8 ? 14 : sizeof(ITEM) == 16 ? 7 : kP2NWordPer>>(q.p2_targs, scatter);
     if(!found) return no_kernel("p2_scatter_sorted_kernel");
     S2->items[0] = tmp; S2->off[0] = d_goff + q.d0;
     return JFGPU_OK;
@@ -500,6 +526,8 @@ int run_p2(jfgpu_table* t, const FlushPlan& p, const GroupPlan& q, const SegList
   // single pass: destination d of the whole table sits at d * cap2 of a buffer that only holds this group's (shifted base)
   unsigned int* d_gcur2 = (unsigned int*)blk[0]; uint64_t* d_off2 = (uint64_t*)blk[1];
   ITEM* out_v = (ITEM*)blk[2] - (p.share ? (int64_t)q.d0 * (int64_t)p.cap2 : 0);
+  if constexpr(sizeof(ITEM) == 32) return no_kernel("single-pass P2 of 32-byte items");
+  else {
   if(q.p2 == kP2Sort) {
     constexpr int per = sizeof(ITEM) == 4 ? kP2PairPer : sizeof(ITEM) == 8 ? kP2MidPer : kP2WidePer;
     ++t->n_p2_sort;
@@ -520,6 +548,7 @@ int run_p2(jfgpu_table* t, const FlushPlan& p, const GroupPlan& q, const SegList
   // offsets from the group's first destination, items absolute
   S2->items[0] = out_v; S2->off[0] = d_off2 + 2 * q.d0; S2->sh[0] = 1; S2->dense[0] = q.dense;
   return JFGPU_OK;
+  }
 }
 
 // The tile insert of group g behind its P2, with the profile spans that go with the plan: groups sharing a buffer run P2
@@ -612,7 +641,7 @@ template <typename ITEM>
 int part_flush_t(jfgpu_table* t) {
   FlushSizes fs;
   { const int rc = flush_sizes(t, fs); if(rc) return rc; }
-  if constexpr(sizeof(ITEM) != 16) { int rc = refresh_d_dt(t); if(rc) return rc; }
+  if constexpr(sizeof(ITEM) < 16) { int rc = refresh_d_dt(t); if(rc) return rc; }
   const PartFacts f = part_facts(t);
   SegList S1; memset(&S1, 0, sizeof S1);
   S1.n = (uint32_t)t->pending.size();
@@ -639,7 +668,7 @@ int part_flush_t(jfgpu_table* t) {
 
 int part_flush(jfgpu_table* t) {
   if(t->pending.empty()) return JFGPU_OK;
-  const int rc = t->item128 ? part_flush_t<u128>(t) : t->item32 ? part_flush_t<uint32_t>(t) : part_flush_t<uint64_t>(t);
+  const int rc = t->item256 ? part_flush_t<u256>(t) : t->item128 ? part_flush_t<u128>(t) : t->item32 ? part_flush_t<uint32_t>(t) : part_flush_t<uint64_t>(t);
   if(rc) {      // what was pending is lost with the failed flush: the table no longer holds what it was fed, and says so until
     if(t->stream) hipStreamSynchronize(t->stream);      // it is cleared (jfgpu_clear), instead of carrying on with k-mers missing
     t->pending.clear(); t->pending_bytes = 0; t->ws_used = 0;

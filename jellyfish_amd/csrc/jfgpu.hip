@@ -31,6 +31,7 @@
 #include "kernels_wide.hip.hpp"
 #include "kernels_wide_part.hip.hpp"
 #include "kernels_nword.hip.hpp"
+#include "kernels_nword_part.hip.hpp"
 #include "kernels_bloom_query.hip.hpp"
 #include "kernels_parse.hip.hpp"
 #include "kernels_bgzf.hip.hpp"
@@ -99,7 +100,7 @@ struct jfgpu_table {
   uint64_t flushes_plain = 0, flushes_heavy = 0; // tile-kernel instantiation chosen per flush launch (jfgpu_get_counters)
   // which partition kernels ran since the last clear (jfgpu_get_counters 10..15): P2 launches by kind -- loader / storer
   // rings, shared rings, the sort-based single pass, the exact count + scatter -- and P1 launches: ring kernel, any other
-  uint64_t n_p2_roles = 0, n_p2_ring = 0, n_p2_sort = 0, n_p2_exact = 0, n_p1_ring = 0, n_p1_other = 0, n_tile_dense = 0;
+  uint64_t n_p2_roles = 0, n_p2_ring = 0, n_p2_sort = 0, n_p2_exact = 0, n_p1_ring = 0, n_p1_other = 0, n_tile_dense = 0, n_tile_nword = 0;
   // count --bc: the cache of admitted k-mers (kernels_bloom.hip.hpp) -- 0 undecided, 1 on, -1 off; decided from the first
   // filtered batches (host_partition.inl: bloom_cache_decide), dropped when the counter is detached
   DevBuf<uint64_t> d_bcache; int bcache_state = 0; uint64_t mers_seen = 0;
@@ -114,7 +115,7 @@ struct jfgpu_table {
   uint64_t grow_seed = 0;
   // two-word keys (33 <= k <= 64): 128-bit slots, kernels_wide.hip.hpp
   bool wide = false;
-  // keys of three or four words (65 <= k <= 128): 256-bit slots, kernels_nword.hip.hpp (direct path only)
+  // keys of three or four words (65 <= k <= 128): 256-bit slots, kernels_nword.hip.hpp; partitioned path: kernels_nword_part.hip.hpp
   bool nword = false;
   NTable nt{};
   WideTable wt{};
@@ -139,6 +140,7 @@ struct jfgpu_table {
   PartGeom pg{};
   bool item32 = false;
   bool item128 = false;          // two-word keys: 128-bit items (kernels_wide_part.hip.hpp)
+  bool item256 = false;          // keys of three and four words: 256-bit items (kernels_nword_part.hip.hpp)
   bool pristine = true;          // table known all-zero: tile_insert may skip the tile read
   std::vector<PendingBatch> pending;
   uint64_t pending_bytes = 0;
@@ -234,6 +236,7 @@ int check_deferred(jfgpu_table* t, uint64_t* ctr_out = nullptr) {
 }
 
 bool use_partitioned(const jfgpu_table* t, size_t nbytes);
+bool nword_auto_partitioned(const TableGeom& g, size_t nbytes);
 int part_ingest(jfgpu_table* t, const uint8_t* base, int64_t lo, int64_t hi, bool from_keys, uint64_t max_items);
 int part_flush(jfgpu_table* t);
 int table_grow(jfgpu_table* t);
@@ -308,6 +311,10 @@ int launch_count_chunk(jfgpu_table* t, const char* d_bases, size_t n) {
   const uint8_t* base; int64_t lo, hi;
   align_buffer(d_bases, n, base, lo, hi);
   if(t->nword) {
+    if(t->operation == 0 && use_partitioned(t, n)) {      // PRIME / UPDATE passes run on the direct kernel, as for the narrower keys
+      const int rc = part_ingest(t, base, lo, hi, false, n);
+      if(rc >= 0) return rc;        // < 0: no memory for the pending batch -> direct kernel
+    }
     t->pristine = false;
     const int64_t nt = (hi + kTilePos - 1) / kTilePos;
     ProfScope ps(t, 0, n);
@@ -633,12 +640,7 @@ int grow_swap(jfgpu_table* t, GrowNew& N) {
   t->returning = t->g.cnt_bits < 40; t->ovf_failed_need = 0;
   (void)t->d_M2.reset();
   (void)t->d_strag.reset(); (void)t->d_strag_n.reset();     // (the item width may change with the geometry)
-  if(t->nword) {
-    t->nt = N.nn;
-    t->pristine = false;
-    ++t->grow_seed;
-    return check_deferred(t);
-  }
+  if(t->nword) t->nt = N.nn;
   if(t->wide) {
     t->wt = N.nw;
     const int wl = (int)(((size_t)16 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits));
@@ -669,6 +671,8 @@ void refresh_views(jfgpu_table* t) {
 
 bool use_partitioned(const jfgpu_table* t, size_t nbytes) {
   if(!t->part_ok || t->mode == MODE_DIRECT) return false;
+  // keys of three and four words: a table with a filter attached and a shard stay on the direct kernel
+  if(t->nword) return !t->nt.bloom.data && t->g.shard_bits == 0 && (t->mode == MODE_PARTITIONED || nword_auto_partitioned(t->g, nbytes));
   if(t->mode == MODE_PARTITIONED) return true;
   return nbytes >= kPartMinBytes || !t->pending.empty();
 }
@@ -788,7 +792,8 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
     NTable& w = t->nt;
     w.slots = d.slots; w.fwd_tbl = d.fwd_tbl; w.inv_tbl = d.inv_tbl; w.ovf_key = d.ovf_key; w.ovf_cnt = d.ovf_cnt;
     w.ovf_mask = d.ovf_mask; w.counters = d.counters; w.max_probe = d.max_probe;
-    t->part_ok = false; t->mode = MODE_DIRECT;
+    memset(&w.bloom, 0, sizeof w.bloom);
+    part_geom_init(t.get());
     const int nl = (int)(((size_t)32 << kNTileBits) + ((size_t)2 << kNTileBits));
     HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_words_kernel<NTable>, hipFuncAttributeMaxDynamicSharedMemorySize, nl));
     {                                                                          // the routing passes of a shard, world 1 included (route_buffer)
@@ -807,10 +812,8 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
     const int wl = (int)(((size_t)16 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits));
     HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_words_kernel<WideTable>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
   } else part_geom_init(t.get());
-  if(!nword) {
-    if(t->tun.mode == 1) t->mode = MODE_DIRECT;
-    else if(t->tun.mode == 2 && t->part_ok) t->mode = MODE_PARTITIONED;
-  }
+  if(t->tun.mode == 1) t->mode = MODE_DIRECT;
+  else if(t->tun.mode == 2 && t->part_ok) t->mode = MODE_PARTITIONED;
   {
 #define TATTR2(I, R, S, P, H, M, HL) HIP_TRY(hipFuncSetAttribute((const void*)tile_rank_insert_kernel<I, R, S, P, kTileBlock, H, M, HL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_rank_lds(sizeof(S), kMaxTileBits, P)))
 #define TATTR1(I, R, S, P, H, M) TATTR2(I, R, S, P, H, M, true)
@@ -892,6 +895,12 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
     HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wt));
     HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_wide_pipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wt));
     HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_wide_pipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wt));
+    const int np = (int)p1_nword_lds(32), ntl = 32 << kNTileBits;
+    HIP_TRY(hipFuncSetAttribute((const void*)p1_nword_granule_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, np));
+    HIP_TRY(hipFuncSetAttribute((const void*)p1_nword_granule_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, np));
+    HIP_TRY(hipFuncSetAttribute((const void*)p2_scatter_sorted_kernel<u256, kP2NWordPer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2NWordPer * 32));
+    HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_nword_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ntl));
+    HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_nword_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ntl));
   }
   rc = jfgpu_clear(t.get());
   if(rc) { t->stream.sync(); return rc; }      // (drained before the handle goes, like every destroy path)
@@ -941,7 +950,7 @@ int jfgpu_clear(jfgpu_table* t) {
   HIP_TRY(hipStreamSynchronize(t->stream));
   t->pristine = true; t->occ_known = 0; t->fed_since = 0; t->direct_seen = 0; t->occ_bound = 0; t->bigval_bound = 0; t->ovf_failed_need = 0;
   t->flushes_plain = 0; t->flushes_heavy = 0;
-  t->n_p2_roles = t->n_p2_ring = t->n_p2_sort = t->n_p2_exact = t->n_p1_ring = t->n_p1_other = t->n_tile_dense = 0;
+  t->n_p2_roles = t->n_p2_ring = t->n_p2_sort = t->n_p2_exact = t->n_p1_ring = t->n_p1_other = t->n_tile_dense = t->n_tile_nword = 0;
   return JFGPU_OK;
 }
 
@@ -1015,7 +1024,7 @@ static int add_keys_piece(jfgpu_table* t, const uint64_t* d_keys, size_t n, uint
     const int prc = part_ingest(t, (const uint8_t*)d_keys, 0, (int64_t)n, true, n);
     if(prc >= 0) return prc;
   }
-  if(one_word && (d_is_new || val != 1)) { rc = part_flush(t); if(rc) return rc; }   // is_new / set() must see earlier adds
+  if((one_word && (d_is_new || val != 1)) || t->nword) { rc = part_flush(t); if(rc) return rc; }   // is_new / set() must see earlier adds
   if(!t->wide) t->pristine = false;                      // (an add of two-word keys never cleared it: kept so)
   const int grid = grid_for(t, (n + kBlock - 1) / kBlock);
   ProfScope ps(t, 1, n);
@@ -1324,6 +1333,7 @@ int jfgpu_set_growth(jfgpu_table* t, int on) {
 int jfgpu_reserve(jfgpu_table* t, uint64_t input_bytes) {
   int rc = use(t); if(rc) return rc;
   if(!t->part_ok || t->mode == MODE_DIRECT) return JFGPU_OK;
+  if(t->nword && t->mode != MODE_PARTITIONED) return JFGPU_OK;      // (auto: the arena grows with the first batch that takes the path)
   rc = part_flush(t); if(rc) return rc;
   t->reserved_input = input_bytes;
   const uint32_t nb1 = 1u << t->pg.b1, nb2 = 1u << t->pg.b2;
@@ -1335,7 +1345,7 @@ int jfgpu_reserve(jfgpu_table* t, uint64_t input_bytes) {
   const size_t need = 2 * pend + headroom + (n_tiles_of(t) + 1 + nb1) * sizeof(uint64_t) +
                       (size_t)kMaxSeg * (align_up((2 * nb1 + 1) * sizeof(uint64_t), 256) + align_up(nb1 * 16, 256) + 1280) + ((size_t)1 << 20);
   size_t want = need;
-  if(t->item128) {      // 16-byte items: what a whole input would need may exceed the device; the arena is then flushed more than once
+  if(t->item128 || t->item256) {      // 16- and 32-byte items: what a whole input would need may exceed the device; the arena is then flushed more than once
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     const size_t avail = free_b + t->ws_cap > ((size_t)8 << 30) ? free_b + t->ws_cap - ((size_t)8 << 30) : 0;
@@ -1424,7 +1434,7 @@ int jfgpu_get_counters(jfgpu_table* t, uint64_t* out, uint32_t n) {
   rc = read_counters(t, c); if(rc) return rc;
   const uint64_t v[JFGPU_N_COUNTERS] = {c[CTR_FULL], c[CTR_MERS], c[CTR_OVF_FULL], c[CTR_OVF_USED], c[CTR_MISROUTED], c[CTR_DIRECT],
                                         c[CTR_T_ITEMS], c[CTR_T_QUEUED], t->flushes_plain, t->flushes_heavy,
-                                        t->n_p2_roles, t->n_p2_ring, t->n_p2_sort, t->n_p2_exact, t->n_p1_ring, t->n_p1_other, t->n_tile_dense};
+                                        t->n_p2_roles, t->n_p2_ring, t->n_p2_sort, t->n_p2_exact, t->n_p1_ring, t->n_p1_other, t->n_tile_dense, t->n_tile_nword};
   for(uint32_t i = 0; i < n; ++i) out[i] = i < JFGPU_N_COUNTERS ? v[i] : 0;
   return JFGPU_OK;
 }

@@ -10,7 +10,8 @@
 // every word so far equals its own, so the lane that sets the last word matched all the others and the slot holds
 // exactly that lane's key; a lane that meets a foreign word probes on, nobody waits (the reference's per-word "set"
 // bits, offsets_key_value.hpp:28-31, large_hash_array.hpp:542-579).  Tiles are 2048 slots (64 KiB, what the sorted
-// dump sorts in LDS).  Insert path: global atomics only (this range is a correctness feature, not a benchmark).
+// dump sorts in LDS).  Insert paths: the direct kernel here (global atomics), and the partitioned one of
+// kernels_nword_part.hip.hpp (P1n, P2, Tn: the same claim on LDS words).
 #pragma once
 #include "kernels.hip.hpp"
 #include "kernels_bloom.hip.hpp"
@@ -149,12 +150,14 @@ __device__ inline bool bloom_admits_nword(const DevBloom& B, const K256& key) {
 
 struct NSlot { uint64_t lo[3]; uint64_t hi_low; };
 
-__device__ inline NSlot nword_words(const NGeom& N, const K256& key, uint32_t idx0) {
-  const K256 tag = k256_or(k256_shl(k256_from64(idx0), N.g.rem_bits), k256_shr(key, N.g.lsize_g));
+__device__ inline NSlot nword_tag_words(const NGeom& N, const K256& tag) {      // tag = (idx0 << rem_bits) | (key >> lsize_g)
   NSlot s;
   for(uint32_t i = 0; i < 3; ++i) s.lo[i] = (k256_chunk63(tag, i) << 1) | 1ull;
   s.hi_low = N.g.occ_bit | k256_shr(tag, kNLoBits).w[0];
   return s;
+}
+__device__ inline NSlot nword_words(const NGeom& N, const K256& key, uint32_t idx0) {
+  return nword_tag_words(N, k256_or(k256_shl(k256_from64(idx0), N.g.rem_bits), k256_shr(key, N.g.lsize_g)));
 }
 
 __device__ inline K256 nword_slot_key(const NTable& T, const uint64_t* inv_tbl, const uint64_t* slot, uint64_t tile_base) {
@@ -178,14 +181,14 @@ __device__ inline bool nword_addr(const NTable& T, const uint64_t* fwd, const K2
   return false;
 }
 
-// claim-or-increment at the key's home.  Returns true when the key was new (this lane set the last word).
+// claim-or-increment of the slot words `w` in the tile at tile_base, probing from idx0.  Returns true when the key was new
+// (this lane set the last word).  The partitioned path's way out of a full region claims with it too (kernels_nword_part.hip.hpp).
 template <bool RETURNING>
-__device__ inline bool nword_add_at(const NTable& T, const K256& key, const SlotAddr& a, uint64_t cnt) {
+__device__ inline bool nword_claim(const NTable& T, const NSlot& w, uint64_t tile_base, uint32_t idx0, uint64_t cnt) {
   const TableGeom& g = T.N.g;
-  const NSlot w = nword_words(T.N, key, a.idx0);
   const uint64_t add = cnt << (g.tag_bits + 1);
   for(uint32_t p = 0; p <= T.max_probe; ++p) {
-    const uint64_t slot = a.tile_base + probe_slot(a.idx0, p, (uint32_t)g.tile_mask);
+    const uint64_t slot = tile_base + probe_slot(idx0, p, (uint32_t)g.tile_mask);
     unsigned long long* sp = (unsigned long long*)&T.slots[4 * slot];
     const unsigned long long old = atomicCAS(sp + 3, 0ull, (unsigned long long)w.hi_low);
     if(old != 0ull && (old & g.low_mask) != w.hi_low) continue;
@@ -208,6 +211,12 @@ __device__ inline bool nword_add_at(const NTable& T, const K256& key, const Slot
   }
   atomicAdd((unsigned long long*)&T.counters[CTR_FULL], 1ull);
   return false;
+}
+
+// claim-or-increment at the key's home.
+template <bool RETURNING>
+__device__ inline bool nword_add_at(const NTable& T, const K256& key, const SlotAddr& a, uint64_t cnt) {
+  return nword_claim<RETURNING>(T, nword_words(T.N, key, a.idx0), a.tile_base, a.idx0, cnt);
 }
 
 template <bool RETURNING>

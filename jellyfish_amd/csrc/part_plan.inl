@@ -16,16 +16,17 @@ size_t arena_take(size_t& used, size_t cap, size_t bytes) {
 
 struct PartFacts {
   PartGeom pg{};
-  uint32_t item_bytes = 4;       // 4 / 8 / 16
+  uint32_t item_bytes = 4;       // 4 / 8 / 16 / 32
   bool slot32 = false;
   int mode = 0, n_cu = 0, g1 = 0;
   uint64_t n_tiles = 0;
   bool returning = false, wide = false, filter = false;
+  bool nword = false;            // the key class: keys of three and four words (32-byte items); wide: two words (16-byte items); else one
   int filter_kind = 0;           // (a filter of kind 1 changes as it is asked: count --bf-size)
   uint32_t nbytes = 0;
   bool hash_xs = false, canonical = false;
   uint32_t lsize_g = 0, lsize_l = 0, tile_bits = 0;
-  uint32_t tag_bits = 0;         // where an item's P2 sub-bucket starts (two-word keys: tag_full)
+  uint32_t tag_bits = 0;         // where an item's P2 sub-bucket starts (keys of two and more words: tag_full)
   double items_per_byte = 0;
   size_t ws_cap = 0, ws_used = 0;
   uint64_t reserved_input = 0;
@@ -48,7 +49,7 @@ template <class F> void with_flags(bool a, bool b, F&& f) { with_flags(a, [&](au
 
 // ---- P1: one batch ---------------------------------------------------------------------------------------------------
 enum FlushWhy { kFlushNo = 0, kFlushSegments, kFlushWideShare, kFlushEven, kFlushArenaFull };
-enum P1Kind { kP1Ring, kP1KeysGranule, kP1Granule64, kP1WideGranule, kP1ExactSorted, kP1ExactKeysSorted, kP1ExactPlain };
+enum P1Kind { kP1Ring, kP1KeysGranule, kP1Granule64, kP1WideGranule, kP1ExactSorted, kP1ExactKeysSorted, kP1ExactPlain, kP1NWordGranule };
 struct PendingSum { size_t n = 0; uint64_t input_bytes = 0; };     // the pending batches: how many, made from how many sequence bytes
 struct P1Plan {
   int flush = kFlushNo;          // apply what is pending first, and why (kFlushSegments: then ask again)
@@ -56,7 +57,7 @@ struct P1Plan {
   uint32_t gran_cap = 0;         // single-pass P1: items per bucket region; 0: the exact two-pass scheme
   size_t bytes = 0, arena = 0;   // of the batch's items; of all its arena blocks (the arena grows to this when smaller)
   int kind = kP1ExactPlain;
-  TArgs targs{};                 // kP1Ring <BLOOM, N, CN>, kP1KeysGranule <RT, N>, kP1Granule64 <RT, BL, N>, kP1WideGranule <RT, BL, XS>,
+  TArgs targs{};                 // kP1Ring <BLOOM, N, CN>, kP1KeysGranule <RT, N>, kP1Granule64 <RT, BL, N>, kP1WideGranule <RT, BL, XS>, kP1NWordGranule <RT>,
                                  // kP1ExactSorted <RT, BL, N>, kP1ExactKeysSorted <N>, kP1ExactPlain p1_kernel's <SC = 1, FK, RT, BL, N>
   TArgs count_targs{};           // the exact kinds' first pass: p1_kernel's <SC = 0, FK, RT, BL, N>
   size_t lds = 0;
@@ -67,8 +68,8 @@ struct P1Plan {
 // two-pass scheme.  Every block may strand part of one reservation per bucket, so small batches would be
 // mostly holes: auto mode wants the mean bucket load to be at least 4x that.
 uint32_t granule_cap(const PartFacts& f, bool from_keys, uint64_t max_items) {
-  const bool wide = f.item_bytes == 16;
-  if(wide) { if(f.pg.b1 > 10 || !f.g1) return 0; }                      // the only P1 two-word keys have
+  const bool wide = f.item_bytes >= 16;                                   // (keys of two words, and of three and four)
+  if(wide) { if(f.pg.b1 > 10 || !f.g1) return 0; }                      // the only P1 these keys have
   else if(f.pg.b2 == 0 || f.pg.b1 > 10 || f.tun.p1_single == 0 || !f.g1) return 0;
   else if(f.item_bytes == 8 && from_keys) return 0;                       // 64-bit items: single-pass from sequence only
   const uint64_t nb = 1ull << f.pg.b1, strand = (uint64_t)f.g1 * kGran;
@@ -94,9 +95,10 @@ int compiled_nbytes(uint32_t nbytes, uint32_t from) { return nbytes >= from && n
 P1Plan p1_plan(const PartFacts& f, bool from_keys, uint64_t max_items, int64_t lo, int64_t hi, PendingSum pend) {
   P1Plan p;
   if(pend.n >= (size_t)kMaxSeg) { p.flush = kFlushSegments; return p; }
-  const bool wide = f.item_bytes == 16, item32 = f.item_bytes == 4;
+  const bool wide = f.item_bytes >= 16, item32 = f.item_bytes == 4;
   const uint32_t nb = 1u << f.pg.b1, gcap = p.gran_cap = granule_cap(f, from_keys, max_items);
-  if(wide && (!gcap || from_keys)) { p.refuse = true; return p; }       // two-word keys: single-pass P1 from sequence or the direct kernel
+  if(wide && (!gcap || from_keys)) { p.refuse = true; return p; }       // keys of two and more words: single-pass P1 from sequence or the direct kernel
+  if(f.nword && f.filter) { p.refuse = true; return p; }                // ... and of three and four words: no filtered P1
   // a one-pass Bloom filter (count --bf-size) changes as it is asked: the two-pass P1 would ask it twice per k-mer
   if(!gcap && !from_keys && f.filter && f.filter_kind == 1) { p.refuse = true; return p; }
   p.bytes = gcap ? (size_t)nb * gcap * f.item_bytes : max_items * f.item_bytes;
@@ -118,7 +120,9 @@ P1Plan p1_plan(const PartFacts& f, bool from_keys, uint64_t max_items, int64_t l
   if(!p.flush && pend.n && f.ws_used + need > f.ws_cap) p.flush = kFlushArenaFull;      // apply what is pending, arena is empty again
   const int rt = f.returning, bl = f.filter && !from_keys;     // the filter applies to the sequence feed only
   p.grid = (uint32_t)f.g1;
-  if(gcap && wide) {
+  if(gcap && f.nword) {
+    p.kind = kP1NWordGranule; p.targs = {rt}; p.lds = p1_nword_lds(f.nbytes);
+  } else if(gcap && wide) {
     const int xs = f.hash_xs && !bl;
     p.kind = kP1WideGranule; p.targs = {rt, bl, xs}; p.lds = (size_t)kWideChunk * 18 + (size_t)f.nbytes * 2048;
   } else if(gcap && !item32) {
@@ -218,7 +222,8 @@ FlushPlan flush_plan(const PartFacts& f, uint64_t total, const uint64_t* bucket_
   // what is pending, the P1 buckets go through P2 and the tile insert in groups sharing one buffer.
   // (The single-pass kernel places one destination per thread (GranuleLds: kGranMaxB = 1024); from 2^34 slots on b2 is 11,
   // and what is not routed to pairs takes the exact scheme, whose kernels go to kMaxBuckets = 2048 destinations)
-  const bool single_ok = f.tun.p2_single && (item >= 8 || p.pair) && f.tun.flush_groups <= 1 && (1u << p.b2e) <= (uint32_t)kGranMaxB;
+  // (32-byte items have the exact scheme only)
+  const bool single_ok = f.tun.p2_single && ((item >= 8 && item <= 16) || p.pair) && f.tun.flush_groups <= 1 && (1u << p.b2e) <= (uint32_t)kGranMaxB;
   uint32_t single_groups = 1;
   if(single_ok) {
     // what a destination's region may lose to reservations nobody fills: one granule per block -- two with the ring kernel,
@@ -301,8 +306,8 @@ GroupPlan group_plan(const PartFacts& f, const FlushPlan& p, uint32_t g, const u
   q.d0 = (uint64_t)q.b0 << p.b2e; q.nd = (uint64_t)q.nbk << p.b2e;
   q.grid_y = q.nbk;
   if(!p.cap2) {
-    // 8- and 16-byte items: chunks of 112 KiB (longer runs per destination)
-    const int per_thread = p.pair ? kP2PairPer : item == 4 ? 16 : item == 8 ? 14 : 7;
+    // 8- and 16-byte items: chunks of 112 KiB (longer runs per destination); 32-byte items: 96 KiB
+    const int per_thread = p.pair ? kP2PairPer : item == 4 ? 16 : item == 8 ? 14 : item == 16 ? 7 : kP2NWordPer;
     q.p2 = kP2Exact; q.p2_targs = {per_thread}; q.grid_x = kG2Exact; q.lds = (size_t)kPBlock * per_thread * item;
   } else if(item == 4 && p2_rings_fit(f, p.b2e, q.nbk) && (all_granule || p2_rings_roles(f, p.b2e, q.nbk))) {
     const bool roles = p2_rings_roles(f, p.b2e, q.nbk);
@@ -315,7 +320,7 @@ GroupPlan group_plan(const PartFacts& f, const FlushPlan& p, uint32_t g, const u
   }
   q.tile0 = (uint64_t)q.b0 << f.pg.b2;
   q.ntile = (uint32_t)q.nd;                               // units of the tile kernel: tiles, or pairs of tiles
-  q.sample = f.wide ? 0 : tile_sample_units(f, q.ntile, 1);
+  q.sample = f.wide || f.nword ? 0 : tile_sample_units(f, q.ntile, 1);
   q.tile_dense = q.dense && item == 4 && p.pair && f.tun.tile_adapt != 2;
   return q;
 }

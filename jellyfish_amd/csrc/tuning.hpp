@@ -55,7 +55,7 @@ constexpr uint64_t kDumpDeviceMinRecords = 1ull << 23;
 
 struct Tuning {
   // ---- tables (jfgpu_create)
-  int mode = 0;                  // JFGPU_MODE=direct|partitioned            0: not set, 1 direct, 2 partitioned
+  int mode = 0;                  // JFGPU_MODE=direct|partitioned (or 1|2)   0: not set, 1 direct, 2 partitioned
   bool slot64 = false;           // JFGPU_SLOT64=1         never use 32-bit slots (A/B against the 4-byte layout)
   int p1_single = -1;            // JFGPU_P1_SINGLE        single-pass P1: -1 auto, 0 never, 1 whenever the geometry allows
   double p1_slack = 0.03;        // JFGPU_P1_SLACK         head-room of a P1 bucket region over the mean (negative: forces the exhausted path)
@@ -96,7 +96,7 @@ struct Tuning {
   static Tuning from_env() {
     Tuning u;
     auto str = [](const char* name) -> const char* { const char* e = getenv(name); return e && *e ? e : nullptr; };
-    if(const char* e = str("JFGPU_MODE")) u.mode = !strcmp(e, "direct") ? 1 : !strcmp(e, "partitioned") ? 2 : 0;
+    if(const char* e = str("JFGPU_MODE")) u.mode = !strcmp(e, "direct") || !strcmp(e, "1") ? 1 : !strcmp(e, "partitioned") || !strcmp(e, "2") ? 2 : 0;
     if(const char* e = str("JFGPU_SLOT64")) u.slot64 = atoi(e) != 0;
     if(const char* e = str("JFGPU_MATRIX")) u.matrix = (!strcmp(e, "xs") || !strcmp(e, "xorshift")) ? 1 : (!strcmp(e, "reference") || !strcmp(e, "ref")) ? 2 : 0;
     if(const char* e = str("JFGPU_P1_SINGLE")) u.p1_single = atoi(e) ? 1 : 0;

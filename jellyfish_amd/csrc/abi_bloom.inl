@@ -110,31 +110,6 @@ static int bloom_create(const jfgpu_bloom_params* p, jfgpu_bloom** out, uint32_t
   b->tun = Tuning::from_env();
   if(b->tun.bloom_mode == 1) b->mode = 1;
   else if(b->tun.bloom_mode == 2 && b->part_ok) b->mode = 2;
-  {
-    const int pl = (int)((size_t)kBloomChunk * 6 + (size_t)2 * 8 * 2048);
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_granule_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, pl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_granule_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, pl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_granule_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, pl));
-    {
-      const int pl2 = (int)((size_t)kPBlock * 5 * 6 + (size_t)8 * 512);
-      HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_granule2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, pl2));
-      HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_granule2_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, pl2));
-      HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_granule2_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, pl2));
-    }
-    {
-      const int plr = (int)((size_t)512 * kBloomRingBytes + kBloomRingBytes + (size_t)8 * 512);
-      HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_ring_kernel<0, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, plr));
-      HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_ring_kernel<6, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, plr));
-      HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_ring_kernel<8, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, plr));
-      HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_ring_kernel<0, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, plr));
-      HIP_TRY(hipFuncSetAttribute((const void*)p1_bloom_ring_kernel<8, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, plr));
-    }
-    HIP_TRY(hipFuncSetAttribute((const void*)bloom_segment_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << kBloomSegBits));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_scatter_sorted_kernel<uint32_t, kP2PairPer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2PairPer * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<uint32_t, BloomDirect, kP2PairPer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2PairPer * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_kernel<BloomRingDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_roles_kernel<uint32_t, 2, BloomRingDirect, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
-  }
   rc = b->d_data.alloc(b->alloc_bytes); if(rc) return rc;
   HIP_TRY(hipMemsetAsync(b->d_data, 0, b->alloc_bytes, b->stream));
   if((rc = b->d_t1.alloc(t1.size())) || (rc = b->d_t2.alloc(t2.size()))) return rc;
@@ -366,7 +341,7 @@ int jfgpu_attach_bloom(jfgpu_table* t, jfgpu_bloom* b) {   // count --bc (count_
   if(!b) { memset(&t->dt.bloom, 0, sizeof t->dt.bloom); memset(&t->wt.bloom, 0, sizeof t->wt.bloom); memset(&t->nt.bloom, 0, sizeof t->nt.bloom); return JFGPU_OK; }
   rc = bloom_flush(b); if(rc) return rc;
   HIP_TRY(hipStreamSynchronize(b->stream));
-  if(t->nword) t->nt.bloom = b->view(); else if(t->wide) t->wt.bloom = b->view(); else t->dt.bloom = b->view();
+  table_bloom(t) = b->view();
   { uint64_t c[CTR_COUNT]; rc = read_counters(t, c); if(rc) return rc; t->mers_seen = c[CTR_MERS]; }
   if(b->kind != 0 || t->wide || t->nword || t->tun.bloom_cache == 0) t->bcache_state = -1;      // (a one-pass filter changes as it is asked: nothing to remember)
   else if(t->tun.bloom_cache == 1) { rc = bloom_cache_enable(t); if(rc) return rc; }

@@ -215,10 +215,10 @@ uint32_t items_cap_wanted(const jfgpu_comm* c, const jfgpu_comm::Rank& R, size_t
 // Keys of three and four words: the routing kernels take no filter at all (KeyOps<NTable> has no admits), so a table with one
 // attached is refused here rather than routed unfiltered.
 int comm_filter_ok(const jfgpu_table* t) {
-  if(t->nword && t->nt.bloom.data)
+  const DevBloom& f = table_bloom(t);
+  if(t->nword && f.data)
     return fail(JFGPU_E_UNSUPPORTED, "--bc and --bf-size over shards are not built for mer length " + std::to_string(t->g.k) + " (the routing kernels of keys of more than two words take no filter)");
-  if(t->wide && t->wt.bloom.data && t->wt.bloom.kind != 0) return fail(JFGPU_E_UNSUPPORTED, "--bf-size with --gpus: a one-pass filter cannot be sharded by input");
-  if(!t->wide && t->dt.bloom.data && t->dt.bloom.kind != 0) return fail(JFGPU_E_UNSUPPORTED, "--bf-size with --gpus: a one-pass filter cannot be sharded by input");
+  if(f.data && f.kind != 0) return fail(JFGPU_E_UNSUPPORTED, "--bf-size with --gpus: a one-pass filter cannot be sharded by input");
   return JFGPU_OK;
 }
 
@@ -281,13 +281,15 @@ int comm_route_items_enqueue(jfgpu_comm* c, jfgpu_comm::Rank& R, const char* d_b
     ProfScope ps(t, 2, n);
     unsigned int* gcur = R.d_gcur;
     // the count path's ring P1 (kernels_p1ring.hip.hpp) over the global geometry; what it cannot store goes on the list
-#define PR(N, CN) hipLaunchKernelGGL((p1_ring_kernel<uint32_t, false, N, CN, RouteListDirect>), grid, block, lds, t->stream, gv, rd, pg, base, lo, hi, cap, gcur, tot, items, t->d_strag, t->d_strag_n)
+    int lrc = JFGPU_OK;
+#define PR(N, CN) lrc = launch_lds(p1_ring_kernel<uint32_t, false, N, CN, RouteListDirect>, grid, block, lds, t->stream, gv, rd, pg, base, lo, hi, cap, gcur, tot, items, t->d_strag, t->d_strag_n)
     if(t->dt.bloom.data)      // count --bc: the sender asks its copy of the Bloom counter (read-only: the same answer on every rank)
-      hipLaunchKernelGGL((p1_ring_kernel<uint32_t, true, 0, 2, RouteListDirect>), grid, block, lds, t->stream, gv, rd, pg, base, lo, hi, cap, gcur, tot, items, t->d_strag, t->d_strag_n);
+      lrc = launch_lds(p1_ring_kernel<uint32_t, true, 0, 2, RouteListDirect>, grid, block, lds, t->stream, gv, rd, pg, base, lo, hi, cap, gcur, tot, items, t->d_strag, t->d_strag_n);
     else if(t->g.hash_xs && gv.g.lsize_g > 32 && gv.g.lsize_g < 64 && gv.g.lsize_g - pg.b1 < 32) { if(t->g.canonical) PR(kHashXS, 1); else PR(kHashXS, 0); }
     else if(t->g.hash_xs) PR(kHashXSLow, 2);
     else if(t->g.nbytes == 6) { if(t->g.canonical) PR(6, 1); else PR(6, 0); } else PR(0, 2);
 #undef PR
+    if(lrc) return lrc;
     hipLaunchKernelGGL((p1_stragglers_kernel<uint32_t, RouteListDirect>), dim3(t->n_cu), dim3(256), 0, t->stream, rd, (unsigned long long*)nullptr, (const uint64_t*)t->d_strag,
                        (const uint32_t*)t->d_strag_n, (uint32_t)t->n_cu, cap, gcur, tot, items, kStragPerBlock);
   }
@@ -386,7 +388,8 @@ int comm_insert_prev_items(jfgpu_comm* c, jfgpu_comm::Rank& R, int rank) {
     unsigned long long* tot_v = b.tot - dshift;
     unsigned long long* arrived = R.d_arrived;
     // (fan-out 2^sb <= 16: the packed-counter ranking of p2_granule_kernel, with 1, 2 or 4 words of four destinations)
-#define SPLIT(RT, SW) hipLaunchKernelGGL((p2_granule_kernel<uint32_t, TableDirect<RT>, kP2PairPer, SW>), grid, block, lds, t->stream, \
+    int lrc = JFGPU_OK;
+#define SPLIT(RT, SW) lrc = launch_lds(p2_granule_kernel<uint32_t, TableDirect<RT>, kP2PairPer, SW>, grid, block, lds, t->stream, \
                         TableDirect<RT>{t->d_dt, pd, (unsigned long long*)&t->dt.counters[CTR_DIRECT]}, sb, split_at, S, cap2, gc_v, gs_v, out_v, (uint32_t)first, tot_v, L.nbc - 1)
     if(sb > 4) return fail(JFGPU_E_UNSUPPORTED, "item exchange: more than 16 fine buckets per coarse bucket");
     if(wave_split) {
@@ -401,6 +404,7 @@ int comm_insert_prev_items(jfgpu_comm* c, jfgpu_comm::Rank& R, int rank) {
     else if(t->returning) { if(sb <= 2) SPLIT(true, 1); else if(sb == 3) SPLIT(true, 2); else SPLIT(true, 4); }
     else             { if(sb <= 2) SPLIT(false, 1); else if(sb == 3) SPLIT(false, 2); else SPLIT(false, 4); }
 #undef SPLIT
+    if(lrc) return lrc;
     hipLaunchKernelGGL(granule_finish_kernel, dim3(4), dim3(256), 0, t->stream, gcur, cap2, nb, b.off);
     hipLaunchKernelGGL(comm_count_arrived_kernel, dim3(1), dim3(256), 0, t->stream, b.tot, nb, t->dt.counters, arrived);
     for(int p = 0; p < W; ++p) {
@@ -778,7 +782,7 @@ int comm_grow(jfgpu_comm* c) {
     unsigned long long* d_cnt = R.d_cnt;
     HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * W, t->stream));
     with_view(t, N[q], [&](const auto& old, const auto& neu) {
-      hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, old, neu, have_ovf, 0, (uint32_t)kw, d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
+      hipLaunchKernelGGL(reshard_kernel<std::decay_t<decltype(neu)>>, grid, block, 0, t->stream, old, neu, have_ovf, 0, (uint32_t)kw, d_cnt, (uint64_t*)nullptr, (uint64_t*)nullptr);
     });
     std::vector<unsigned long long> h(W);
     HIP_TRY(hipMemcpyAsync(h.data(), d_cnt, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost, t->stream));
@@ -797,7 +801,7 @@ int comm_grow(jfgpu_comm* c) {
     HIP_TRY(hipMemcpyAsync(d_cnt, h.data(), sizeof(unsigned long long) * W, hipMemcpyHostToDevice, t->stream));   // cursors = offsets
     uint64_t *keys_out = R.send[0], *cnts_out = R.send[1];
     with_view(t, N[q], [&](const auto& old, const auto& neu) {
-      hipLaunchKernelGGL(reshard_kernel, grid, block, 0, t->stream, old, neu, have_ovf, 1, (uint32_t)kw, d_cnt, keys_out, cnts_out);
+      hipLaunchKernelGGL(reshard_kernel<std::decay_t<decltype(neu)>>, grid, block, 0, t->stream, old, neu, have_ovf, 1, (uint32_t)kw, d_cnt, keys_out, cnts_out);
     });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(t->stream));
@@ -834,7 +838,7 @@ int comm_grow(jfgpu_comm* c) {
     }
     const uint64_t *keys_in = R.recv[0], *cnts_in = R.recv[1];
     if(n) with_view(t, N[q], [&](const auto&, const auto& neu) {
-      hipLaunchKernelGGL(add_pairs_kernel, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, neu, keys_in, cnts_in, n, t->key_words);
+      hipLaunchKernelGGL(add_pairs_kernel<std::decay_t<decltype(neu)>>, dim3(grid_for(t, n / kBlock + 1)), dim3(kBlock), 0, t->stream, neu, keys_in, cnts_in, n, t->key_words);
     });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(R.consumed[0], t->stream));

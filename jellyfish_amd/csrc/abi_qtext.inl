@@ -33,15 +33,15 @@ int qtext_grow_tiles(jfgpu_qtext* x, size_t nb) {
 
 // The three launches for n > 0 positions, on s_k; the totals go to d_totals[2 * slot ..].  qtext_write_kernel writes nothing
 // when the text is longer than cap_bytes.  The tile arrays hold (n + 255) / 256 entries (qtext_grow_tiles).
-void qtext_launch(jfgpu_qtext* x, const uint8_t* d_bases, uint64_t n, const uint64_t* d_vals, const uint8_t* d_flags, uint8_t* d_text, uint64_t cap_bytes, int slot) {
+int qtext_launch(jfgpu_qtext* x, const uint8_t* d_bases, uint64_t n, const uint64_t* d_vals, const uint8_t* d_flags, uint8_t* d_text, uint64_t cap_bytes, int slot) {
   const uint32_t nb = (uint32_t)((n + kTextBlock - 1) / kTextBlock);
   const uint32_t lds = qtext_lds_in(x->job.k) + text_lds_out(x->job.line_max);
   const hipStream_t s_k = x->pipe.s_k;
   hipLaunchKernelGGL(qtext_len_kernel, dim3(nb), dim3(kTextBlock), 0, s_k, x->job, n, d_vals, d_flags, x->d_tbytes.get(), x->d_tkept.get());
   hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(kTextBlock), 0, s_k, (const uint32_t*)x->d_tbytes, (const uint32_t*)x->d_tkept, nb, x->d_toff.get(),
                      x->d_totals + 2 * slot);
-  hipLaunchKernelGGL(qtext_write_kernel, dim3(nb), dim3(kTextBlock), lds, s_k, x->job, d_bases, n, d_vals, d_flags, (const uint64_t*)x->d_toff,
-                     (const uint64_t*)(x->d_totals + 2 * slot), cap_bytes, d_text);
+  return launch_lds(qtext_write_kernel, dim3(nb), dim3(kTextBlock), lds, s_k, x->job, d_bases, n, d_vals, d_flags, (const uint64_t*)x->d_toff,
+                    (const uint64_t*)(x->d_totals + 2 * slot), cap_bytes, d_text);
 }
 
 constexpr uint64_t kQTextMaxPositions = (uint64_t)1 << 31;   // of one piece / one format_dev call: tiles are a 32-bit grid
@@ -101,7 +101,7 @@ int qtext_run(jfgpu_qtext* x, hipStream_t qs, const char* bases, size_t n, jfgpu
       if(e == hipSuccess) e = hipStreamWaitEvent(P.s_k, x->asked[slot], 0);
       if(e != hipSuccess) return drain(fail(JFGPU_E_HIP, hipGetErrorString(e)));
     }
-    qtext_launch(x, S.d_raw, len, x->d_vals[slot], x->d_flags[slot], S.d_out, len * line_max, slot);
+    rc = qtext_launch(x, S.d_raw, len, x->d_vals[slot], x->d_flags[slot], S.d_out, len * line_max, slot); if(rc) return drain(rc);
     if((rc = P.kernels_end(slot)) || (rc = P.status(slot, 0, x->d_totals + 2 * slot, 2 * sizeof(uint64_t))) || (rc = P.done(slot))) return drain(rc);
     x->counts[0] += 1; x->counts[1] += i ? len - (k - 1) : len;
     // ---- the piece before this one: download and sink while this one is looked up and formatted
@@ -167,7 +167,7 @@ int jfgpu_qtext_format_dev(jfgpu_qtext* x, const char* d_bases, size_t n, const 
   if(n > kQTextMaxPositions) return fail(JFGPU_E_UNSUPPORTED, "query text: at most 2^31 positions a call");
   HIP_TRY(hipStreamSynchronize(x->pipe.s_k));
   rc = qtext_grow_tiles(x, (size_t)((n + kTextBlock - 1) / kTextBlock)); if(rc) return rc;
-  qtext_launch(x, (const uint8_t*)d_bases, n, d_vals, d_flags, (uint8_t*)d_text, capacity_bytes, 0);
+  rc = qtext_launch(x, (const uint8_t*)d_bases, n, d_vals, d_flags, (uint8_t*)d_text, capacity_bytes, 0); if(rc) return rc;
   HIP_TRY(hipGetLastError());
   uint64_t tot[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(tot, x->d_totals, sizeof tot, hipMemcpyDeviceToHost, x->pipe.s_k));

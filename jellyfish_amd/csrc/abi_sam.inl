@@ -11,7 +11,6 @@ struct BgzfState {
   DevBuf<BamSeg> d_seg;
   DevBuf<uint64_t> d_want, d_rec_off, d_out_off, d_rec_start, d_rec_out;
   DevBuf<BamTotals> d_tot;
-  bool lds_set = false;
 };
 jfgpu_parser::jfgpu_parser() = default;
 jfgpu_parser::~jfgpu_parser() = default;
@@ -106,13 +105,13 @@ int jfgpu_parser_inflate_uploaded(jfgpu_parser* p, int which, const jfgpu_bgzf_b
   rc = stream_reserve(p, w, b.stream_len, b.stream_len + total + 64); if(rc) return rc;
   if(n_blocks) {
     rc = b.d_blocks.reserve(n_blocks); if(rc) return rc;
-    if(!b.lds_set) { HIP_TRY(hipFuncSetAttribute((const void*)bgzf_inflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kInfLds)); b.lds_set = true; }
     HIP_TRY(hipStreamWaitEvent(p->stream, p->up_done[which], 0));
     HIP_TRY(hipMemcpyAsync(b.d_blocks, blocks, n_blocks * sizeof(jfgpu_bgzf_block), hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipMemsetAsync(b.d_err, 0xFF, sizeof(unsigned long long), p->stream));
     HIP_TRY(hipEventRecord(p->ev_a, p->stream));
-    hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)n_blocks), dim3(64), kInfLds, p->stream, (const uint8_t*)p->d_up[which], b.d_blocks,
-                       b.d_stream[w] + b.stream_len, b.d_err);
+    rc = launch_lds(bgzf_inflate_kernel, dim3((unsigned)n_blocks), dim3(64), kInfLds, p->stream, (const uint8_t*)p->d_up[which], b.d_blocks,
+                    b.d_stream[w] + b.stream_len, b.d_err);
+    if(rc) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(p->ev_b, p->stream));
     unsigned long long err = 0;

@@ -30,15 +30,16 @@ int text_grow_tiles(jfgpu_text* x, size_t nb) {
 
 // The three launches for n > 0 records at d_rec, on s_k; the totals go to d_totals[2 * slot ..].  text_write_kernel writes
 // nothing when the text is longer than cap_bytes.  The tile arrays hold (n + 255) / 256 entries (text_grow_tiles).
-void text_launch(jfgpu_text* x, const uint8_t* d_rec, uint64_t n, uint8_t* d_text, uint64_t cap_bytes, int slot) {
+int text_launch(jfgpu_text* x, const uint8_t* d_rec, uint64_t n, uint8_t* d_text, uint64_t cap_bytes, int slot) {
   const uint32_t nb = (uint32_t)((n + kTextBlock - 1) / kTextBlock);
   const uint32_t lds_raw = text_lds_raw(x->job.rb), lds_out = text_lds_out(x->job.line_max);
   const hipStream_t s_k = x->pipe.s_k;
-  hipLaunchKernelGGL(text_len_kernel, dim3(nb), dim3(kTextBlock), lds_raw, s_k, x->job, d_rec, n, x->d_tbytes.get(), x->d_tkept.get());
+  int rc = launch_lds(text_len_kernel, dim3(nb), dim3(kTextBlock), lds_raw, s_k, x->job, d_rec, n, x->d_tbytes.get(), x->d_tkept.get());
+  if(rc) return rc;
   hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(kTextBlock), 0, s_k, (const uint32_t*)x->d_tbytes, (const uint32_t*)x->d_tkept, nb, x->d_toff.get(),
                      x->d_totals + 2 * slot);
-  hipLaunchKernelGGL(text_write_kernel, dim3(nb), dim3(kTextBlock), lds_raw + lds_out, s_k, x->job, d_rec, n, (const uint64_t*)x->d_toff,
-                     (const uint64_t*)(x->d_totals + 2 * slot), cap_bytes, d_text);
+  return launch_lds(text_write_kernel, dim3(nb), dim3(kTextBlock), lds_raw + lds_out, s_k, x->job, d_rec, n, (const uint64_t*)x->d_toff,
+                    (const uint64_t*)(x->d_totals + 2 * slot), cap_bytes, d_text);
 }
 
 constexpr uint64_t kTextMaxRecords = (uint64_t)1 << 31;      // of one window / one format_dev call: tiles are a 32-bit grid
@@ -131,7 +132,7 @@ int jfgpu_text_run(jfgpu_text* x, const void* body, uint64_t n_records, jfgpu_te
     rc = P.upload(slot, (size_t)n * rb, t0); if(rc) return rc;
     // ---- kernels
     rc = P.kernels_begin(slot); if(rc) return rc;
-    text_launch(x, S.d_raw, n, S.d_out, n * line_max, slot);
+    rc = text_launch(x, S.d_raw, n, S.d_out, n * line_max, slot); if(rc) return rc;
     if((rc = P.kernels_end(slot)) || (rc = P.status(slot, 0, x->d_totals + 2 * slot, 2 * sizeof(uint64_t))) || (rc = P.done(slot))) return rc;
     x->counts[0] += 1; x->counts[1] += n;
     // ---- the window before this one: download and sink while this one's kernels run
@@ -153,7 +154,7 @@ int jfgpu_text_format_dev(jfgpu_text* x, const void* d_records, uint64_t n_recor
   if(n_records > kTextMaxRecords) return fail(JFGPU_E_UNSUPPORTED, "text: at most 2^31 records a call");
   HIP_TRY(hipStreamSynchronize(x->pipe.s_k));
   rc = text_grow_tiles(x, (size_t)((n_records + kTextBlock - 1) / kTextBlock)); if(rc) return rc;
-  text_launch(x, (const uint8_t*)d_records, n_records, (uint8_t*)d_text, capacity_bytes, 0);
+  rc = text_launch(x, (const uint8_t*)d_records, n_records, (uint8_t*)d_text, capacity_bytes, 0); if(rc) return rc;
   HIP_TRY(hipGetLastError());
   uint64_t tot[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(tot, x->d_totals, sizeof tot, hipMemcpyDeviceToHost, x->pipe.s_k));
@@ -201,7 +202,7 @@ int jfgpu_dump_next_text(jfgpu_table* t, jfgpu_text* x, char* out, uint64_t capa
   hipError_t e = hipStreamSynchronize(t->stream);                  // the chunk is in d_dump
   uint64_t tot[2] = {0, 0};
   if(e == hipSuccess) {
-    text_launch(x, t->d_dump, nrec, x->pipe.slot[0].d_out, nrec * x->job.line_max, 0);
+    rc = text_launch(x, t->d_dump, nrec, x->pipe.slot[0].d_out, nrec * x->job.line_max, 0); if(rc) return undo(rc);
     e = hipGetLastError();
   }
   if(e == hipSuccess) e = hipMemcpyAsync(tot, x->d_totals, sizeof tot, hipMemcpyDeviceToHost, x->pipe.s_k);

@@ -157,15 +157,16 @@ int bloom_ingest(jfgpu_bloom* b, const uint8_t* base, int64_t lo, int64_t hi) {
     const int64_t plo = at & 15, phi = plo + (int64_t)piece;
     {
       BloomProf ps(b, BS_P1, piece);
-#define PB(N) hipLaunchKernelGGL(p1_bloom_granule_kernel<N>, dim3(b->g1), dim3(kPBlock), lds, b->stream, b->view(), b->bp, b->g, pbase, plo, phi, cap, gcur, p.tot, p.items, b->d_mers)
-#define PB2(N) hipLaunchKernelGGL(p1_bloom_granule2_kernel<N>, dim3(b->g1), dim3(kPBlock), (size_t)kPBlock * 5 * 6 + (size_t)b->g.nbytes * 512, b->stream, \
-                                  b->view(), b->bp, b->g, pbase, plo, phi, cap, gcur, p.tot, p.items, b->d_mers)
-#define PBR(N, PER) hipLaunchKernelGGL((p1_bloom_ring_kernel<N, PER>), dim3(b->n_cu), dim3(kPBlock), (size_t)nb * kBloomRingBytes + kBloomRingBytes + (size_t)b->g.nbytes * 512, b->stream, \
-                                       b->view(), b->bp, b->g, rd, pbase, plo, phi, cap, gcur, p.tot, p.items, b->d_mers, b->d_strag1, b->d_strag1_n)
+#define PB(N) rc = launch_lds(p1_bloom_granule_kernel<N>, dim3(b->g1), dim3(kPBlock), lds, b->stream, b->view(), b->bp, b->g, pbase, plo, phi, cap, gcur, p.tot, p.items, b->d_mers)
+#define PB2(N) rc = launch_lds(p1_bloom_granule2_kernel<N>, dim3(b->g1), dim3(kPBlock), (size_t)kPBlock * 5 * 6 + (size_t)b->g.nbytes * 512, b->stream, \
+                               b->view(), b->bp, b->g, pbase, plo, phi, cap, gcur, p.tot, p.items, b->d_mers)
+#define PBR(N, PER) rc = launch_lds(p1_bloom_ring_kernel<N, PER>, dim3(b->n_cu), dim3(kPBlock), (size_t)nb * kBloomRingBytes + kBloomRingBytes + (size_t)b->g.nbytes * 512, b->stream, \
+                                    b->view(), b->bp, b->g, rd, pbase, plo, phi, cap, gcur, p.tot, p.items, b->d_mers, b->d_strag1, b->d_strag1_n)
       if(b->p1_ring_per) {
         const BloomP1RingDirect rd{b->view().data, b->bp.b2};
         if(b->p1_ring_per == 10) { if(b->g.nbytes == 8) PBR(8, 10); else if(b->g.nbytes == 6) PBR(6, 10); else PBR(0, 10); }
         else { if(b->g.nbytes == 8) PBR(8, 5); else PBR(0, 5); }
+        if(rc) return rc;
         hipLaunchKernelGGL((p1_stragglers_kernel<uint32_t, BloomP1RingDirect>), dim3(b->n_cu), dim3(256), 0, b->stream, rd, (unsigned long long*)nullptr, (const uint64_t*)b->d_strag1,
                            (const uint32_t*)b->d_strag1_n, (uint32_t)b->n_cu, cap, gcur, p.tot, p.items);
       }
@@ -174,6 +175,7 @@ int bloom_ingest(jfgpu_bloom* b, const uint8_t* base, int64_t lo, int64_t hi) {
 #undef PBR
 #undef PB2
 #undef PB
+      if(rc) return rc;
       hipLaunchKernelGGL(granule_finish_kernel, dim3((nb + 255) / 256), dim3(256), 0, b->stream, gcur, cap, nb, p.off);
     }
     HIP_TRY(hipGetLastError());
@@ -204,7 +206,7 @@ int bloom_flush_inner(jfgpu_bloom* b) {
   auto launch_segments = [&](const SegList& S, uint32_t nseg, uint64_t units, uint32_t seg0 = 0) {
     BloomProf ps(b, BS_SEG, units);
     const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nseg, (uint64_t)b->n_cu * 2)));
-    hipLaunchKernelGGL(bloom_segment_kernel, grid, dim3(kPBlock), seg_lds, b->stream, B, S, nseg, seg0);
+    return launch_lds(bloom_segment_kernel, grid, dim3(kPBlock), seg_lds, b->stream, B, S, nseg, seg0);
   };
   if(total == 0) {
     // nothing
@@ -217,7 +219,7 @@ int bloom_flush_inner(jfgpu_bloom* b) {
                          (const uint64_t*)b->pending[s].off, (uint64_t)b->pending[s].cap);
     }
   } else if(b->bp.b2 == 0) {
-    launch_segments(S1, std::min<uint32_t>(nb1, b->bp.n_seg), total);
+    const int rc = launch_segments(S1, std::min<uint32_t>(nb1, b->bp.n_seg), total); if(rc) return rc;
   } else {
     const int g2 = 32;
     if(!b->d_M2) { const int rc = b->d_M2.alloc((size_t)nb1 * g2 * nb2); if(rc) return rc; }
@@ -298,26 +300,29 @@ int bloom_flush_inner(jfgpu_bloom* b) {
             }
             const BloomRingDirect RD{B.data};
             ++b->prof_launches[BS_P2RING]; b->prof_units[BS_P2RING] += gtot;
-            if(roles)
-              hipLaunchKernelGGL((p2_ring_roles_kernel<uint32_t, 2, BloomRingDirect, 3>), dim3(n_ring), block, (size_t)nb2 * 128 + 128, b->stream, RD, b->bp.b2, kBloomItemLow, S1, cap2, d_gcur2,
-                                 out_v, b0, b->d_strag2, b->d_strag2_n, D.counter);
-            else
-            hipLaunchKernelGGL((p2_ring_kernel<BloomRingDirect>), dim3(kG2Single, n_ring), block, (size_t)nb2 * 128 + 128, b->stream, RD, b->bp.b2, kBloomItemLow, S1, cap2, d_gcur2, d_gcur2 + n_tiles,
-                               out_v, b0, (unsigned long long*)nullptr, b->d_strag2, b->d_strag2_n, D.counter);
+            const int rc = roles
+              ? launch_lds(p2_ring_roles_kernel<uint32_t, 2, BloomRingDirect, 3>, dim3(n_ring), block, (size_t)nb2 * 128 + 128, b->stream, RD, b->bp.b2, kBloomItemLow, S1, cap2, d_gcur2,
+                           out_v, b0, b->d_strag2, b->d_strag2_n, D.counter)
+              : launch_lds(p2_ring_kernel<BloomRingDirect>, dim3(kG2Single, n_ring), block, (size_t)nb2 * 128 + 128, b->stream, RD, b->bp.b2, kBloomItemLow, S1, cap2, d_gcur2, d_gcur2 + n_tiles,
+                           out_v, b0, (unsigned long long*)nullptr, b->d_strag2, b->d_strag2_n, D.counter);
+            if(rc) return rc;
             hipLaunchKernelGGL((p1_stragglers_kernel<uint32_t, BloomRingDirect>), dim3(b->n_cu), dim3(256), 0, b->stream, RD, D.counter, (const uint64_t*)b->d_strag2, (const uint32_t*)b->d_strag2_n,
                                n_lists, cap2, d_gcur2, (unsigned long long*)nullptr, out_v, kP2StragPerBlock);
             if(b->tun.flush_trace) { const int rc_ = trace_strag_lists(b->stream, b->d_strag2_n, n_lists, kP2StragPerBlock, roles ? 1 : kG2Single, b0); if(rc_) return rc_; }
           }
-          if(n_ring < gsz && (uint64_t)(b0 + n_ring) * nb2 < b->bp.n_seg)
-            hipLaunchKernelGGL((p2_granule_kernel<uint32_t, BloomDirect, kP2PairPer>), dim3(kG2Single, n_ring ? 1 : gsz), block, (size_t)kPBlock * kP2PairPer * sizeof(uint32_t), b->stream,
-                               D, b->bp.b2, kBloomItemLow, S1, cap2, d_gcur2, d_gcur2 + n_tiles, out_v, b0 + n_ring);
+          if(n_ring < gsz && (uint64_t)(b0 + n_ring) * nb2 < b->bp.n_seg) {
+            const int rc = launch_lds(p2_granule_kernel<uint32_t, BloomDirect, kP2PairPer>, dim3(kG2Single, n_ring ? 1 : gsz), block, (size_t)kPBlock * kP2PairPer * sizeof(uint32_t), b->stream,
+                                      D, b->bp.b2, kBloomItemLow, S1, cap2, d_gcur2, d_gcur2 + n_tiles, out_v, b0 + n_ring,
+                                      (unsigned long long*)nullptr, 0xFFFFFFFFu);      // (the kernel's defaults, which a function pointer does not carry)
+            if(rc) return rc;
+          }
           hipLaunchKernelGGL(granule_finish_range_kernel, dim3(256), dim3(256), 0, b->stream, d_gcur2, cap2, (uint32_t)n_tiles, d_off2, (uint32_t)seg0, gsz * nb2);
         }
         if(seg0 >= b->bp.n_seg) break;
         const uint32_t nseg = (uint32_t)std::min<uint64_t>((uint64_t)gsz * nb2, b->bp.n_seg - seg0);
         SegList S2; memset(&S2, 0, sizeof S2);
         S2.n = 1; S2.items[0] = out_v; S2.off[0] = d_off2 + 2 * seg0; S2.sh[0] = 1;
-        launch_segments(S2, nseg, gtot, (uint32_t)seg0);
+        { const int rc = launch_segments(S2, nseg, gtot, (uint32_t)seg0); if(rc) return rc; }
         continue;
       }
       {
@@ -326,15 +331,16 @@ int bloom_flush_inner(jfgpu_bloom* b) {
         hipLaunchKernelGGL((p2_kernel<uint32_t, false>), grid, block, 0, b->stream, P, kBloomItemLow, S1, b->d_M2, (const uint64_t*)d_goff, tmp, b0);
         hipLaunchKernelGGL(scan_matrix_kernel, dim3(gsz), dim3(1024), 0, b->stream, b->d_M2, (uint32_t)g2, nb2, (const uint64_t*)d_base, d_goff, b0);
         // chunks of 28 Ki cell updates: the runs written per destination are what this pass costs (scatter_write_probe)
-        hipLaunchKernelGGL((p2_scatter_sorted_kernel<uint32_t, kP2PairPer>), grid, block, (size_t)kPBlock * kP2PairPer * sizeof(uint32_t), b->stream,
-                           P, kBloomItemLow, S1, (const uint32_t*)b->d_M2, (const uint64_t*)d_goff, tmp, b0);
+        const int rc = launch_lds(p2_scatter_sorted_kernel<uint32_t, kP2PairPer>, grid, block, (size_t)kPBlock * kP2PairPer * sizeof(uint32_t), b->stream,
+                                  P, kBloomItemLow, S1, (const uint32_t*)b->d_M2, (const uint64_t*)d_goff, tmp, b0);
+        if(rc) return rc;
       }
       // this group's segments: numbers b0 * nb2 .. ; the last group stops at the array's last segment
       if(seg0 >= b->bp.n_seg) break;
       const uint32_t nseg = (uint32_t)std::min<uint64_t>((uint64_t)gsz * nb2, b->bp.n_seg - seg0);
       SegList S2; memset(&S2, 0, sizeof S2);
       S2.n = 1; S2.items[0] = tmp; S2.off[0] = d_goff + seg0;
-      launch_segments(S2, nseg, gtot, (uint32_t)seg0);
+      { const int rc = launch_segments(S2, nseg, gtot, (uint32_t)seg0); if(rc) return rc; }
     }
   }
   HIP_TRY(hipGetLastError());

@@ -42,7 +42,7 @@ size_t item_size(const jfgpu_table* t) { return t->item256 ? 32 : t->item128 ? 1
 // what the plans may know of a table (part_plan.inl)
 PartFacts part_facts(const jfgpu_table* t) {
   PartFacts f;
-  const DevBloom& bloom = t->nword ? t->nt.bloom : t->wide ? t->wt.bloom : t->dt.bloom;
+  const DevBloom& bloom = table_bloom(t);
   f.pg = t->pg; f.item_bytes = (uint32_t)item_size(t); f.slot32 = t->g.slot32; f.mode = t->mode; f.n_cu = t->n_cu; f.g1 = t->g1; f.n_tiles = n_tiles_of(t);
   f.returning = t->returning; f.wide = t->wide; f.nword = t->nword; f.filter = bloom.data != nullptr; f.filter_kind = (int)bloom.kind;
   f.nbytes = t->g.nbytes; f.hash_xs = t->g.hash_xs; f.canonical = t->g.canonical; f.lsize_g = t->g.lsize_g; f.lsize_l = t->g.lsize_l; f.tile_bits = t->g.tile_bits;
@@ -124,18 +124,20 @@ int launch_p2_rings(jfgpu_table* t, const FlushPlan& p, const GroupPlan& q, cons
   const P2RingDirect pd{t->d_dt, t->pg.b2, p.b2e, (int)t->returning};
   unsigned long long* ctr = (unsigned long long*)&t->dt.counters[CTR_DIRECT];
   const dim3 grid(q.grid_x, q.grid_y), block(kPBlock);
+  int rc = JFGPU_OK;
   if(roles) {
     ++t->n_p2_roles;
     if(!pick<Inst<2, 1>, Inst<2, 2>, Inst<2, 3>, Inst<1, 1>, Inst<1, 2>, Inst<1, 3>>(q.p2_targs, [&](auto I) {
          constexpr auto& A = decltype(I)::v;
-         hipLaunchKernelGGL((p2_ring_roles_kernel<uint32_t, A[0], P2RingDirect, A[1]>), grid, block, q.lds, t->stream, pd, p.b2e, p.p2_tag_bits, S1, p.cap2, d_gcur2, out_v, q.b0,
-                            t->d_strag2.get(), t->d_strag2_n.get(), ctr);
+         rc = launch_lds(p2_ring_roles_kernel<uint32_t, A[0], P2RingDirect, A[1]>, grid, block, q.lds, t->stream, pd, p.b2e, p.p2_tag_bits, S1, p.cap2, d_gcur2, out_v, q.b0,
+                         t->d_strag2.get(), t->d_strag2_n.get(), ctr);
        })) return no_kernel("p2_ring_roles_kernel");
   } else {
     ++t->n_p2_ring;
-    hipLaunchKernelGGL((p2_ring_kernel<P2RingDirect>), grid, block, q.lds, t->stream, pd, p.b2e, p.p2_tag_bits, S1, p.cap2, d_gcur2, d_gcur2 + p.n_dest,
-                       out_v, q.b0, (unsigned long long*)nullptr, t->d_strag2.get(), t->d_strag2_n.get(), ctr);
+    rc = launch_lds(p2_ring_kernel<P2RingDirect>, grid, block, q.lds, t->stream, pd, p.b2e, p.p2_tag_bits, S1, p.cap2, d_gcur2, d_gcur2 + p.n_dest,
+                    out_v, q.b0, (unsigned long long*)nullptr, t->d_strag2.get(), t->d_strag2_n.get(), ctr);
   }
+  if(rc) return rc;
   hipLaunchKernelGGL((p1_stragglers_kernel<uint32_t, P2RingDirect>), dim3(t->n_cu), dim3(256), 0, t->stream, pd, ctr, (const uint64_t*)t->d_strag2, (const uint32_t*)t->d_strag2_n,
                      n_lists, p.cap2, d_gcur2, (unsigned long long*)nullptr, out_v, kP2StragPerBlock);
   if(t->tun.flush_trace) return trace_strag_lists(t->stream, t->d_strag2_n, n_lists, kP2StragPerBlock, roles ? 1 : kG2Blocks, q.b0);
@@ -215,26 +217,27 @@ int run_p1(jfgpu_table* t, const P1Plan& p, const uint8_t* base, int64_t lo, int
   const dim3 grid(p.grid), block(kPBlock);
   const uint32_t nb = 1u << t->pg.b1, gcap = p.gran_cap;
   bool found = false;
+  int lrc = JFGPU_OK;               // what a launch with dynamic LDS returned (launch_lds)
   ++(p.kind == kP1Ring ? t->n_p1_ring : t->n_p1_other);
   if(p.kind == kP1NWordGranule) {
     if(t->tun.flush_trace) fprintf(stderr, "[jfgpu flush] P1: p1_nword_granule_kernel, %u buckets, regions of %u items\n", nb, gcap);
     found = pick<Inst<1>, Inst<0>>(p.targs, [&](auto I) {
-      hipLaunchKernelGGL((p1_nword_granule_kernel<decltype(I)::v[0] != 0>), grid, block, p.lds, t->stream, t->nt, t->pg, base, lo, hi, gcap, gcur, b.tot, (u256*)b.items);
+      lrc = launch_lds(p1_nword_granule_kernel<decltype(I)::v[0] != 0>, grid, block, p.lds, t->stream, t->nt, t->pg, base, lo, hi, gcap, gcur, b.tot, (u256*)b.items);
     });
   } else if(p.kind == kP1WideGranule) {
     found = pick<Inst<1, 0, 1>, Inst<0, 0, 1>, Inst<1, 1, 0>, Inst<1, 0, 0>, Inst<0, 1, 0>, Inst<0, 0, 0>>(p.targs, [&](auto I) {
       constexpr auto& A = decltype(I)::v;
-      hipLaunchKernelGGL((p1_wide_granule_kernel<A[0] != 0, A[1] != 0, A[2] != 0>), grid, block, p.lds, t->stream, t->wt, t->pg, base, lo, hi, gcap, gcur, b.tot, (u128*)b.items);
+      lrc = launch_lds(p1_wide_granule_kernel<A[0] != 0, A[1] != 0, A[2] != 0>, grid, block, p.lds, t->stream, t->wt, t->pg, base, lo, hi, gcap, gcur, b.tot, (u128*)b.items);
     });
   } else if(p.kind == kP1Granule64) {
     found = pick<Inst<1, 1, 0>, Inst<0, 1, 0>, Inst<1, 0, kHashXS>, Inst<0, 0, kHashXS>, Inst<1, 0, 0>, Inst<0, 0, 8>, Inst<0, 0, 7>, Inst<0, 0, 0>>(p.targs, [&](auto I) {
       constexpr auto& A = decltype(I)::v;
-      hipLaunchKernelGGL((p1_granule64_kernel<A[0] != 0, A[1] != 0, A[2]>), grid, block, p.lds, t->stream, t->dt, t->pg, base, lo, hi, gcap, gcur, b.tot, (uint64_t*)b.items);
+      lrc = launch_lds(p1_granule64_kernel<A[0] != 0, A[1] != 0, A[2]>, grid, block, p.lds, t->stream, t->dt, t->pg, base, lo, hi, gcap, gcur, b.tot, (uint64_t*)b.items);
     });
   } else if(p.kind == kP1KeysGranule) {
     found = pick<Inst<1, 0>, Inst<0, 6>, Inst<0, 7>, Inst<0, 8>, Inst<0, 0>>(p.targs, [&](auto I) {
       constexpr auto& A = decltype(I)::v;
-      hipLaunchKernelGGL((p1_keys_granule_kernel<A[0] != 0, A[1]>), grid, block, p.lds, t->stream, t->dt, t->pg, (const uint64_t*)base, hi, gcap, gcur, b.tot, (uint32_t*)b.items);
+      lrc = launch_lds(p1_keys_granule_kernel<A[0] != 0, A[1]>, grid, block, p.lds, t->stream, t->dt, t->pg, (const uint64_t*)base, hi, gcap, gcur, b.tot, (uint32_t*)b.items);
     });
   } else if(p.kind == kP1Ring) {
     // what cannot be stored in a region (p1_stragglers_kernel) reads the table's descriptor from device memory
@@ -244,9 +247,10 @@ int run_p1(jfgpu_table* t, const P1Plan& p, const uint8_t* base, int64_t lo, int
     unsigned long long* ctr = (unsigned long long*)&t->dt.counters[CTR_DIRECT];
     found = pick<Inst<0, kHashXS, 1>, Inst<0, kHashXS, 0>, Inst<0, kHashXSLow, 2>, Inst<0, 6, 1>, Inst<0, 6, 0>, Inst<1, 0, 2>, Inst<0, 0, 2>>(p.targs, [&](auto I) {
       constexpr auto& A = decltype(I)::v;
-      hipLaunchKernelGGL((p1_ring_kernel<uint32_t, A[0] != 0, A[1], A[2]>), grid, block, p.lds, t->stream, t->dt, od, t->pg, base, lo, hi, gcap, gcur, b.tot, (uint32_t*)b.items,
-                         t->d_strag.get(), t->d_strag_n.get());
+      lrc = launch_lds(p1_ring_kernel<uint32_t, A[0] != 0, A[1], A[2]>, grid, block, p.lds, t->stream, t->dt, od, t->pg, base, lo, hi, gcap, gcur, b.tot, (uint32_t*)b.items,
+                       t->d_strag.get(), t->d_strag_n.get());
     });
+    if(lrc) return lrc;
     hipLaunchKernelGGL((p1_stragglers_kernel<uint32_t, OneWordDirect>), dim3(t->n_cu), dim3(256), 0, t->stream, od, ctr, (const uint64_t*)t->d_strag, (const uint32_t*)t->d_strag_n,
                        (uint32_t)t->n_cu, gcap, gcur, b.tot, (uint32_t*)b.items);
   } else {
@@ -257,15 +261,16 @@ int run_p1(jfgpu_table* t, const P1Plan& p, const uint8_t* base, int64_t lo, int
     if(p.kind == kP1ExactSorted)
       found = pick<Inst<0, 0, 6>, Inst<0, 0, 7>, Inst<0, 0, 8>, Inst<1, 1, 0>, Inst<1, 0, 0>, Inst<0, 1, 0>, Inst<0, 0, 0>>(p.targs, [&](auto I) {
         constexpr auto& A = decltype(I)::v;
-        hipLaunchKernelGGL((p1_scatter_sorted_kernel<A[0] != 0, A[1] != 0, A[2]>), grid, block, p.lds, t->stream, t->dt, t->pg, base, lo, hi, (const uint32_t*)t->d_M1, (const uint64_t*)b.off, (uint32_t*)b.items);
+        lrc = launch_lds(p1_scatter_sorted_kernel<A[0] != 0, A[1] != 0, A[2]>, grid, block, p.lds, t->stream, t->dt, t->pg, base, lo, hi, (const uint32_t*)t->d_M1, (const uint64_t*)b.off, (uint32_t*)b.items);
       });
     else if(p.kind == kP1ExactKeysSorted)
       found = pick<Inst<6>, Inst<7>, Inst<8>, Inst<0>>(p.targs, [&](auto I) {
-        hipLaunchKernelGGL(p1_keys_scatter_sorted_kernel<decltype(I)::v[0]>, grid, block, p.lds, t->stream, t->dt, t->pg, (const uint64_t*)base, hi, (const uint32_t*)t->d_M1, (const uint64_t*)b.off, (uint32_t*)b.items);
+        lrc = launch_lds(p1_keys_scatter_sorted_kernel<decltype(I)::v[0]>, grid, block, p.lds, t->stream, t->dt, t->pg, (const uint64_t*)base, hi, (const uint32_t*)t->d_M1, (const uint64_t*)b.off, (uint32_t*)b.items);
       });
     else found = launch_p1<uint64_t>(t, p.targs, base, lo, hi, b.off, b.items);
   }
   if(!found) return no_kernel("P1");
+  if(lrc) return lrc;
   if(gcap) hipLaunchKernelGGL(granule_finish_kernel, dim3((nb + 255) / 256), dim3(256), 0, t->stream, gcur, gcap, nb, b.off);
   return JFGPU_OK;
 }
@@ -380,63 +385,69 @@ int flush_sizes(jfgpu_table* t, FlushSizes& fs) {
 // HL: the hole-aware instantiation.  The one for hole-free regions (SegList::dense) exists where such regions do: 4-byte
 // items into pairs of tiles, the plain kernel (HEAVY keeps the hole-aware code on both kinds of input).
 template <typename ITEM, typename SLOT, int TPB, bool HV, bool SM, bool HL>
-void launch_tile_rank_inst(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, hipStream_t ts) {
+int launch_tile_rank_inst(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, hipStream_t ts) {
   const size_t lds = tile_rank_lds(sizeof(SLOT), t->g.tile_bits, TPB);
   const dim3 grid((unsigned)std::min<uint64_t>(ntile, (uint64_t)t->n_cu * 16)), block(kTileBlock);
+  int rc = JFGPU_OK;
   with_flags(t->returning, [&](auto RT) {      // a tile is read only if its dirty byte is set (clean after jfgpu_clear)
-    hipLaunchKernelGGL((tile_rank_insert_kernel<ITEM, decltype(RT)::value, SLOT, TPB, kTileBlock, HV, SM, HL>), grid, block, lds, ts, t->dt, S, tile0, ntile);
+    rc = launch_lds(tile_rank_insert_kernel<ITEM, decltype(RT)::value, SLOT, TPB, kTileBlock, HV, SM, HL>, grid, block, lds, ts, t->dt, S, tile0, ntile);
   });
+  return rc;
 }
 template <typename ITEM, typename SLOT, int TPB, bool HV, bool SM>
-void launch_tile_rank_variant(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, hipStream_t ts) {
+int launch_tile_rank_variant(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, hipStream_t ts) {
   if constexpr(sizeof(ITEM) == 4 && TPB == 2 && !HV) {
-    if(S.n == 1 && S.sh[0] == 1 && S.dense[0]) { ++t->n_tile_dense; launch_tile_rank_inst<ITEM, SLOT, TPB, HV, SM, false>(t, S, tile0, ntile, ts); return; }
+    if(S.n == 1 && S.sh[0] == 1 && S.dense[0]) { ++t->n_tile_dense; return launch_tile_rank_inst<ITEM, SLOT, TPB, HV, SM, false>(t, S, tile0, ntile, ts); }
   }
-  launch_tile_rank_inst<ITEM, SLOT, TPB, HV, SM, true>(t, S, tile0, ntile, ts);
+  return launch_tile_rank_inst<ITEM, SLOT, TPB, HV, SM, true>(t, S, tile0, ntile, ts);
 }
 // Which instantiation (plain, or HEAVY for high-coverage input) is decided from the flush itself: the first `sample` units
 // of a large launch (a 64th: tile_sample_units) go through the plain kernel with its counters on, the host reads them (one
 // wait inside the flush) and the rest follows in the instantiation they call for.  JFGPU_TILE_ADAPT=0: always plain; 2: always
 // HEAVY (tests).
 template <typename ITEM, typename SLOT, int TPB>
-void launch_tile_rank(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, uint32_t sample, hipStream_t ts) {
+int launch_tile_rank(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, uint32_t sample, hipStream_t ts) {
   bool heavy = t->tun.tile_adapt == 2;
   if(sample) {
     (void)hipMemsetAsync(&t->dt.counters[CTR_T_ITEMS], 0, 2 * sizeof(uint64_t), ts);
-    launch_tile_rank_variant<ITEM, SLOT, TPB, false, true>(t, S, tile0, sample, ts);
+    { const int rc = launch_tile_rank_variant<ITEM, SLOT, TPB, false, true>(t, S, tile0, sample, ts); if(rc) return rc; }
     uint64_t smp[2] = {0, 0};                              // items placed, items past rank 3
     if(hipMemcpyAsync(smp, &t->dt.counters[CTR_T_ITEMS], sizeof smp, hipMemcpyDeviceToHost, ts) == hipSuccess && hipStreamSynchronize(ts) == hipSuccess)
       heavy = smp[1] * 4 > smp[0];
   }
   SegList Sr = S; Sr.off[0] = S.off[0] + ((size_t)sample << S.sh[0]);
   if(heavy) ++t->flushes_heavy; else ++t->flushes_plain;
-  if(heavy) launch_tile_rank_variant<ITEM, SLOT, TPB, true, false>(t, Sr, tile0 + (uint64_t)TPB * sample, ntile - sample, ts);
-  else      launch_tile_rank_variant<ITEM, SLOT, TPB, false, false>(t, Sr, tile0 + (uint64_t)TPB * sample, ntile - sample, ts);
+  if(heavy) return launch_tile_rank_variant<ITEM, SLOT, TPB, true, false>(t, Sr, tile0 + (uint64_t)TPB * sample, ntile - sample, ts);
+  return launch_tile_rank_variant<ITEM, SLOT, TPB, false, false>(t, Sr, tile0 + (uint64_t)TPB * sample, ntile - sample, ts);
 }
 
 // the tile insert of one item array (or of the pending batches themselves), on stream `ts`
 template <typename ITEM>
-void launch_tile_kernel(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, uint32_t sample, hipStream_t ts, bool pair) {
+int launch_tile_kernel(jfgpu_table* t, const SegList& S, uint64_t tile0, uint32_t ntile, uint32_t sample, hipStream_t ts, bool pair) {
   if constexpr(sizeof(ITEM) == 32) {
     // keys of three and four words: 256-bit items, 256-bit slots; 64 KiB of LDS: two blocks per CU
     const size_t tile_lds = (size_t)32 << t->g.tile_bits;
     const dim3 block(kNTileBlock), grid((unsigned)std::min<uint64_t>(ntile, (uint64_t)t->n_cu * 8));
     ++t->n_tile_nword;
     if(t->tun.flush_trace) fprintf(stderr, "[jfgpu flush] T: tile_insert_nword_kernel, %u tiles from %llu, %u segment(s)\n", ntile, (unsigned long long)tile0, S.n);
-    with_flags(t->returning, [&](auto RT) { hipLaunchKernelGGL(tile_insert_nword_kernel<decltype(RT)::value>, grid, block, tile_lds, ts, t->nt, S, tile0, ntile); });
+    int rc = JFGPU_OK;
+    with_flags(t->returning, [&](auto RT) { rc = launch_lds(tile_insert_nword_kernel<decltype(RT)::value>, grid, block, tile_lds, ts, t->nt, S, tile0, ntile); });
+    return rc;
   } else if constexpr(sizeof(ITEM) == 16) {
     // two-word keys: 128-bit items, 128-bit slots; 128 KiB of LDS: one block per CU
     const size_t tile_lds = (size_t)16 << t->g.tile_bits;
     const bool pipe = S.n == 1 && t->tun.wide_pipe;        // one item array (a flush's P2 output): the pipelined kernel
     const dim3 block(kPBlock), grid((unsigned)std::min<uint64_t>(ntile, (uint64_t)t->n_cu * (pipe ? 1 : 4)));
+    int rc = JFGPU_OK;
     with_flags(t->returning, [&](auto RT) {
-      if(pipe) hipLaunchKernelGGL(tile_insert_wide_pipe_kernel<decltype(RT)::value>, grid, block, tile_lds, ts, t->wt, S, tile0, ntile);
-      else     hipLaunchKernelGGL(tile_insert_wide_kernel<decltype(RT)::value>, grid, block, tile_lds, ts, t->wt, S, tile0, ntile);
+      if(pipe) rc = launch_lds(tile_insert_wide_pipe_kernel<decltype(RT)::value>, grid, block, tile_lds, ts, t->wt, S, tile0, ntile);
+      else     rc = launch_lds(tile_insert_wide_kernel<decltype(RT)::value>, grid, block, tile_lds, ts, t->wt, S, tile0, ntile);
     });
+    return rc;
   } else {
     // one-word keys: placement by rank inside buckets of four (kernels_tile.hip.hpp); two workgroups per CU
-    if(t->g.slot32) { if(pair) launch_tile_rank<ITEM, unsigned int, 2>(t, S, tile0, ntile, sample, ts); else launch_tile_rank<ITEM, unsigned int, 1>(t, S, tile0, ntile, sample, ts); }
-    else launch_tile_rank<ITEM, unsigned long long, 1>(t, S, tile0, ntile, sample, ts);
+    if(t->g.slot32) return pair ? launch_tile_rank<ITEM, unsigned int, 2>(t, S, tile0, ntile, sample, ts) : launch_tile_rank<ITEM, unsigned int, 1>(t, S, tile0, ntile, sample, ts);
+    return launch_tile_rank<ITEM, unsigned long long, 1>(t, S, tile0, ntile, sample, ts);
   }
 }
 
@@ -461,20 +472,21 @@ void run_items_direct(jfgpu_table* t, const FlushSizes& fs) {
 
 // kRouteSingleLevel: the P1 buckets are the tiles; keys of two and more words take all batches in one pass, one-word keys one pass a batch
 template <typename ITEM>
-void run_single_level(jfgpu_table* t, const PartFacts& f, const FlushSizes& fs, const SegList& S1) {
+int run_single_level(jfgpu_table* t, const PartFacts& f, const FlushSizes& fs, const SegList& S1) {
   const uint32_t nb1 = 1u << t->pg.b1;
   auto launch_tiles = [&](const SegList& S, uint64_t units) {
     ProfScope ps(t, 6, units);
-    launch_tile_kernel<ITEM>(t, S, 0, nb1, tile_sample_units(f, nb1, S.n), t->stream, false);
+    return launch_tile_kernel<ITEM>(t, S, 0, nb1, tile_sample_units(f, nb1, S.n), t->stream, false);
   };
-  if constexpr(sizeof(ITEM) >= 16) launch_tiles(S1, fs.total);
+  if constexpr(sizeof(ITEM) >= 16) return launch_tiles(S1, fs.total);
   else for(size_t s = 0; s < S1.n; ++s) {
     const uint64_t n = fs.offs[s * (nb1 + 1) + nb1];
     if(!n) continue;
     SegList Sb; memset(&Sb, 0, sizeof Sb);
     Sb.n = 1; Sb.items[0] = S1.items[s]; Sb.off[0] = S1.off[s]; Sb.sh[0] = S1.sh[s];
-    launch_tiles(Sb, n);
+    const int rc = launch_tiles(Sb, n); if(rc) return rc;
   }
+  return JFGPU_OK;
 }
 
 // The three blocks of a two-level flush (FlushPlan::block_*): from the arena where the plan put them, or -- one_off -- held
@@ -513,13 +525,15 @@ int run_p2(jfgpu_table* t, const FlushPlan& p, const GroupPlan& q, const SegList
     ++t->n_p2_exact;
     hipLaunchKernelGGL((p2_kernel<ITEM, false>), grid, block, 0, t->stream, pg2, p.p2_tag_bits, S1, t->d_M2, (const uint64_t*)d_goff, tmp, q.b0);
     hipLaunchKernelGGL(scan_matrix_kernel, dim3(q.nbk), dim3(1024), 0, t->stream, t->d_M2, kG2Exact, 1u << p.b2e, (const uint64_t*)d_base, d_goff, q.b0);
+    int rc = JFGPU_OK;
     auto scatter = [&](auto I) {
-      hipLaunchKernelGGL((p2_scatter_sorted_kernel<ITEM, decltype(I)::v[0]>), grid, block, q.lds, t->stream, pg2, p.p2_tag_bits, S1, (const uint32_t*)t->d_M2, (const uint64_t*)d_goff, tmp, q.b0);
+      rc = launch_lds(p2_scatter_sorted_kernel<ITEM, decltype(I)::v[0]>, grid, block, q.lds, t->stream, pg2, p.p2_tag_bits, S1, (const uint32_t*)t->d_M2, (const uint64_t*)d_goff, tmp, q.b0);
     };
     bool found;
     if constexpr(sizeof(ITEM) == 4) found = pick<Inst<kP2PairPer>, Inst<16>>(q.p2_targs, scatter);
     else found = pick<Inst<sizeof(ITEM) == 8 ? 14 : sizeof(ITEM) == 16 ? 7 : kP2NWordPer>>(q.p2_targs, scatter);
     if(!found) return no_kernel("p2_scatter_sorted_kernel");
+    if(rc) return rc;
     S2->items[0] = tmp; S2->off[0] = d_goff + q.d0;
     return JFGPU_OK;
   }
@@ -531,14 +545,17 @@ int run_p2(jfgpu_table* t, const FlushPlan& p, const GroupPlan& q, const SegList
   if(q.p2 == kP2Sort) {
     constexpr int per = sizeof(ITEM) == 4 ? kP2PairPer : sizeof(ITEM) == 8 ? kP2MidPer : kP2WidePer;
     ++t->n_p2_sort;
+    int rc = JFGPU_OK;
     with_flags(t->returning, [&](auto RT) {
       constexpr bool rt = decltype(RT)::value;
       const auto direct = [&] {      // what does not fit a region goes straight to the table
         if constexpr(sizeof(ITEM) == 16) return WideDirect<rt>{t->wt, t->pg};
         else return TableDirect<rt>{t->d_dt, t->pg, (unsigned long long*)&t->dt.counters[CTR_DIRECT]};
       }();
-      hipLaunchKernelGGL((p2_granule_kernel<ITEM, std::remove_const_t<decltype(direct)>, per>), grid, block, q.lds, t->stream, direct, p.b2e, p.p2_tag_bits, S1, p.cap2, d_gcur2, d_gcur2 + p.n_dest, out_v, q.b0);
+      rc = launch_lds(p2_granule_kernel<ITEM, std::remove_const_t<decltype(direct)>, per>, grid, block, q.lds, t->stream, direct, p.b2e, p.p2_tag_bits, S1, p.cap2, d_gcur2, d_gcur2 + p.n_dest, out_v, q.b0,
+                      (unsigned long long*)nullptr, 0xFFFFFFFFu);      // (no totals, every bucket: the kernel's defaults, which a function pointer does not carry)
     });
+    if(rc) return rc;
   } else if constexpr(sizeof(ITEM) == 4) {
     const int rc = launch_p2_rings(t, p, q, S1, d_gcur2, out_v); if(rc) return rc;
   } else return no_kernel("ring P2 of items wider than 4 bytes");
@@ -566,7 +583,7 @@ int tile_stage(jfgpu_table* t, const FlushPlan& p, const GroupPlan& q, uint32_t 
       hipEventRecord(gb, ts); hipEventRecord(gc, ts);
       t->prof_pending.push_back({ga, gb, 5, q.items});
     }
-    launch_tile_kernel<ITEM>(t, S2, q.tile0, q.ntile, q.sample, ts, p.pair);
+    { const int rc = launch_tile_kernel<ITEM>(t, S2, q.tile0, q.ntile, q.sample, ts, p.pair); if(rc) return rc; }
     if(prof) { hipEventRecord(gd, ts); t->prof_pending.push_back({gc, gd, 6, q.items}); }
     return JFGPU_OK;
   }
@@ -577,7 +594,7 @@ int tile_stage(jfgpu_table* t, const FlushPlan& p, const GroupPlan& q, uint32_t 
     ts = t->stream2;
   }
   if(prof && g == 0) hipEventRecord(whole[2], ts);
-  launch_tile_kernel<ITEM>(t, S2, q.tile0, q.ntile, q.sample, ts, p.pair);
+  { const int rc = launch_tile_kernel<ITEM>(t, S2, q.tile0, q.ntile, q.sample, ts, p.pair); if(rc) return rc; }
   if(prof && last) hipEventRecord(whole[3], ts);
   return JFGPU_OK;
 }
@@ -655,7 +672,7 @@ int part_flush_t(jfgpu_table* t) {
   switch(p.route) {
   case kRouteNothing: break;
   case kRouteDirect: run_items_direct<ITEM>(t, fs); break;
-  case kRouteSingleLevel: run_single_level<ITEM>(t, f, fs, S1); break;
+  case kRouteSingleLevel: { const int rc = run_single_level<ITEM>(t, f, fs, S1); if(rc) return rc; } break;
   case kRouteTwoLevel: { const int rc = run_two_level<ITEM>(t, f, p, fs, S1, all_granule); if(rc) return rc; }
   }
   hipError_t e = hipGetLastError();

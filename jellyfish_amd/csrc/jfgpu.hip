@@ -5,6 +5,7 @@
 // and hands the table to the dumper (:349-355).  Here the "threads" are HIP
 // kernels enqueued on one stream per table; there is no CPU fallback.
 // Who owns what on the host: hip_own.hpp (owners in handles, raw pointers only inside the structs handed to kernels).
+// Kernels with dynamic LDS are launched through launch_lds (hip_launch.hpp), which raises the kernel's limit on this device.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -79,6 +80,7 @@ struct ProfSpan { hipEvent_t a, b; int which; uint64_t units; };   // (events of
 }  // namespace
 
 #include "hip_own.hpp"
+#include "hip_launch.hpp"
 
 struct jfgpu_table {
   jfgpu_params params{};
@@ -181,6 +183,9 @@ int use(const jfgpu_table* t) {
 
 size_t slot_bytes_of(const jfgpu_table* t) { return t->g.slot32 ? 4 : 8 * (size_t)t->slot_words; }
 uint64_t n_tiles_of(const jfgpu_table* t) { return 1ull << (t->g.lsize_l - t->g.tile_bits); }
+// the filter attached to the table (count --bc, --bf-size), which lives in the view of its key width
+DevBloom& table_bloom(jfgpu_table* t) { return t->nword ? t->nt.bloom : t->wide ? t->wt.bloom : t->dt.bloom; }
+const DevBloom& table_bloom(const jfgpu_table* t) { return table_bloom(const_cast<jfgpu_table*>(t)); }
 
 int grid_for(const jfgpu_table* t, uint64_t work_items) {
   uint64_t g = std::min<uint64_t>(work_items, (uint64_t)t->n_cu * 8);
@@ -272,7 +277,14 @@ __global__ void ovf_rehash_kernel(const uint64_t* __restrict__ okey, const uint6
   }
 }
 
-void refresh_views(jfgpu_table* t);     // the two- and N-word views of the table share its side table and counters
+// The two- and N-word views of the table share its slots, hash tables, side table and counters: what a view holds of them, from
+// the DevTable (create, doubling, a side table rebuilt larger).  Geometry and filter are the view's own.
+template <class View> void fill_view(View& v, const DevTable& d) {
+  v.slots = d.slots; v.fwd_tbl = d.fwd_tbl; v.inv_tbl = d.inv_tbl; v.ovf_key = d.ovf_key; v.ovf_cnt = d.ovf_cnt;
+  v.ovf_mask = d.ovf_mask; v.counters = d.counters; v.max_probe = d.max_probe;
+  if constexpr(std::is_same_v<View, WideTable>) v.dirty = d.dirty;
+}
+void refresh_views(jfgpu_table* t);
 
 int ensure_ovf(jfgpu_table* t, uint64_t more_occurrences, uint64_t more_big_adds) {
   t->occ_bound += more_occurrences; t->bigval_bound += more_big_adds;
@@ -305,55 +317,7 @@ int ensure_ovf(jfgpu_table* t, uint64_t more_occurrences, uint64_t more_big_adds
   return JFGPU_OK;
 }
 
-int launch_count_chunk(jfgpu_table* t, const char* d_bases, size_t n) {
-  if(n < t->g.k) return JFGPU_OK;
-  { int rc = ensure_ovf(t, n, 0); if(rc) return rc; }
-  const uint8_t* base; int64_t lo, hi;
-  align_buffer(d_bases, n, base, lo, hi);
-  if(t->nword) {
-    if(t->operation == 0 && use_partitioned(t, n)) {      // PRIME / UPDATE passes run on the direct kernel, as for the narrower keys
-      const int rc = part_ingest(t, base, lo, hi, false, n);
-      if(rc >= 0) return rc;        // < 0: no memory for the pending batch -> direct kernel
-    }
-    t->pristine = false;
-    const int64_t nt = (hi + kTilePos - 1) / kTilePos;
-    ProfScope ps(t, 0, n);
-    const bool bl = t->nt.bloom.data != nullptr;
-#define CN(RT, BL) hipLaunchKernelGGL((count_ascii_nword_kernel<RT, BL>), dim3(grid_for(t, (uint64_t)nt)), dim3(kBlock), 0, t->stream, t->nt, base, lo, hi, t->operation)
-    if(t->returning) { if(bl) CN(true, true); else CN(true, false); } else { if(bl) CN(false, true); else CN(false, false); }
-#undef CN
-    HIP_TRY(hipGetLastError());
-    return JFGPU_OK;
-  }
-  if(t->wide) {
-    if(t->operation == 0 && use_partitioned(t, n)) {
-      const int rc = part_ingest(t, base, lo, hi, false, n);
-      if(rc >= 0) return rc;        // < 0: batch too small for the single-pass partition / no memory -> direct kernel
-    }
-    t->pristine = false;
-    const int64_t nt = (hi + kTilePos - 1) / kTilePos;
-    ProfScope ps(t, 0, n);
-    if(t->returning) hipLaunchKernelGGL(count_ascii_wide_kernel<true>, dim3(grid_for(t, (uint64_t)nt)), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, t->operation);
-    else             hipLaunchKernelGGL(count_ascii_wide_kernel<false>, dim3(grid_for(t, (uint64_t)nt)), dim3(kBlock), 0, t->stream, t->wt, base, lo, hi, t->operation);
-    HIP_TRY(hipGetLastError());
-    return JFGPU_OK;
-  }
-  if(t->operation == 0 && use_partitioned(t, n)) {        // PRIME / UPDATE passes of --if run on the direct kernel
-    const int rc = part_ingest(t, base, lo, hi, false, n);
-    if(rc >= 0) return rc;          // < 0: no memory for the pending batch -> direct kernel below
-  }
-  t->pristine = false;
-  const int64_t n_tiles = (hi + kTilePos - 1) / kTilePos;
-  const int grid = grid_for(t, (uint64_t)n_tiles);
-  ProfScope ps(t, 0, n);
-  const bool bl = t->dt.bloom.data != nullptr;
-#define CA(RT, BL) hipLaunchKernelGGL((count_ascii_kernel<RT, BL>), dim3(grid), dim3(kBlock), 0, t->stream, t->dt, base, lo, hi, t->operation)
-  if(t->returning) { if(bl) CA(true, true); else CA(true, false); } else { if(bl) CA(false, true); else CA(false, false); }
-#undef CA
-  HIP_TRY(hipGetLastError());
-  return JFGPU_OK;
-}
-
+int launch_count_chunk(jfgpu_table* t, const char* d_bases, size_t n);
 
 // How many more k-mers may be enqueued before the table could exceed 80 % load, assuming every one
 // of them is new (an upper bound: duplicates are only discovered by inserting).
@@ -446,6 +410,32 @@ template <class F> void with_view(jfgpu_table* t, F&& f) {
   if(t->nword) f(t->nt); else if(t->wide) f(t->wt); else f(t->dt);
 }
 
+// One piece of sequence into the table: the partitioned path where it applies, else the direct kernel of the key width.
+int launch_count_chunk(jfgpu_table* t, const char* d_bases, size_t n) {
+  if(n < t->g.k) return JFGPU_OK;
+  { int rc = ensure_ovf(t, n, 0); if(rc) return rc; }
+  const uint8_t* base; int64_t lo, hi;
+  align_buffer(d_bases, n, base, lo, hi);
+  if(t->operation == 0 && use_partitioned(t, n)) {        // PRIME / UPDATE passes of --if run on the direct kernel
+    const int rc = part_ingest(t, base, lo, hi, false, n);
+    if(rc >= 0) return rc;          // < 0: batch too small for the single-pass partition / no memory for the pending batch -> direct kernel below
+  }
+  t->pristine = false;
+  const dim3 grid(grid_for(t, (uint64_t)((hi + kTilePos - 1) / kTilePos))), block(kBlock);
+  ProfScope ps(t, 0, n);
+  with_view(t, [&](const auto& T) {
+    typedef std::decay_t<decltype(T)> Table;
+    with_flags(t->returning, T.bloom.data != nullptr, [&](auto RT, auto BL) {
+      constexpr bool rt = decltype(RT)::value, bl = decltype(BL)::value;
+      if constexpr(std::is_same_v<Table, NTable>) hipLaunchKernelGGL((count_ascii_nword_kernel<rt, bl>), grid, block, 0, t->stream, T, base, lo, hi, t->operation);
+      else if constexpr(std::is_same_v<Table, WideTable>) hipLaunchKernelGGL(count_ascii_wide_kernel<rt>, grid, block, 0, t->stream, T, base, lo, hi, t->operation);   // (takes no BL flag)
+      else hipLaunchKernelGGL((count_ascii_kernel<rt, bl>), grid, block, 0, t->stream, T, base, lo, hi, t->operation);
+    });
+  });
+  HIP_TRY(hipGetLastError());
+  return JFGPU_OK;
+}
+
 // stats / histo / tile counts / digest: the one-word kernels, scan_kernel for the wider keys.
 // out: 64-bit counters, zeroed by the caller (tile_counts for SCAN_TILES: the wider keys want them zeroed as well).
 struct ScanArgs { int what; uint64_t lower = 0, upper = ~0ull; int have_ovf = 0; uint64_t hbase = 0, hceil = 0, hinc = 1, nb = 1; };
@@ -458,22 +448,22 @@ void launch_scan(jfgpu_table* t, const DevTable& T, const ScanArgs& a, unsigned 
 }
 template <class Table>
 void launch_scan(jfgpu_table* t, const Table& T, const ScanArgs& a, unsigned long long* out, uint32_t* tile_counts) {
-  hipLaunchKernelGGL(scan_kernel, dim3(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), dim3(kBlock), 0, t->stream, T, a.what, a.lower, a.upper, a.have_ovf,
+  hipLaunchKernelGGL(scan_kernel<Table>, dim3(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), dim3(kBlock), 0, t->stream, T, a.what, a.lower, a.upper, a.have_ovf,
                      a.hbase, a.hceil, a.hinc, a.nb, out, tile_counts);
 }
 
 // Pass 2 of the sorted dump (jfgpu_dump_next) for tiles [t0, t0 + ntile): records at d_tile_off, into d_dump.
-void launch_dump(jfgpu_table* t, const DevTable& T, uint64_t t0, uint64_t ntile, uint32_t key_bytes) {
-  const size_t lds = ((size_t)8 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits) + (size_t)t->g.nbytes * 2048;
-  hipLaunchKernelGGL(dump_tiles_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), lds, t->stream, T, t->dump_lower,
-                     t->dump_upper, t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump.get(), key_bytes,
-                     t->out_counter_len);
+int launch_dump(jfgpu_table* t, const DevTable& T, uint64_t t0, uint64_t ntile, uint32_t key_bytes) {
+  const size_t lds = ((size_t)8 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits) + (size_t)t->g.nbytes * 2048;      // > 64 KiB at tiles of 2^13 slots
+  return launch_lds(dump_tiles_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), lds, t->stream, T, t->dump_lower,
+                    t->dump_upper, t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump.get(), key_bytes,
+                    t->out_counter_len);
 }
 template <class Table>
-void launch_dump(jfgpu_table* t, const Table& T, uint64_t t0, uint64_t ntile, uint32_t key_bytes) {
+int launch_dump(jfgpu_table* t, const Table& T, uint64_t t0, uint64_t ntile, uint32_t key_bytes) {
   const size_t lds = ((size_t)(8 * KeyOps<Table>::kSlotWords) << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits);     // 16 or 32 bytes of slot, 2 of index
-  hipLaunchKernelGGL(dump_tiles_words_kernel, dim3(grid_for(t, ntile)), dim3(kBlock), lds, t->stream, T, t->dump_lower, t->dump_upper,
-                     t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump.get(), key_bytes, t->out_counter_len);
+  return launch_lds(dump_tiles_words_kernel<Table>, dim3(grid_for(t, ntile)), dim3(kBlock), lds, t->stream, T, t->dump_lower, t->dump_upper,
+                    t->dump_have_ovf, t0, ntile, (const uint64_t*)t->d_tile_off, t->d_dump.get(), key_bytes, t->out_counter_len);
 }
 
 // The sender's two passes over one contract buffer (route_count_kernel, route_scatter_kernel): the buffer's k-mers into `out`,
@@ -487,21 +477,23 @@ int route_buffer(jfgpu_table* t, const char* d_bases, size_t n, unsigned long lo
   const int grid = grid_for(t, (uint64_t)((hi + kTilePos - 1) / kTilePos));
   auto launch = [&](bool scatter) {
     ProfScope ps(t, 2, scatter ? 0 : n);
+    int rc = JFGPU_OK;
     with_view(t, [&](const auto& T) {
       typedef std::decay_t<decltype(T)> Table;
       typedef KeyOps<Table> K;
       const size_t lds = K::kFwdLdsWords ? 0 : route_lds_bytes(t->g.nbytes, K::kHaloWords);
       auto go = [&](auto bloom) {
-        if(scatter) hipLaunchKernelGGL((route_scatter_kernel<Table, decltype(bloom)::value>), dim3(grid), dim3(kBlock), lds, t->stream, T, base, lo, hi, d_cnt, out, t->key_words);
-        else hipLaunchKernelGGL((route_count_kernel<Table, decltype(bloom)::value>), dim3(grid), dim3(kBlock), lds, t->stream, T, base, lo, hi, d_cnt);
+        if(scatter) rc = launch_lds(route_scatter_kernel<Table, decltype(bloom)::value>, dim3(grid), dim3(kBlock), lds, t->stream, T, base, lo, hi, d_cnt, out, t->key_words);
+        else rc = launch_lds(route_count_kernel<Table, decltype(bloom)::value>, dim3(grid), dim3(kBlock), lds, t->stream, T, base, lo, hi, d_cnt);
       };
       if constexpr(std::is_same_v<Table, NTable>) go(std::false_type());      // (takes no filter)
       else if(T.bloom.data) go(std::true_type());
       else go(std::false_type());
     });
+    return rc;
   };
   HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * W, t->stream));
-  launch(false);
+  { const int rc = launch(false); if(rc) return rc; }
   std::vector<unsigned long long> h(W);
   HIP_TRY(hipMemcpyAsync(h.data(), d_cnt, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost, t->stream));
   HIP_TRY(hipStreamSynchronize(t->stream));
@@ -509,7 +501,7 @@ int route_buffer(jfgpu_table* t, const char* d_bases, size_t n, unsigned long lo
   for(uint32_t p = 0; p < W; ++p) { counts[p] = h[p]; h[p] = total; total += counts[p]; }
   if(total > capacity) return fail(JFGPU_E_INVALID, "partition buffer too small: need " + std::to_string(total) + " keys");
   HIP_TRY(hipMemcpyAsync(d_cnt, h.data(), sizeof(unsigned long long) * W, hipMemcpyHostToDevice, t->stream));   // cursors = offsets
-  launch(true);
+  { const int rc = launch(true); if(rc) return rc; }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(t->stream));       // (the host vector h is read by the copy above)
   return JFGPU_OK;
@@ -620,15 +612,8 @@ int grow_prepare(jfgpu_table* t, GrowNew& N) {
   HIP_TRY(hipMemcpyAsync(N.ni, inv.data(), inv.size() * 8, hipMemcpyHostToDevice, t->stream));
   HIP_TRY(hipStreamSynchronize(t->stream));                  // (fwd / inv are this function's)
   N.nw = t->wt; N.nn = t->nt;
-  if(t->nword) {
-    NTable& nn = N.nn;
-    nn.N = N.ng2; nn.slots = nd.slots; nn.fwd_tbl = N.nf; nn.inv_tbl = N.ni; nn.ovf_key = nd.ovf_key; nn.ovf_cnt = nd.ovf_cnt;
-    nn.ovf_mask = nd.ovf_mask; nn.counters = nd.counters; nn.max_probe = nd.max_probe;
-  } else if(t->wide) {
-    WideTable& nw = N.nw;
-    nw.W = N.w2; nw.slots = nd.slots; nw.fwd_tbl = N.nf; nw.inv_tbl = N.ni; nw.ovf_key = nd.ovf_key; nw.ovf_cnt = nd.ovf_cnt;
-    nw.ovf_mask = nd.ovf_mask; nw.counters = nd.counters; nw.max_probe = nd.max_probe; nw.dirty = nd.dirty;
-  }
+  if(t->nword) { N.nn.N = N.ng2; fill_view(N.nn, nd); }
+  else if(t->wide) { N.nw.W = N.w2; fill_view(N.nw, nd); }
   return JFGPU_OK;
 }
 
@@ -641,11 +626,7 @@ int grow_swap(jfgpu_table* t, GrowNew& N) {
   (void)t->d_M2.reset();
   (void)t->d_strag.reset(); (void)t->d_strag_n.reset();     // (the item width may change with the geometry)
   if(t->nword) t->nt = N.nn;
-  if(t->wide) {
-    t->wt = N.nw;
-    const int wl = (int)(((size_t)16 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits));
-    HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_words_kernel<WideTable>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
-  }
+  if(t->wide) t->wt = N.nw;
   part_geom_init(t);
   if(t->mode == MODE_PARTITIONED && !t->part_ok) t->mode = MODE_AUTO;
   t->pristine = false;
@@ -658,15 +639,15 @@ int table_grow(jfgpu_table* t) {
   int rc = grow_prepare(t, N); if(rc) return rc;
   const int have_ovf = (int)(N.ctr[CTR_OVF_USED] != 0);
   const dim3 grid(grid_for(t, (1ull << t->g.lsize_l) / kBlock + 1)), block(kBlock);
-  with_view(t, N, [&](const auto& old, const auto& neu) { hipLaunchKernelGGL(rehash_kernel, grid, block, 0, t->stream, old, neu, have_ovf); });
+  with_view(t, N, [&](const auto& old, const auto& neu) { hipLaunchKernelGGL(rehash_kernel<std::decay_t<decltype(neu)>>, grid, block, 0, t->stream, old, neu, have_ovf); });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(t->stream));
   return grow_swap(t, N);
 }
 
 void refresh_views(jfgpu_table* t) {
-  if(t->nword) { t->nt.ovf_key = t->dt.ovf_key; t->nt.ovf_cnt = t->dt.ovf_cnt; t->nt.ovf_mask = t->dt.ovf_mask; }
-  if(t->wide) { t->wt.ovf_key = t->dt.ovf_key; t->wt.ovf_cnt = t->dt.ovf_cnt; t->wt.ovf_mask = t->dt.ovf_mask; }
+  if(t->nword) fill_view(t->nt, t->dt);
+  if(t->wide) fill_view(t->wt, t->dt);
 }
 
 bool use_partitioned(const jfgpu_table* t, size_t nbytes) {
@@ -785,123 +766,11 @@ int jfgpu_create(const jfgpu_params* p, jfgpu_table** out) {
   d.max_probe = (uint32_t)std::min<uint64_t>(t->g.tile_mask, 1023);
   HIP_TRY(hipMemcpy(t->d_fwd, fwd.data(), fwd.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(t->d_inv, inv.data(), inv.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-  // dump kernel needs > 64 KiB of dynamic LDS
-  const size_t dump_lds = ((size_t)8 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits) + (size_t)t->g.nbytes * 2048;
-  HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dump_lds));
-  if(nword) {
-    NTable& w = t->nt;
-    w.slots = d.slots; w.fwd_tbl = d.fwd_tbl; w.inv_tbl = d.inv_tbl; w.ovf_key = d.ovf_key; w.ovf_cnt = d.ovf_cnt;
-    w.ovf_mask = d.ovf_mask; w.counters = d.counters; w.max_probe = d.max_probe;
-    memset(&w.bloom, 0, sizeof w.bloom);
-    part_geom_init(t.get());
-    const int nl = (int)(((size_t)32 << kNTileBits) + ((size_t)2 << kNTileBits));
-    HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_words_kernel<NTable>, hipFuncAttributeMaxDynamicSharedMemorySize, nl));
-    {                                                                          // the routing passes of a shard, world 1 included (route_buffer)
-      const int rl = (int)route_lds_bytes(t->g.nbytes, KeyOps<NTable>::kHaloWords);
-      HIP_TRY(hipFuncSetAttribute((const void*)route_count_kernel<NTable, false>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-      HIP_TRY(hipFuncSetAttribute((const void*)route_scatter_kernel<NTable, false>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-    }
-    HIP_TRY(hipFuncSetAttribute((const void*)query_ascii_kernel<NTable>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)query_lds_bytes(t->g.nbytes, KeyOps<NTable>::kHaloWords)));
-  } else if(wide) {
-    WideTable& w = t->wt;
-    w.slots = d.slots; w.fwd_tbl = d.fwd_tbl; w.inv_tbl = d.inv_tbl; w.ovf_key = d.ovf_key; w.ovf_cnt = d.ovf_cnt;
-    w.ovf_mask = d.ovf_mask; w.counters = d.counters; w.max_probe = d.max_probe; w.dirty = d.dirty;
-    memset(&w.bloom, 0, sizeof w.bloom);
-    part_geom_init(t.get());
-    const int wl = (int)(((size_t)16 << t->g.tile_bits) + ((size_t)2 << t->g.tile_bits));
-    HIP_TRY(hipFuncSetAttribute((const void*)dump_tiles_words_kernel<WideTable>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
-  } else part_geom_init(t.get());
+  if(nword) { fill_view(t->nt, d); memset(&t->nt.bloom, 0, sizeof t->nt.bloom); }
+  else if(wide) { fill_view(t->wt, d); memset(&t->wt.bloom, 0, sizeof t->wt.bloom); }
+  part_geom_init(t.get());
   if(t->tun.mode == 1) t->mode = MODE_DIRECT;
   else if(t->tun.mode == 2 && t->part_ok) t->mode = MODE_PARTITIONED;
-  {
-#define TATTR2(I, R, S, P, H, M, HL) HIP_TRY(hipFuncSetAttribute((const void*)tile_rank_insert_kernel<I, R, S, P, kTileBlock, H, M, HL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_rank_lds(sizeof(S), kMaxTileBits, P)))
-#define TATTR1(I, R, S, P, H, M) TATTR2(I, R, S, P, H, M, true)
-#define TATTR(I, S, P) TATTR1(I, true, S, P, false, false); TATTR1(I, false, S, P, false, false); TATTR1(I, true, S, P, true, false); TATTR1(I, false, S, P, true, false); \
-                       TATTR1(I, true, S, P, false, true); TATTR1(I, false, S, P, false, true)
-    TATTR(uint32_t, unsigned int, 1); TATTR(uint32_t, unsigned int, 2); TATTR(uint32_t, unsigned long long, 1);
-    TATTR(uint64_t, unsigned int, 1); TATTR(uint64_t, unsigned int, 2); TATTR(uint64_t, unsigned long long, 1);
-    // the instantiations for hole-free regions (launch_tile_rank_variant: 4-byte items into pairs of tiles, plain and sampling)
-    TATTR2(uint32_t, true, unsigned int, 2, false, false, false); TATTR2(uint32_t, false, unsigned int, 2, false, false, false);
-    TATTR2(uint32_t, true, unsigned int, 2, false, true, false); TATTR2(uint32_t, false, unsigned int, 2, false, true, false);
-#undef TATTR
-#undef TATTR1
-#undef TATTR2
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_scatter_sorted_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_scatter_sorted_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_scatter_sorted_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_scatter_sorted_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
-#define PATTR(N) HIP_TRY(hipFuncSetAttribute((const void*)p1_keys_scatter_sorted_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6)); \
-                 HIP_TRY(hipFuncSetAttribute((const void*)p1_scatter_sorted_kernel<false, false, N>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6))
-    PATTR(0); PATTR(6); PATTR(7); PATTR(8);
-#undef PATTR
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_keys_granule_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_keys_granule_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_keys_granule_kernel<false, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_keys_granule_kernel<false, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_keys_granule_kernel<false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kPTilePos * 6));
-    {
-      const int rl = kGranMaxB * 128 + 128;
-#define RATTR(IT, BL, N, CN) HIP_TRY(hipFuncSetAttribute((const void*)p1_ring_kernel<IT, BL, N, CN>, hipFuncAttributeMaxDynamicSharedMemorySize, rl))
-      HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_kernel<P2RingDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-      HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_roles_kernel<uint32_t, 2, P2RingDirect, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-      HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_roles_kernel<uint32_t, 1, P2RingDirect, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-      HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_roles_kernel<uint32_t, 2, P2RingDirect, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-      HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_roles_kernel<uint32_t, 1, P2RingDirect, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-      HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_roles_kernel<uint32_t, 2, P2RingDirect, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-      HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_roles_kernel<uint32_t, 1, P2RingDirect, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-      RATTR(uint32_t, false, 6, 1); RATTR(uint32_t, false, 6, 0); RATTR(uint32_t, true, 0, 2); RATTR(uint32_t, false, 0, 2);
-      RATTR(uint32_t, false, kHashXS, 1); RATTR(uint32_t, false, kHashXS, 0); RATTR(uint32_t, false, kHashXSLow, 2);
-#undef RATTR
-    }
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_scatter_sorted_kernel<uint32_t, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * 16 * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_ring_kernel<uint32_t, false, 6, 1, RouteListDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_ring_kernel<uint32_t, false, 6, 0, RouteListDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_ring_kernel<uint32_t, false, 0, 2, RouteListDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_ring_kernel<uint32_t, true, 0, 2, RouteListDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_ring_kernel<uint32_t, false, kHashXS, 1, RouteListDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_ring_kernel<uint32_t, false, kHashXS, 0, RouteListDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_ring_kernel<uint32_t, false, kHashXSLow, 2, RouteListDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGranMaxB * 128 + 128)));
-#define SATTR(SW) HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<uint32_t, TableDirect<true>, kP2PairPer, SW>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2PairPer * 4)); \
-                  HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<uint32_t, TableDirect<false>, kP2PairPer, SW>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2PairPer * 4))
-    SATTR(1); SATTR(2); SATTR(4);
-#undef SATTR
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<uint64_t, TableDirect<true>, kP2MidPer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2MidPer * 8));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<uint64_t, TableDirect<false>, kP2MidPer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2MidPer * 8));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<uint32_t, TableDirect<true>, kP2PairPer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2PairPer * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<uint32_t, TableDirect<false>, kP2PairPer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2PairPer * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_scatter_sorted_kernel<uint32_t, kP2PairPer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2PairPer * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_scatter_sorted_kernel<uint64_t, 14>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * 14 * 8));
-    const int gl = kG64Chunk * 10;
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_granule64_kernel<true, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, gl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_granule64_kernel<false, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, gl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_granule64_kernel<true, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, gl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_granule64_kernel<false, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, gl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_granule64_kernel<false, false, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, gl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_granule64_kernel<false, false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, gl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_granule64_kernel<false, false, kHashXS>, hipFuncAttributeMaxDynamicSharedMemorySize, gl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_granule64_kernel<true, false, kHashXS>, hipFuncAttributeMaxDynamicSharedMemorySize, gl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<u128, WideDirect<true>, kP2WidePer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2WidePer * 16));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<u128, WideDirect<false>, kP2WidePer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2WidePer * 16));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_scatter_sorted_kernel<u128, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * 7 * 16));
-    const int wl = kWideChunk * 18 + 16 * 2048, wt = 16 << kMaxTileBits;
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_wide_granule_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_wide_granule_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_wide_granule_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_wide_granule_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_wide_granule_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_wide_granule_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wl));
-    HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wt));
-    HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wt));
-    HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_wide_pipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wt));
-    HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_wide_pipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wt));
-    const int np = (int)p1_nword_lds(32), ntl = 32 << kNTileBits;
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_nword_granule_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, np));
-    HIP_TRY(hipFuncSetAttribute((const void*)p1_nword_granule_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, np));
-    HIP_TRY(hipFuncSetAttribute((const void*)p2_scatter_sorted_kernel<u256, kP2NWordPer>, hipFuncAttributeMaxDynamicSharedMemorySize, kPBlock * kP2NWordPer * 32));
-    HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_nword_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ntl));
-    HIP_TRY(hipFuncSetAttribute((const void*)tile_insert_nword_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ntl));
-  }
   rc = jfgpu_clear(t.get());
   if(rc) { t->stream.sync(); return rc; }      // (drained before the handle goes, like every destroy path)
   *out = t.release();
@@ -1033,7 +902,7 @@ static int add_keys_piece(jfgpu_table* t, const uint64_t* d_keys, size_t n, uint
     else             hipLaunchKernelGGL(add_keys_one_kernel<false>, dim3(grid), dim3(kBlock), 0, t->stream, t->dt, d_keys, (uint64_t)n);
   } else {
     with_view(t, [&](const auto& T) {
-      hipLaunchKernelGGL(add_keys_kernel, dim3(grid), dim3(kBlock), 0, t->stream, T, d_keys, (uint64_t)n, t->key_words, val, d_is_new);
+      hipLaunchKernelGGL(add_keys_kernel<std::decay_t<decltype(T)>>, dim3(grid), dim3(kBlock), 0, t->stream, T, d_keys, (uint64_t)n, t->key_words, val, d_is_new);
     });
   }
   HIP_TRY(hipGetLastError());
@@ -1098,7 +967,7 @@ int jfgpu_add_key_vals(jfgpu_table* t, const uint64_t* keys, const uint64_t* val
     t->pristine = false;
     const dim3 grid(grid_for(t, take / kBlock + 1)), block(kBlock);
     with_view(t, [&](const auto& T) {
-      hipLaunchKernelGGL(add_pairs_kernel, grid, block, 0, t->stream, T, (const uint64_t*)(d_k + off * kw), (const uint64_t*)(d_v + off), (uint64_t)take, t->key_words);
+      hipLaunchKernelGGL(add_pairs_kernel<std::decay_t<decltype(T)>>, grid, block, 0, t->stream, T, (const uint64_t*)(d_k + off * kw), (const uint64_t*)(d_v + off), (uint64_t)take, t->key_words);
     });
     if(hipGetLastError() != hipSuccess) return done(fail(JFGPU_E_HIP, "add_key_vals: launch"));
     off += (size_t)take;
@@ -1117,7 +986,7 @@ int jfgpu_lookup_dev(jfgpu_table* t, const uint64_t* d_keys, size_t n, uint64_t*
   const int grid = grid_for(t, (n + kBlock - 1) / kBlock);
   ProfScope ps(t, 3, n);
   with_view(t, [&](const auto& T) {
-    hipLaunchKernelGGL(lookup_kernel, dim3(grid), dim3(kBlock), 0, t->stream, T, d_keys, (uint64_t)n, t->key_words, d_vals, d_found, (int)(c[CTR_OVF_USED] != 0));
+    hipLaunchKernelGGL(lookup_kernel<std::decay_t<decltype(T)>>, dim3(grid), dim3(kBlock), 0, t->stream, T, d_keys, (uint64_t)n, t->key_words, d_vals, d_found, (int)(c[CTR_OVF_USED] != 0));
   });
   HIP_TRY(hipGetLastError());
   return JFGPU_OK;
@@ -1155,8 +1024,9 @@ int jfgpu_query_ascii_dev(jfgpu_table* t, const char* d_bases, size_t n, uint64_
     typedef std::decay_t<decltype(T)> Table;
     typedef KeyOps<Table> K;
     const size_t lds = K::kFwdLdsWords ? 0 : query_lds_bytes(t->g.nbytes, K::kHaloWords);
-    hipLaunchKernelGGL(query_ascii_kernel<Table>, dim3(grid), dim3(kBlock), lds, t->stream, T, base, lo, hi, d_vals, d_flags, (int)(c[CTR_OVF_USED] != 0));
+    rc = launch_lds(query_ascii_kernel<Table>, dim3(grid), dim3(kBlock), lds, t->stream, T, base, lo, hi, d_vals, d_flags, (int)(c[CTR_OVF_USED] != 0));
   });
+  if(rc) return rc;
   HIP_TRY(hipGetLastError());
   return JFGPU_OK;
 }
@@ -1291,7 +1161,9 @@ int dump_next_chunk(jfgpu_table* t, uint64_t capacity_records, uint64_t* n_read)
   std::vector<uint64_t> offs(ntile);
   for(uint64_t i = 0; i < ntile; ++i) offs[i] = t->dump_prefix[t0 + i] - t->dump_prefix[t0];
   HIP_TRY(hipMemcpyAsync(t->d_tile_off, offs.data(), ntile * sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
-  with_view(t, [&](const auto& T) { launch_dump(t, T, t0, ntile, key_bytes); });
+  int rc = JFGPU_OK;
+  with_view(t, [&](const auto& T) { rc = launch_dump(t, T, t0, ntile, key_bytes); });
+  if(rc) return rc;
   HIP_TRY(hipGetLastError());
   t->dump_tile_cursor = t1;
   *n_read = nrec;

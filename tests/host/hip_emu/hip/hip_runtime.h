@@ -22,6 +22,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -73,6 +74,17 @@ inline long& live_events() { static long v = 0; return v; }
 inline size_t mem_total() { const char* e = getenv("JFGPU_EMU_MEM_MB"); return (size_t)(e ? atol(e) : 49152) << 20; }
 inline int n_cus() { const char* e = getenv("JFGPU_EMU_CUS"); const int v = e ? atoi(e) : 2; return v > 0 ? v : 2; }
 struct AllocHeader { size_t bytes; size_t magic; char pad[256 - 2 * sizeof(size_t)]; };
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize): the largest value per function and the number of calls, for launch() to
+// enforce and for tests to read (tests/host/launch_check.cc)
+struct FuncAttrs { std::mutex mu; std::map<const void*, size_t> limit; long calls = 0; };
+inline FuncAttrs& func_attrs() { static FuncAttrs* a = new FuncAttrs; return *a; }
+inline size_t func_lds_limit(const void* f) {
+  FuncAttrs& a = func_attrs();
+  std::lock_guard<std::mutex> lk(a.mu);
+  const auto it = a.limit.find(f);
+  return it == a.limit.end() ? 0 : it->second;
+}
+inline long func_attr_calls() { FuncAttrs& a = func_attrs(); std::lock_guard<std::mutex> lk(a.mu); return a.calls; }
 }  // namespace hip_emu
 
 static inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory (emu)" : "error (emu)"; }
@@ -146,7 +158,15 @@ static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; --hip_emu::li
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t = nullptr) { e->t_ms = hip_emu::now_ms(); return hipSuccess; }
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { *ms = (float)(b->t_ms - a->t_ms); return hipSuccess; }
-static inline hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
+static inline hipError_t hipFuncSetAttribute(const void* f, hipFuncAttribute, int v) {
+  if(!f || v < 0) return hipErrorInvalidValue;
+  hip_emu::FuncAttrs& a = hip_emu::func_attrs();
+  std::lock_guard<std::mutex> lk(a.mu);
+  ++a.calls;
+  size_t& have = a.limit[f];
+  if((size_t)v > have) have = (size_t)v;
+  return hipSuccess;
+}
 
 // ---------------------------------------------------------------- fibers
 extern "C" void hip_emu_switch(void** save_sp, void* new_sp);
@@ -185,6 +205,9 @@ struct Fiber {
 };
 constexpr size_t kStackBytes = 256 << 10;
 constexpr size_t kDynLdsBytes = 160 << 10;
+// Dynamic LDS beyond this needs the function's limit raised first (hipFuncSetAttribute).  64 KiB is the line the engine itself
+// draws (kmer_core.hpp; "needs > 64 KiB" at the dump kernel); where the runtime of an MI355X really refuses has not been measured.
+constexpr size_t kDynLdsFree = 64 << 10;
 
 struct BlockRun {
   std::vector<Fiber> fibers;
@@ -267,8 +290,18 @@ inline void run_block(BlockRun& R, unsigned nthreads) {
 
 template <typename F> inline void invoke_thunk(const void* p) { (*(const F*)p)(); }
 
+// (one per launching thread, gone with it: the ABI may be called from threads that end)
+struct OwnRun {
+  BlockRun* R = nullptr;
+  ~OwnRun() {
+    if(!R) return;
+    for(Fiber& f : R->fibers) if(f.stack) munmap(f.stack, kStackBytes);
+    free(R->dyn_lds); delete R;
+  }
+};
 inline BlockRun* my_run() {
-  static thread_local BlockRun* R = nullptr;
+  static thread_local OwnRun own;
+  BlockRun*& R = own.R;
   if(!R) { R = new BlockRun; R->fibers.resize(1024); R->dyn_lds = (unsigned char*)aligned_alloc(256, kDynLdsBytes); }
   return R;
 }
@@ -332,10 +365,15 @@ struct Pool {
 inline Pool& pool() { static Pool* p = new Pool; return *p; }
 
 template <typename F>
-inline void launch(dim3 grid, dim3 block, size_t dyn_lds_bytes, const F& body) {
+inline void launch(const void* kern, dim3 grid, dim3 block, size_t dyn_lds_bytes, const F& body) {
   const unsigned nthreads = block.x * block.y * block.z;
   if(nthreads == 0 || nthreads > 1024) { fprintf(stderr, "hip_emu: bad block size %u\n", nthreads); abort(); }
   if(dyn_lds_bytes > kDynLdsBytes) { fprintf(stderr, "hip_emu: %zu bytes of dynamic LDS requested (> 160 KiB)\n", dyn_lds_bytes); abort(); }
+  if(dyn_lds_bytes > kDynLdsFree && func_lds_limit(kern) < dyn_lds_bytes) {
+    fprintf(stderr, "hip_emu: %zu bytes of dynamic LDS requested (> 64 KiB) from a function whose limit was raised to %zu only "
+                    "(hipFuncSetAttribute: launch through launch_lds)\n", dyn_lds_bytes, func_lds_limit(kern));
+    abort();
+  }
   Job J;
   J.grid = grid; J.block = block; J.nthreads = nthreads; J.body = &body; J.invoke = &invoke_thunk<F>;
   J.total = (uint64_t)grid.x * grid.y * grid.z;
@@ -399,7 +437,7 @@ template <typename T> inline T lane_read(T v, int src) {
 #define gridDim (::hip_emu::tls_run()->grid_dim)
 
 #define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) \
-  ::hip_emu::launch(dim3(grid), dim3(block), (size_t)(lds), [&]() { kern(__VA_ARGS__); })
+  ::hip_emu::launch((const void*)(kern), dim3(grid), dim3(block), (size_t)(lds), [&]() { kern(__VA_ARGS__); })
 
 // ---------------------------------------------------------------- device builtins
 static inline void __syncthreads() { ::hip_emu::block_barrier(); }

@@ -71,21 +71,6 @@ struct DevBufs {
 
 void say(char* dst, size_t len, const std::string& s) { if(dst && len) { strncpy(dst, s.c_str(), len - 1); dst[len - 1] = 0; } }
 
-int kt_ring_attrs() {
-  static bool done = false;
-  if(done) return JFGPU_OK;
-  const int rl = kGranMaxB * 128 + 128;                         // (the engine's own value: jfgpu_create)
-  HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_kernel<RecordDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-#define KT_A(NV, PD) HIP_TRY(hipFuncSetAttribute((const void*)p2_ring_roles_kernel<uint32_t, NV, RecordDirect, PD>, hipFuncAttributeMaxDynamicSharedMemorySize, rl))
-  KT_A(1, 1); KT_A(1, 2); KT_A(1, 3); KT_A(2, 1); KT_A(2, 2); KT_A(2, 3);
-#undef KT_A
-#define KT_A(N, CN) HIP_TRY(hipFuncSetAttribute((const void*)p1_ring_kernel<uint32_t, false, N, CN, RecordDirect>, hipFuncAttributeMaxDynamicSharedMemorySize, rl))
-  KT_A(0, 2); KT_A(6, 0); KT_A(6, 1); KT_A(kHashXSLow, 2);
-#undef KT_A
-  done = true;
-  return JFGPU_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -156,7 +141,6 @@ int jfkt_p2(jfgpu_table* t, int kernel, int nv, int pd, uint32_t b2e, uint32_t t
       if(sh[s] == 1 && (a % 4)) return fail(JFGPU_E_INVALID, "jfkt_p2: a granule region starts at a multiple of 16 bytes");
     }
   }
-  KT_TRY(kt_ring_attrs());
   DevBufs D;
   SegList S; memset(&S, 0, sizeof S);
   S.n = n_seg;
@@ -178,14 +162,14 @@ int jfkt_p2(jfgpu_table* t, int kernel, int nv, int pd, uint32_t b2e, uint32_t t
   const RecordDirect pd_{d_rec, d_nrec, rec_cap};
   const size_t lds = ((size_t)1 << b2e) * 128 + 128;                              // (launch_p2_rings)
   std::string name;
-#define KT_P2R(NV, PD) do { hipLaunchKernelGGL((p2_ring_roles_kernel<uint32_t, NV, RecordDirect, PD>), dim3(nbk), dim3(kPBlock), lds, t->stream, pd_, b2e, tag_bits, S, cap, d_gcur, d_out, bucket0, d_strag, d_strag_n, d_ctr); \
+#define KT_P2R(NV, PD) do { KT_TRY(launch_lds(p2_ring_roles_kernel<uint32_t, NV, RecordDirect, PD>, dim3(nbk), dim3(kPBlock), lds, t->stream, pd_, b2e, tag_bits, S, cap, d_gcur, d_out, bucket0, d_strag, d_strag_n, d_ctr)); \
                             name = "p2_ring_roles_kernel<uint32_t," #NV ",RecordDirect," #PD ">"; } while(0)
   if(kernel == 0 && nv == 2) { if(pd == 1) KT_P2R(2, 1); else if(pd == 2) KT_P2R(2, 2); else KT_P2R(2, 3); }
   else if(kernel == 0) { if(pd == 1) KT_P2R(1, 1); else if(pd == 2) KT_P2R(1, 2); else KT_P2R(1, 3); }
 #undef KT_P2R
   else {
-    hipLaunchKernelGGL((p2_ring_kernel<RecordDirect>), dim3(kG2Blocks, nbk), dim3(kPBlock), lds, t->stream, pd_, b2e, tag_bits, S, cap, d_gcur, d_gcur + n_dest,
-                       d_out, bucket0, (unsigned long long*)nullptr, d_strag, d_strag_n, d_ctr);
+    KT_TRY(launch_lds(p2_ring_kernel<RecordDirect>, dim3(kG2Blocks, nbk), dim3(kPBlock), lds, t->stream, pd_, b2e, tag_bits, S, cap, d_gcur, d_gcur + n_dest,
+                       d_out, bucket0, (unsigned long long*)nullptr, d_strag, d_strag_n, d_ctr));
     name = "p2_ring_kernel<RecordDirect>";
   }
   HIP_TRY(hipGetLastError());
@@ -234,8 +218,8 @@ int jfkt_tile(jfgpu_table* t, int tpb, int heavy, int sample, int holes, uint32_
   const bool rt = t->returning;
   std::string name;
 #define KT_T(I, SL, P, H, M, HL) do { \
-    if(rt) hipLaunchKernelGGL((tile_rank_insert_kernel<I, true, SL, P, kTileBlock, H, M, HL>), g, block, lds, t->stream, t->dt, S, tile0, n_units); \
-    else   hipLaunchKernelGGL((tile_rank_insert_kernel<I, false, SL, P, kTileBlock, H, M, HL>), g, block, lds, t->stream, t->dt, S, tile0, n_units); \
+    if(rt) KT_TRY(launch_lds(tile_rank_insert_kernel<I, true, SL, P, kTileBlock, H, M, HL>, g, block, lds, t->stream, t->dt, S, tile0, n_units)); \
+    else   KT_TRY(launch_lds(tile_rank_insert_kernel<I, false, SL, P, kTileBlock, H, M, HL>, g, block, lds, t->stream, t->dt, S, tile0, n_units)); \
     name = std::string("tile_rank_insert_kernel<" #I ",") + (rt ? "true" : "false") + "," #SL "," #P ",kTileBlock," #H "," #M "," #HL ">"; } while(0)
 #define KT_TV(I, SL, P) do { if(heavy) KT_T(I, SL, P, true, false, true); else if(sample) KT_T(I, SL, P, false, true, true); else KT_T(I, SL, P, false, false, true); } while(0)
   if(!holes) { if(sample) KT_T(uint32_t, unsigned int, 2, false, true, false); else KT_T(uint32_t, unsigned int, 2, false, false, false); }
@@ -276,7 +260,6 @@ int jfkt_p1(jfgpu_table* t, int variant, uint32_t b1, const uint8_t* bases, uint
   if(variant == 1 && t->g.nbytes != 6) return fail(JFGPU_E_INVALID, "jfkt_p1: NB = 6 needs keys of six bytes");
   if(variant == 2 && !t->g.hash_xs) return fail(JFGPU_E_INVALID, "jfkt_p1: the table's matrix is not the xor-shift one");
   if(variant == 2 && t->g.lsize_g > 32) return fail(JFGPU_E_INVALID, "jfkt_p1: kHashXSLow is for positions of at most 32 bits");
-  KT_TRY(kt_ring_attrs());
   const uint32_t nb = 1u << b1;
   DevBufs D;
   uint8_t* d_bases; uint32_t *d_out, *d_strag_n; unsigned int* d_gcur; unsigned long long *d_tot, *d_nrec; uint64_t *d_strag, *d_rec;
@@ -293,7 +276,7 @@ int jfkt_p1(jfgpu_table* t, int variant, uint32_t b1, const uint8_t* bases, uint
   const RecordDirect od{d_rec, d_nrec, rec_cap};
   const size_t lds = (size_t)nb * 128 + 128;                                      // (part_ingest)
   std::string name;
-#define KT_P1(N, CN) do { hipLaunchKernelGGL((p1_ring_kernel<uint32_t, false, N, CN, RecordDirect>), dim3(grid), dim3(kPBlock), lds, t->stream, t->dt, od, P, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, d_strag, d_strag_n); \
+#define KT_P1(N, CN) do { KT_TRY(launch_lds(p1_ring_kernel<uint32_t, false, N, CN, RecordDirect>, dim3(grid), dim3(kPBlock), lds, t->stream, t->dt, od, P, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, d_strag, d_strag_n)); \
                           name = "p1_ring_kernel<uint32_t,false," #N "," #CN ",RecordDirect>"; } while(0)
   if(variant == 0) KT_P1(0, 2);
   else if(variant == 1) { if(t->g.canonical) KT_P1(6, 1); else KT_P1(6, 0); }
@@ -386,8 +369,7 @@ int jfkt_p2_sort(jfgpu_table* t, int scheme, uint32_t item_bytes, int pair, uint
 #define KT_G(I, PER) do { \
       const RecordDirectT<I> rd{d_rec, d_nrec, rec_cap, d_ctr, b2e, tag_bits}; \
       const size_t lds = (size_t)kPBlock * PER * sizeof(I); \
-      HIP_TRY(hipFuncSetAttribute((const void*)p2_granule_kernel<I, RecordDirectT<I>, PER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      hipLaunchKernelGGL((p2_granule_kernel<I, RecordDirectT<I>, PER>), g1p, block, lds, t->stream, rd, b2e, tag_bits, S, cap, d_gcur, d_gcur + n_dest, (I*)d_out, bucket0); \
+      KT_TRY(launch_lds(p2_granule_kernel<I, RecordDirectT<I>, PER>, g1p, block, lds, t->stream, rd, b2e, tag_bits, S, cap, d_gcur, d_gcur + n_dest, (I*)d_out, bucket0, (unsigned long long*)nullptr, 0xFFFFFFFFu)); \
       name = "p2_granule_kernel<" #I ",RecordDirectT<" #I ">," #PER ">"; } while(0)
     if(item_bytes == 4) KT_G(uint32_t, kP2PairPer); else if(item_bytes == 8) KT_G(uint64_t, kP2MidPer); else KT_G(u128, kP2WidePer);
 #undef KT_G
@@ -411,7 +393,7 @@ int jfkt_p2_sort(jfgpu_table* t, int scheme, uint32_t item_bytes, int pair, uint
 #define KT_X(I, PER) do { \
       hipLaunchKernelGGL((p2_kernel<I, false>), grid, block, 0, t->stream, pg2, tag_bits, S, d_M2, (const uint64_t*)d_goff, (I*)d_out, bucket0); \
       hipLaunchKernelGGL(scan_matrix_kernel, dim3(nbk), dim3(1024), 0, t->stream, d_M2, (uint32_t)g2, nb2e, (const uint64_t*)d_base, d_goff, bucket0); \
-      hipLaunchKernelGGL((p2_scatter_sorted_kernel<I, PER>), grid, block, (size_t)kPBlock * PER * sizeof(I), t->stream, pg2, tag_bits, S, (const uint32_t*)d_M2, (const uint64_t*)d_goff, (I*)d_out, bucket0); \
+      KT_TRY(launch_lds(p2_scatter_sorted_kernel<I, PER>, grid, block, (size_t)kPBlock * PER * sizeof(I), t->stream, pg2, tag_bits, S, (const uint32_t*)d_M2, (const uint64_t*)d_goff, (I*)d_out, bucket0)); \
       name = "p2_kernel<" #I ",false>+scan_matrix_kernel+p2_scatter_sorted_kernel<" #I "," #PER ">"; } while(0)
     if(item_bytes == 4 && pair) KT_X(uint32_t, kP2PairPer); else if(item_bytes == 4) KT_X(uint32_t, 16); else if(item_bytes == 8) KT_X(uint64_t, 14); else KT_X(u128, 7);
 #undef KT_X
@@ -460,7 +442,7 @@ int jfkt_p1_wide(jfgpu_table* t, uint32_t b1, const uint8_t* bases, uint64_t n_b
   const size_t wlds = (size_t)kWideChunk * 18 + (size_t)t->g.nbytes * 2048;         // (part_ingest)
   const bool xs = t->g.hash_xs != 0;
   std::string name;
-#define KT_PW(RT, X) do { hipLaunchKernelGGL((p1_wide_granule_kernel<RT, false, X>), dim3(grid), dim3(kPBlock), wlds, t->stream, t->wt, P, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, (u128*)d_out); \
+#define KT_PW(RT, X) do { KT_TRY(launch_lds(p1_wide_granule_kernel<RT, false, X>, dim3(grid), dim3(kPBlock), wlds, t->stream, t->wt, P, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, (u128*)d_out)); \
                           name = "p1_wide_granule_kernel<" #RT ",false," #X ">"; } while(0)
   if(xs) { if(t->returning) KT_PW(true, true); else KT_PW(false, true); }
   else { if(t->returning) KT_PW(true, false); else KT_PW(false, false); }
@@ -517,13 +499,13 @@ int jfkt_tile_wide(jfgpu_table* t, int kernel, uint32_t n_seg, const void* const
   std::string name;
   if(kernel == 0) {
     const dim3 g(std::min(grid, n_units)), block(kPBlock);
-    if(rt) hipLaunchKernelGGL(tile_insert_wide_kernel<true>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units);
-    else   hipLaunchKernelGGL(tile_insert_wide_kernel<false>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units);
+    if(rt) KT_TRY(launch_lds(tile_insert_wide_kernel<true>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units));
+    else   KT_TRY(launch_lds(tile_insert_wide_kernel<false>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units));
     name = std::string("tile_insert_wide_kernel<") + r + ">";
   } else if(kernel == 1) {
     const dim3 g(std::min(grid, n_units)), block(kPBlock);
-    if(rt) hipLaunchKernelGGL(tile_insert_wide_pipe_kernel<true>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units);
-    else   hipLaunchKernelGGL(tile_insert_wide_pipe_kernel<false>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units);
+    if(rt) KT_TRY(launch_lds(tile_insert_wide_pipe_kernel<true>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units));
+    else   KT_TRY(launch_lds(tile_insert_wide_pipe_kernel<false>, g, block, tile_lds, t->stream, t->wt, S, tile0, n_units));
     name = std::string("tile_insert_wide_pipe_kernel<") + r + ">";
   } else {
     const dim3 g(grid), block(kBlock);
@@ -548,32 +530,13 @@ int jfkt_tile_wide(jfgpu_table* t, int kernel, uint32_t n_seg, const void* const
 // BloomRingDirect, BloomP1RingDirect): what they do IS the output here, a side effect on the filter.
 namespace {
 
-int kt_bloom_attrs() {                                          // (the engine's own values: bloom_create)
-  static bool done = false;
-  if(done) return JFGPU_OK;
-  const int pl = (int)((size_t)kBloomChunk * 6 + (size_t)2 * 8 * 2048), pl2 = (int)((size_t)kPBlock * 5 * 6 + (size_t)8 * 512);
-  const int plr = (int)((size_t)512 * kBloomRingBytes + kBloomRingBytes + (size_t)8 * 512), rl = (int)(kGranMaxB * 128 + 128);
-#define KT_A(F, N) HIP_TRY(hipFuncSetAttribute((const void*)F, hipFuncAttributeMaxDynamicSharedMemorySize, N))
-  KT_A(p1_bloom_granule_kernel<0>, pl); KT_A(p1_bloom_granule_kernel<6>, pl); KT_A(p1_bloom_granule_kernel<8>, pl);
-  KT_A(p1_bloom_granule2_kernel<0>, pl2); KT_A(p1_bloom_granule2_kernel<6>, pl2); KT_A(p1_bloom_granule2_kernel<8>, pl2);
-  KT_A((p1_bloom_ring_kernel<0, 10>), plr); KT_A((p1_bloom_ring_kernel<6, 10>), plr); KT_A((p1_bloom_ring_kernel<8, 10>), plr);
-  KT_A((p1_bloom_ring_kernel<0, 5>), plr); KT_A((p1_bloom_ring_kernel<8, 5>), plr);
-  KT_A(bloom_segment_kernel, 1 << kBloomSegBits);
-  KT_A((p2_granule_kernel<uint32_t, BloomDirect, kP2PairPer>), kPBlock * kP2PairPer * 4);
-  KT_A(p2_ring_kernel<BloomRingDirect>, rl);
-  KT_A((p2_ring_roles_kernel<uint32_t, 2, BloomRingDirect, 3>), rl);
-#undef KT_A
-  done = true;
-  return JFGPU_OK;
-}
-
 int kt_bloom_use(jfgpu_bloom* b, const BloomPart& BP, const char* who) {
   int rc = use_b(b); if(rc) return rc;
   if(b->kind != 0 || !b->part_ok || b->mode != 1 || !b->pending.empty() || b->wide || b->nword)
     return fail(JFGPU_E_INVALID, std::string(who) + ": a Bloom counter of one-word keys with whole segments, in mode 1, nothing pending");
   if(BP.n_seg != b->bp.n_seg || BP.b1 > 10 || BP.b2 > 11 || ((uint64_t)1 << (BP.b1 + BP.b2)) < BP.n_seg)
     return fail(JFGPU_E_INVALID, std::string(who) + ": n_seg is the filter's own, b1 <= 10, b2 <= 11, n_seg <= 2^(b1 + b2)");
-  return kt_bloom_attrs();
+  return JFGPU_OK;
 }
 
 // a cell update the kernels may be given: digit below five, (with `bucket`) a segment of the filter
@@ -637,11 +600,11 @@ int jfkt_bloom_p1(jfgpu_bloom* b, int family, int nbt, int per, uint32_t b1, uin
   const size_t lds2 = (size_t)nb * kBloomRingBytes + kBloomRingBytes + nby * 512;
   const BloomP1RingDirect rd{B.data, b2};
   std::string name;
-#define KT_PB(N) do { hipLaunchKernelGGL(p1_bloom_granule_kernel<N>, dim3(grid), dim3(kPBlock), lds0, b->stream, B, BP, b->g, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, b->d_mers); \
+#define KT_PB(N) do { KT_TRY(launch_lds(p1_bloom_granule_kernel<N>, dim3(grid), dim3(kPBlock), lds0, b->stream, B, BP, b->g, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, b->d_mers)); \
                       name = "p1_bloom_granule_kernel<" #N ">"; } while(0)
-#define KT_PB2(N) do { hipLaunchKernelGGL(p1_bloom_granule2_kernel<N>, dim3(grid), dim3(kPBlock), lds1, b->stream, B, BP, b->g, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, b->d_mers); \
+#define KT_PB2(N) do { KT_TRY(launch_lds(p1_bloom_granule2_kernel<N>, dim3(grid), dim3(kPBlock), lds1, b->stream, B, BP, b->g, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, b->d_mers)); \
                        name = "p1_bloom_granule2_kernel<" #N ">"; } while(0)
-#define KT_PBR(N, PER) do { hipLaunchKernelGGL((p1_bloom_ring_kernel<N, PER>), dim3(grid), dim3(kPBlock), lds2, b->stream, B, BP, b->g, rd, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, b->d_mers, d_strag, d_strag_n); \
+#define KT_PBR(N, PER) do { KT_TRY(launch_lds(p1_bloom_ring_kernel<N, PER>, dim3(grid), dim3(kPBlock), lds2, b->stream, B, BP, b->g, rd, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, d_out, b->d_mers, d_strag, d_strag_n)); \
                             name = "p1_bloom_ring_kernel<" #N "," #PER ">"; } while(0)
   if(family == 0) { if(nbt == 8) KT_PB(8); else if(nbt == 6) KT_PB(6); else KT_PB(0); }
   else if(family == 1) { if(nbt == 8) KT_PB2(8); else if(nbt == 6) KT_PB2(6); else KT_PB2(0); }
@@ -698,7 +661,7 @@ int jfkt_bloom_seg(jfgpu_bloom* b, uint32_t n_arr, const uint32_t* const* seg_it
     KT_TRY(D.put(&doff, seg_off[s], (size_t)n_off[s]));
     S.items[s] = di; S.off[s] = doff; S.sh[s] = sh[s];
   }
-  hipLaunchKernelGGL(bloom_segment_kernel, dim3(grid), dim3(kPBlock), (size_t)1 << kBloomSegBits, b->stream, b->view(), S, n_seg, seg0);
+  KT_TRY(launch_lds(bloom_segment_kernel, dim3(grid), dim3(kPBlock), (size_t)1 << kBloomSegBits, b->stream, b->view(), S, n_seg, seg0));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(b->stream));
   say(launched, launched_len, "bloom_segment_kernel");
@@ -784,17 +747,17 @@ int jfkt_bloom_p2(jfgpu_bloom* b, int kernel, uint32_t b1, uint32_t b2, uint32_t
   const size_t rl = ((size_t)1 << b2) * 128 + 128;
   std::string name;
   if(kernel == 0) {
-    hipLaunchKernelGGL((p2_granule_kernel<uint32_t, BloomDirect, kP2PairPer>), dim3(kG2Blocks, nbk), block, (size_t)kPBlock * kP2PairPer * sizeof(uint32_t), b->stream,
-                       DD, b2, kBloomItemLow, S, cap2, d_gcur, d_gcur + n_dest, d_out, bucket0);
+    KT_TRY(launch_lds(p2_granule_kernel<uint32_t, BloomDirect, kP2PairPer>, dim3(kG2Blocks, nbk), block, (size_t)kPBlock * kP2PairPer * sizeof(uint32_t), b->stream,
+                       DD, b2, kBloomItemLow, S, cap2, d_gcur, d_gcur + n_dest, d_out, bucket0, (unsigned long long*)nullptr, 0xFFFFFFFFu));
     name = "p2_granule_kernel<uint32_t,BloomDirect,kP2PairPer>";
   } else {
     if(kernel == 1) {
-      hipLaunchKernelGGL((p2_ring_roles_kernel<uint32_t, 2, BloomRingDirect, 3>), dim3(nbk), block, rl, b->stream, RD, b2, kBloomItemLow, S, cap2, d_gcur,
-                         d_out, bucket0, d_strag, d_strag_n, d_ctr);
+      KT_TRY(launch_lds(p2_ring_roles_kernel<uint32_t, 2, BloomRingDirect, 3>, dim3(nbk), block, rl, b->stream, RD, b2, kBloomItemLow, S, cap2, d_gcur,
+                         d_out, bucket0, d_strag, d_strag_n, d_ctr));
       name = "p2_ring_roles_kernel<uint32_t,2,BloomRingDirect,3>";
     } else {
-      hipLaunchKernelGGL((p2_ring_kernel<BloomRingDirect>), dim3(kG2Blocks, nbk), block, rl, b->stream, RD, b2, kBloomItemLow, S, cap2, d_gcur, d_gcur + n_dest,
-                         d_out, bucket0, (unsigned long long*)nullptr, d_strag, d_strag_n, d_ctr);
+      KT_TRY(launch_lds(p2_ring_kernel<BloomRingDirect>, dim3(kG2Blocks, nbk), block, rl, b->stream, RD, b2, kBloomItemLow, S, cap2, d_gcur, d_gcur + n_dest,
+                         d_out, bucket0, (unsigned long long*)nullptr, d_strag, d_strag_n, d_ctr));
       name = "p2_ring_kernel<BloomRingDirect>";
     }
     HIP_TRY(hipGetLastError());

@@ -121,8 +121,8 @@ int jfktn_p1(jfgpu_table* t, uint32_t b1, const uint8_t* bases, uint64_t n_bases
   uint64_t c0[CTR_COUNT], c1[CTR_COUNT];
   KTN_TRY(read_counters(t, c0));
   const size_t lds = p1_nword_lds(t->g.nbytes);                                      // (p1_plan)
-  if(t->returning) hipLaunchKernelGGL(p1_nword_granule_kernel<true>, dim3(grid), dim3(kPBlock), lds, t->stream, t->nt, P, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, (u256*)d_out);
-  else             hipLaunchKernelGGL(p1_nword_granule_kernel<false>, dim3(grid), dim3(kPBlock), lds, t->stream, t->nt, P, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, (u256*)d_out);
+  if(t->returning) KTN_TRY(launch_lds(p1_nword_granule_kernel<true>, dim3(grid), dim3(kPBlock), lds, t->stream, t->nt, P, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, (u256*)d_out));
+  else             KTN_TRY(launch_lds(p1_nword_granule_kernel<false>, dim3(grid), dim3(kPBlock), lds, t->stream, t->nt, P, (const uint8_t*)d_bases, lo, hi, cap, d_gcur, d_tot, (u256*)d_out));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(t->stream));
   t->pristine = false;
@@ -166,8 +166,8 @@ int jfktn_p2(jfgpu_table* t, uint32_t b2e, uint32_t tag_bits, uint32_t n_seg, co
   const dim3 grid(g2, nbk), block(kPBlock);
   hipLaunchKernelGGL((p2_kernel<u256, false>), grid, block, 0, t->stream, pg2, tag_bits, S, d_M2, (const uint64_t*)d_goff, (u256*)d_out, bucket0);
   hipLaunchKernelGGL(scan_matrix_kernel, dim3(nbk), dim3(1024), 0, t->stream, d_M2, (uint32_t)g2, nb2e, (const uint64_t*)d_base, d_goff, bucket0);
-  hipLaunchKernelGGL((p2_scatter_sorted_kernel<u256, kP2NWordPer>), grid, block, (size_t)kPBlock * kP2NWordPer * sizeof(u256), t->stream, pg2, tag_bits, S,
-                     (const uint32_t*)d_M2, (const uint64_t*)d_goff, (u256*)d_out, bucket0);
+  KTN_TRY(launch_lds(p2_scatter_sorted_kernel<u256, kP2NWordPer>, grid, block, (size_t)kPBlock * kP2NWordPer * sizeof(u256), t->stream, pg2, tag_bits, S,
+                     (const uint32_t*)d_M2, (const uint64_t*)d_goff, (u256*)d_out, bucket0));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(t->stream));
   HIP_TRY(hipMemcpy(goff, d_goff, ((size_t)n_dest + 1) * 8, hipMemcpyDeviceToHost));
@@ -201,8 +201,8 @@ int jfktn_tile(jfgpu_table* t, int kernel, uint32_t n_seg, const void* const* se
   if(kernel == 0) {
     const dim3 g(std::min(grid, n_units)), block(kNTileBlock);
     const size_t tile_lds = (size_t)32 << t->g.tile_bits;                             // (launch_tile_kernel)
-    if(rt) hipLaunchKernelGGL(tile_insert_nword_kernel<true>, g, block, tile_lds, t->stream, t->nt, S, tile0, n_units);
-    else   hipLaunchKernelGGL(tile_insert_nword_kernel<false>, g, block, tile_lds, t->stream, t->nt, S, tile0, n_units);
+    if(rt) KTN_TRY(launch_lds(tile_insert_nword_kernel<true>, g, block, tile_lds, t->stream, t->nt, S, tile0, n_units));
+    else   KTN_TRY(launch_lds(tile_insert_nword_kernel<false>, g, block, tile_lds, t->stream, t->nt, S, tile0, n_units));
     name = std::string("tile_insert_nword_kernel<") + (rt ? "true" : "false") + ">";
   } else {
     const dim3 g(grid), block(kBlock);

@@ -3,6 +3,7 @@
 #   make engine     -> jellyfish_amd/lib/libjfgpu.so   (hipcc cross-compiles without a GPU)
 #   make kernel-harness -> tests/kernels/_build/libjfgpu_kt.so   (the stage tests' library; not product)
 #   make kernel-harness-nword -> tests/kernels/_build/libjfgpu_ktn.so   (the same for the keys of three and four words)
+#   make kernel-harness-bloom-keys -> tests/kernels/_build/libjfgpu_ktbk.so   (P1b of the Bloom insert for keys of two to four words)
 HIPCC    ?= hipcc
 CXX      ?= g++
 ARCH     ?= gfx950
@@ -35,6 +36,14 @@ $(KTDIR)/libjfgpu_ktn.so: tests/kernels/stage_harness_nword.hip $(wildcard $(CSR
 	@mkdir -p $(KTDIR)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ tests/kernels/stage_harness_nword.hip -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
+# ... and P1b of the partitioned Bloom insert for keys of two to four words (tests/kernels/stage_harness_bloom_keys.hip;
+# tests/test_gpu_stage_bloom_p1_keys.py)
+kernel-harness-bloom-keys: $(KTDIR)/libjfgpu_ktbk.so
+
+$(KTDIR)/libjfgpu_ktbk.so: tests/kernels/stage_harness_bloom_keys.hip $(wildcard $(CSRC)/*.hip) $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/*.inl) include/jfgpu.h
+	@mkdir -p $(KTDIR)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ tests/kernels/stage_harness_bloom_keys.hip -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+
 cli: bin/jellyfish-amd
 
 bin/jellyfish-amd: $(wildcard jellyfish_amd/cli/*.cc) $(wildcard jellyfish_amd/include/jellyfish_amd/*.hpp) include/jfgpu.h $(LIBDIR)/libjfgpu.so
@@ -48,4 +57,4 @@ oracle:
 
 clean:
 	rm -rf $(LIBDIR) bin oracle/_build $(KTDIR)
-.PHONY: all engine cli oracle clean kernel-harness kernel-harness-nword
+.PHONY: all engine cli oracle clean kernel-harness kernel-harness-nword kernel-harness-bloom-keys

@@ -246,9 +246,10 @@ int  jfgpu_dump_end(jfgpu_table* t);
 /* ---- Bloom counter: `jellyfish bc` and `count --bc` (BASELINE config 3) -------------------
  * Mer lengths 1 to 128, like the reference's mer_dna_bloom_counter (two 64 x 2k matrices over mer_dna): every entry point
  * below -- jfgpu_bc_create, jfgpu_bf_create, the inserts, jfgpu_bc_keys, jfgpu_attach_bloom -- takes them all on one GPU.
- * Above 64 bases (keys of three and four words) the insert is the direct one (jfgpu_bc_set_mode(2) is refused), and a
- * table with a filter attached is refused by the routing and sharded entry points (jfgpu_partition_ascii_dev, the
- * jfgpu_comm_* steps) with JFGPU_E_UNSUPPORTED. */
+ * Both insert strategies (jfgpu_bc_set_mode) exist for every mer length: above 32 bases (keys of two, three and four words) the
+ * partitioned one routes its cell updates with a kernel of its own and shares everything behind it with the shorter mers.
+ * Above 64 bases a table with a filter attached is refused by the routing and sharded entry points
+ * (jfgpu_partition_ascii_dev, the jfgpu_comm_* steps) with JFGPU_E_UNSUPPORTED. */
 typedef struct jfgpu_bloom jfgpu_bloom;   /* opaque: ceil(m/5) bytes of base-3 cells in HBM */
 typedef struct jfgpu_bloom_params {
   uint32_t k, canonical;
@@ -299,7 +300,12 @@ int  jfgpu_bc_query_ascii(jfgpu_bloom* b, const char* bases, size_t n, uint64_t*
 int  jfgpu_bf_create(const jfgpu_bloom_params* p, jfgpu_bloom** out);
 /* How jfgpu_bc_insert_* applies the increments (no reference counterpart; the array is the same either way because the
  * increments saturate and commute): 0 auto, 1 direct (one global compare-and-swap per cell), 2 partitioned (cell updates
- * routed to 64 KiB segments of the array and applied in LDS at the next jfgpu_bc_sync / _read / _keys / attach).
+ * routed to 64 KiB segments of the array and applied in LDS at the next jfgpu_bc_sync / _read / _load / _keys /
+ * _query_ascii / attach).  Mode 2 is accepted for every mer length up to 128 whenever the counter has a segment geometry (a
+ * Bloom counter of at most 128 GiB; a one-pass filter of jfgpu_bf_create has none: JFGPU_E_UNSUPPORTED).  Auto: mers of up
+ * to 32 bases take the partitioned path for batches of 1 MiB and more on counters of 64 segments and more, or while batches
+ * are pending; mers of 33 to 128 bases for batches of 1 MiB and more (profiles/bloom_keys_part_rate.txt: 3.7 and 5.6 times the
+ * direct kernel's rate on 2 Gbp of reads at k = 63 and k = 100); everything else goes direct.
  * jfgpu_bc_reserve sizes the routing workspace up front (default: taken from free memory at the first large batch). */
 int  jfgpu_bc_set_mode(jfgpu_bloom* b, int mode);
 int  jfgpu_bc_reserve(jfgpu_bloom* b, uint64_t workspace_bytes);

@@ -7,7 +7,7 @@ struct jfgpu_bloom {
   Stream stream;                 // (before the buffers used on it: they go first)
   TableGeom g{};                 // only k / key_mask / canonical / nbytes are used (encode side)
   bool wide = false; WideGeom wg{};   // 33 <= k <= 64: two-word keys
-  bool nword = false; NGeom ng{};     // 65 <= k <= 128: keys of three and four words (kernels_nword.hip.hpp), direct path only
+  bool nword = false; NGeom ng{};     // 65 <= k <= 128: keys of three and four words (kernels_nword.hip.hpp)
   uint64_t m = 0; uint32_t nh = 0;
   Gf2Matrix m1, m2;
   DevBuf<uint64_t> d_t1, d_t2;

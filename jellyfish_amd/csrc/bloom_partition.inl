@@ -22,11 +22,12 @@ void bloom_prof_collect(jfgpu_bloom* b) {
   b->spans.clear();
 }
 
-// Segments, bucket bits.  part_ok == false: the direct kernel is the only path (tiny or > 128 GiB filters, keys of two to four words).
+// Segments, bucket bits: the geometry depends on the filter only, never on the key's width.  part_ok == false: the direct
+// kernel is the only path (empty or > 128 GiB filters).
 void bloom_part_init(jfgpu_bloom* b) {
   b->part_ok = false;
   const uint64_t n_seg = (b->data_bytes + ((1ull << kBloomSegBits) - 1)) >> kBloomSegBits;
-  if(b->wide || b->nword || n_seg == 0 || n_seg > (1ull << 21)) return;
+  if(n_seg == 0 || n_seg > (1ull << 21)) return;
   uint32_t sb = 0;
   while((1ull << sb) < n_seg) ++sb;
   uint32_t b1, b2;
@@ -37,9 +38,20 @@ void bloom_part_init(jfgpu_bloom* b) {
   b->part_ok = true;
 }
 
+// Keys of two to four words (33 <= k <= 128), AUTO: the partitioned path for batches of at least kBloomKeysPartMinBytes of
+// sequence -- the smallest batch of the sweep in profiles/bloom_keys_part_rate.txt (one batch of 1 MiB .. 1 GiB of 150 bp
+// reads, k = 63 and k = 100, canonical, a counter of opt_m(0.001, n) cells: 27 segments at 1 MiB) from which mode 2 beats the
+// parent commit's direct kernel by more than the larger of the two spreads: it does from 1 MiB on, 0.35 ms against 0.49 at
+// k = 63 and 0.36 against 0.60 at k = 100, and by 4.1 and 6 times at 1 GiB.  Smaller batches were not measured and stay
+// direct, as they do for one-word keys.  (No floor on the number of segments: the sweep's smallest filters win too.)
+// JFGPU_BLOOM_MODE=partitioned / jfgpu_bc_set_mode(b, 2) take the path for every batch, =direct / mode 1 for none.
+constexpr uint64_t kBloomKeysPartMinBytes = 1ull << 20;
+bool bloom_keys_auto_partitioned(const jfgpu_bloom*, size_t nbytes) { return (uint64_t)nbytes >= kBloomKeysPartMinBytes; }
+
 bool bloom_use_partitioned(const jfgpu_bloom* b, size_t nbytes) {
   if(!b->part_ok || b->mode == 1) return false;
   if(b->mode == 2) return true;
+  if(b->wide || b->nword) return bloom_keys_auto_partitioned(b, nbytes);
   return b->bp.n_seg >= 64 && (nbytes >= kBloomMinPiece || !b->pending.empty());
 }
 
@@ -95,6 +107,8 @@ int bloom_launch_direct(jfgpu_bloom* b, const uint8_t* base, int64_t lo, int64_t
 
 // One contract buffer [lo, hi) through P1b, in pieces that fit half of the arena (the other half is the flush's).
 int bloom_ingest(jfgpu_bloom* b, const uint8_t* base, int64_t lo, int64_t hi) {
+  const bool keys = b->wide || b->nword;                       // p1_bloom_keys_kernel: one workgroup per CU (118 KB of LDS at k = 128)
+  if(!b->g1 && keys) b->g1 = b->n_cu;
   if(!b->g1) {
     b->g1 = b->tun.bloom_p1_two ? 2 * b->n_cu : b->n_cu;      // workgroups of P1b: two per CU (78 KB of LDS each) or one (136 KB)
     // The ring P1b (p1_bloom_ring_kernel): one workgroup per CU, every owner lane may strand two reservations per bucket
@@ -162,7 +176,11 @@ int bloom_ingest(jfgpu_bloom* b, const uint8_t* base, int64_t lo, int64_t hi) {
                                b->view(), b->bp, b->g, pbase, plo, phi, cap, gcur, p.tot, p.items, b->d_mers)
 #define PBR(N, PER) rc = launch_lds(p1_bloom_ring_kernel<N, PER>, dim3(b->n_cu), dim3(kPBlock), (size_t)nb * kBloomRingBytes + kBloomRingBytes + (size_t)b->g.nbytes * 512, b->stream, \
                                     b->view(), b->bp, b->g, rd, pbase, plo, phi, cap, gcur, p.tot, p.items, b->d_mers, b->d_strag1, b->d_strag1_n)
-      if(b->p1_ring_per) {
+      if(b->nword) rc = launch_lds(p1_bloom_keys_kernel<NTable, kBloomKeysPer>, dim3(b->g1), dim3(kPBlock), p1_bloom_keys_lds(b->g.nbytes), b->stream,
+                                   b->view(), b->bp, b->ng, pbase, plo, phi, cap, gcur, p.tot, p.items, b->d_mers);
+      else if(b->wide) rc = launch_lds(p1_bloom_keys_kernel<WideTable, kBloomKeysPer>, dim3(b->g1), dim3(kPBlock), p1_bloom_keys_lds(b->g.nbytes), b->stream,
+                                       b->view(), b->bp, b->wg, pbase, plo, phi, cap, gcur, p.tot, p.items, b->d_mers);
+      else if(b->p1_ring_per) {
         const BloomP1RingDirect rd{b->view().data, b->bp.b2};
         if(b->p1_ring_per == 10) { if(b->g.nbytes == 8) PBR(8, 10); else if(b->g.nbytes == 6) PBR(6, 10); else PBR(0, 10); }
         else { if(b->g.nbytes == 8) PBR(8, 5); else PBR(0, 5); }

@@ -61,6 +61,60 @@ struct BloomRingDirect {
   __device__ void operator()(uint32_t dest, uint64_t item, uint32_t cnt) const { for(uint32_t i = 0; i < cnt; ++i) bloom_segment_item_direct_call(data, dest, (uint32_t)item); }
 };
 
+// ---- P1b: what its sort-based kernels share, for keys of every width ------------------------------------------------------
+// The nibble tables of both matrices in LDS, built from the byte tables: entry (nibble j, value v) at s_tn[16 j + v] is the
+// byte tables' entry of that value in that nibble, one uint4 holding both hashes; B.nbytes * 32 entries.  (For the kernels of
+// two- to four-word keys.  p1_bloom_granule_body keeps the loop in its own text: built through this function the
+// two-workgroup kernel spilled eight or nine more SGPRs, profiles/bloom_keys_p1_resources.txt.)
+__device__ __forceinline__ void bloom_nibble_tables_lds(uint4* s_tn, const DevBloom& B) {
+  for(uint32_t i = threadIdx.x; i < B.nbytes * 32; i += blockDim.x) {
+    const uint32_t j = i >> 4, v = i & 15u;
+    const uint32_t at = (j >> 1) * 256 + ((j & 1) ? (v << 4) : v);
+    const uint64_t a = B.tbl1[at], c = B.tbl2[at];
+    s_tn[i] = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)c, (uint32_t)(c >> 32));
+  }
+}
+
+// What every sort-based P1b does with a position once it has the k-mer's first cell and increment, whatever the key's
+// width: the nh cells in rounds of PER a lane, each round counted per bucket, sorted and placed by granule_emit; what finds
+// its region exhausted is bumped in place.  Called by every lane of the workgroup at every position (the rounds have
+// barriers); valid: this lane has a k-mer here.  Returns the updates this lane applied itself.
+template <int PER>
+__device__ __forceinline__ uint32_t bloom_p1_emit_cells(const DevBloom& B, const BloomPart& BP, GranuleLds& G, uint32_t nb, uint32_t cap,
+                                                        unsigned int* __restrict__ gcur, uint32_t* __restrict__ out, uint32_t* s_item, uint16_t* s_bkt,
+                                                        bool valid, uint64_t cell, uint64_t inc) {
+  uint32_t my_direct = 0;
+  for(uint32_t h0 = 0; h0 < B.nh; h0 += PER) {                                      // block-uniform trip count
+    lds_barrier();
+    for(uint32_t q = threadIdx.x; q < nb; q += blockDim.x) G.hist[q] = 0;
+    lds_barrier();
+    uint32_t it[PER], dr[PER];
+#pragma unroll
+    for(int e = 0; e < PER; ++e) {
+      dr[e] = 0xFFFFFFFFu; it[e] = 0;
+      if(valid && h0 + e < B.nh) {
+        uint64_t byte; uint32_t dig;
+        divmod5(cell, byte, dig);
+        const uint64_t seg = byte >> kBloomSegBits;
+        const uint32_t b = (uint32_t)(seg >> BP.b2);
+        it[e] = ((uint32_t)(seg & ((1u << BP.b2) - 1)) << kBloomItemLow) | ((uint32_t)(byte & 0xFFFFu) << 3) | dig;
+        dr[e] = (b << 16) | atomicAdd(&G.hist[b], 1u);
+        cell += inc; if(cell >= B.m) cell -= B.m;
+      }
+    }
+    my_direct += granule_emit(G, nb, cap, gcur, out, s_item, s_bkt, it, dr,
+                              [&](uint32_t b, uint32_t v) { bloom_item_direct(B, BP, b, v); });
+  }
+  return my_direct;
+}
+
+// the workgroup's k-mers onto the counter's tally: one atomic a wave
+__device__ __forceinline__ void bloom_p1_add_mers(unsigned long long* __restrict__ mers, uint32_t my_mers) {
+  uint64_t w = my_mers;
+  for(int o = 32; o > 0; o >>= 1) w += __shfl_down(w, o, 64);
+  if((threadIdx.x & 63) == 0 && w) atomicAdd(mers, (unsigned long long)w);
+}
+
 // ---- P1b ----------------------------------------------------------------------------------------------------
 // One block iteration = 16384 sequence positions.  The lanes roll their 16 windows together, one position per round:
 // a round gives every lane at most kBloomPer items (nh > kBloomPer takes more rounds), 10240 per block, sorted and
@@ -132,33 +186,11 @@ __device__ __forceinline__ void p1_bloom_granule_body(const DevBloom& B, const B
           inc = bloom_mod(hash_tables_t<NB>(s_t2, key, B.nbytes), B.m, B.recip);
         }
       }
-      for(uint32_t h0 = 0; h0 < B.nh; h0 += PER) {                                      // block-uniform trip count
-        lds_barrier();
-        for(uint32_t q = threadIdx.x; q < nb; q += blockDim.x) G.hist[q] = 0;
-        lds_barrier();
-        uint32_t it[PER], dr[PER];
-#pragma unroll
-        for(int e = 0; e < PER; ++e) {
-          dr[e] = 0xFFFFFFFFu; it[e] = 0;
-          if(valid && h0 + e < B.nh) {
-            uint64_t byte; uint32_t dig;
-            divmod5(cell, byte, dig);
-            const uint64_t seg = byte >> kBloomSegBits;
-            const uint32_t b = (uint32_t)(seg >> BP.b2);
-            it[e] = ((uint32_t)(seg & ((1u << BP.b2) - 1)) << kBloomItemLow) | ((uint32_t)(byte & 0xFFFFu) << 3) | dig;
-            dr[e] = (b << 16) | atomicAdd(&G.hist[b], 1u);
-            cell += inc; if(cell >= B.m) cell -= B.m;
-          }
-        }
-        my_direct += granule_emit(G, nb, cap, gcur, out, s_item, s_bkt, it, dr,
-                                  [&](uint32_t b, uint32_t v) { bloom_item_direct(B, BP, b, v); });
-      }
+      my_direct += bloom_p1_emit_cells<PER>(B, BP, G, nb, cap, gcur, out, s_item, s_bkt, valid, cell, inc);
     }
   }
   granule_finish(G, nb, cap, tot, out);
-  uint64_t w = my_mers;
-  for(int o = 32; o > 0; o >>= 1) w += __shfl_down(w, o, 64);
-  if((threadIdx.x & 63) == 0 && w) atomicAdd(mers, (unsigned long long)w);
+  bloom_p1_add_mers(mers, my_mers);
   (void)my_direct;
 }
 
@@ -392,3 +424,5 @@ __global__ __launch_bounds__(kBlock) void bloom_items_direct_kernel(DevBloom B, 
 }
 
 }  // namespace jfgpu
+
+#include "kernels_bloom_part_keys.hip.hpp"      // P1b for keys of two to four words

@@ -74,7 +74,8 @@ struct Tuning {
   int matrix = 0;                // JFGPU_MATRIX=xs|reference   the matrix family of tables created with matrix_kind 0 (0: not set -> the reference's)
   uint32_t bloom_cache_log2 = 28;// JFGPU_BLOOM_CACHE_LOG2 two-way sets of that cache (2^28 sets = 4 GB; tests: tiny caches evict all the time)
   // ---- Bloom counters (jfgpu_bloom_create)
-  int bloom_mode = 0;            // JFGPU_BLOOM_MODE=direct|partitioned      0: not set
+  int bloom_mode = 0;            // JFGPU_BLOOM_MODE=direct|partitioned      0: not set (auto: bloom_use_partitioned).  Both hold for every mer length up to 128:
+                                 //                        above 32 bases the partitioned path's P1b is p1_bloom_keys_kernel (profiles/bloom_keys_part_rate.txt)
   int bloom_p1_two = 1;          // JFGPU_BLOOM_P1_TWO     P1b as two workgroups per CU (rounds of 5 cells, nibble tables); 0: one, rounds of 10 (A/B)
   int bloom_p1_ring = 1;         // JFGPU_BLOOM_P1_RING    P1b through rings of 256 bytes where the filter gives it >= 200 buckets of at most 512 (0: the sort-based kernels; A/B)
   // ---- query formatters (jfgpu_qtext_create)

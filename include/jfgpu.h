@@ -398,16 +398,26 @@ int  jfgpu_reserve(jfgpu_table* t, uint64_t input_bytes);
  *          quality string of the wrong length give JFGPU_E_FORMAT and produce nothing: pass that
  *          chunk to the host parser, which implements the reference's general reader and its
  *          "Invalid fastq sequence" error (:292-309).
+ * Line ends: '\n', or any run of '\r' followed by '\n'.  A run of '\r' of ANY length is dropped where it touches a
+ * '\n' or the chunk's boundary on either side (before a line's '\n', between a '\n' and the next line or its '>', at
+ * the start or the end of the chunk) and kept where it stands between two other bytes of a line, as the reference's
+ * unbounded loops do (:267-287); there is no run length at which this changes and none that gives JFGPU_E_FORMAT.
+ * A FASTQ chunk with more than n / 8 + 16 line ends is also given JFGPU_E_FORMAT (the host parser's); at or below that
+ * the device parses it.
  * The returned buffer belongs to the parser and stays valid until the second-next parse call
- * (two buffers alternate), so one chunk can be counted while the next is parsed.  Calls are
- * synchronous: on return the buffer is complete. */
+ * (two buffers alternate), so one chunk can be counted while the next is parsed; a call that fails
+ * takes no turn and leaves the buffer of the call before it intact.  Calls are synchronous: on return
+ * the buffer is complete. */
 typedef struct jfgpu_parser jfgpu_parser;
 #define JFGPU_PARSE_FASTA    1u
 #define JFGPU_PARSE_FASTQ    2u
 #define JFGPU_PARSE_CONTINUE 4u
 int  jfgpu_parser_create(int device, uint32_t k, jfgpu_parser** out);
 void jfgpu_parser_destroy(jfgpu_parser* p);
-/* d_bytes: device memory, readable up to the next multiple of 16 bytes. */
+/* d_bytes: device memory at any alignment, readable up to the next multiple of 16 bytes.  The bytes are only read --
+ * unless a minimum quality is set (jfgpu_parser_set_min_quality): then a FASTQ chunk is EDITED IN PLACE, the masked
+ * bases of the caller's device buffer are 'N' on return.  jfgpu_parser_parse works on its own copy and never changes
+ * the caller's host bytes. */
 int  jfgpu_parser_parse_dev(jfgpu_parser* p, const char* d_bytes, size_t n, unsigned flags,
                             const char** d_out, size_t* n_out, uint64_t* n_records);
 /* bytes: host memory (e.g. the mmap of the file); copied to the device, then as above. */

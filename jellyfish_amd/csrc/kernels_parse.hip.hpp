@@ -22,6 +22,10 @@
 //     chunk boundary (trailing '\r' stripped :270-273, leading ones skipped :283-290), kept otherwise
 //   * every other byte is kept as is ('>' in the middle of a line included): the count kernels map
 //     non-ACGT to "break the k-mer" exactly as mer_iterator does
+//   A run of '\r' may have any length, as in the reference, whose two loops have no limit: what a run
+//   touches is decided once per run and tile ("runs of '\r'" below), never by a search of limited
+//   reach.  The work stays a constant per byte, plus, for each tile a run of '\r' leaves, one wave's
+//   walk to that run's other end.  The FASTQ sequence line follows the same '\r' rule.
 // FASTQ: strict 4-line records ('@' header, sequence, '+' line, quality).  Anything else -- wrapped
 // sequence, blank lines, a quality string of the wrong length -- is reported back so the caller can
 // hand the chunk to the host parser, which follows the reference's general reader including its
@@ -50,20 +54,6 @@ struct ParseResult { uint64_t total; uint64_t records; uint64_t lines; uint64_t 
 __device__ inline uint32_t byte_of(const uint4& w, int i) {
   const uint32_t x = i < 4 ? w.x : i < 8 ? w.y : i < 12 ? w.z : w.w;
   return (x >> ((i & 3) * 8)) & 0xFFu;
-}
-
-// Is p the first character of a line the way the reference's reader sees it?
-__device__ inline bool after_newline(const uint8_t* __restrict__ b, int64_t lo, int64_t p) {
-  int64_t q = p - 1;
-  for(int s = 0; s < 64 && q >= lo && b[q] == '\r'; ++s) --q;
-  return q < lo || b[q] == '\n';
-}
-
-__device__ inline bool cr_dropped(const uint8_t* __restrict__ b, int64_t lo, int64_t hi, int64_t p) {
-  int64_t q = p + 1;
-  for(int s = 0; s < 64 && q < hi && b[q] == '\r'; ++s) ++q;
-  if(q >= hi || b[q] == '\n') return true;
-  return after_newline(b, lo, p);
 }
 
 // exclusive "last non-zero" scan over the workgroup; *total = last non-zero of all
@@ -106,17 +96,84 @@ __device__ inline T block_scan_sum(T v, T* s_w, T* total) {
   return prefix + incl - v;
 }
 
-// What one thread knows about its 16 bytes before any cross-thread state: which are valid, which
-// are '\n', which open a FASTA header.
-struct LaneBytes {
-  uint4 w; int64_t p0; uint32_t valid, nl, hdr;
-};
+// ---- runs of '\r' ---------------------------------------------------------------------------
+// Whether a '\r' is dropped, and whether a '>' opens a header, depends on the nearest byte that is not a '\r' on each
+// side -- however far away that is.  That byte's class is found once per run and shared: inside a lane by carry
+// arithmetic on the lane's 16-bit masks, across lanes from three wave ballots, across waves through LDS, and for the two
+// runs that leave the tile by one wave each, which walks the raw bytes to the run's other end, 64 bytes a step.
+// Bytes outside [lo, hi) count as NB_EDGE: the chunk's boundary acts like a '\n'.
+enum : uint32_t { NB_CR = 0, NB_EDGE = 1, NB_DATA = 2 };   // still inside the run / '\n' or the chunk's edge / anything else
 
+// cr: the lane's '\r' bytes; edge: its NB_EDGE bytes; in: is the nearest non-'\r' byte below bit 0 NB_EDGE?
+// -> after: bytes whose nearest non-'\r' byte below is NB_EDGE ('\r' bytes of such a run included).
+// A run whose first byte follows an edge gets +1 at that byte: the carry clears the run and lands on the byte behind it.
+__device__ inline uint32_t after_edge(uint32_t cr, uint32_t edge, uint32_t in) {
+  const uint32_t seed = ((edge << 1) | in) & 0xFFFFu;
+  const uint32_t sum = cr + (seed & cr);
+  return (seed | (cr ^ sum)) & 0xFFFFu;
+}
+// the low 16 bits in reverse order  (JFGPU_EMU: the host emulation of tests/host/hip_emu has no __brev)
+__device__ inline uint32_t rev16(uint32_t x) {
+#if defined(JFGPU_EMU)
+  uint32_t r = 0;
+  for(int i = 0; i < 16; ++i) r |= ((x >> i) & 1u) << (15 - i);
+  return r;
+#else
+  return __brev(x) >> 16;
+#endif
+}
+
+// For every thread: the class of the nearest non-'\r' byte below its lane (left) and above it (right).  last / first:
+// the class of the lane's own last / first such byte, NB_CR when all 16 are '\r'.  edge_l / edge_r: what lies beyond the
+// tile, given by thread 0 and by the last thread.  s_cr: 2 * waves + 2 words, used by this call alone (one barrier).
+__device__ inline void cr_neighbours(uint32_t last, uint32_t first, uint32_t edge_l, uint32_t edge_r, uint32_t* s_cr,
+                                     uint32_t& left, uint32_t& right) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const uint64_t any = __ballot(last != NB_CR);                      // lanes that hold a byte other than '\r'
+  const uint64_t le = __ballot(last == NB_EDGE), fe = __ballot(first == NB_EDGE);
+  const uint64_t below = any & (((uint64_t)1 << lane) - 1);
+  const uint64_t above = lane == 63 ? 0 : (any >> (lane + 1)) << (lane + 1);
+  uint32_t l = NB_CR, r = NB_CR;
+  if(below) l = (le >> (63 - __builtin_clzll(below)) & 1) ? NB_EDGE : NB_DATA;
+  if(above) r = (fe >> __builtin_ctzll(above) & 1) ? NB_EDGE : NB_DATA;
+  if(lane == 0) {
+    s_cr[wave] = any ? ((le >> (63 - __builtin_clzll(any)) & 1) ? NB_EDGE : NB_DATA) : NB_CR;
+    s_cr[nw + wave] = any ? ((fe >> __builtin_ctzll(any) & 1) ? NB_EDGE : NB_DATA) : NB_CR;
+  }
+  if(threadIdx.x == 0) s_cr[2 * nw] = edge_l;
+  if(threadIdx.x == blockDim.x - 1) s_cr[2 * nw + 1] = edge_r;
+  __syncthreads();
+  for(uint32_t w = wave; l == NB_CR && w-- > 0; ) l = s_cr[w];
+  if(l == NB_CR) l = s_cr[2 * nw];
+  for(uint32_t w = wave + 1; r == NB_CR && w < nw; ++w) r = s_cr[nw + w];
+  if(r == NB_CR) r = s_cr[2 * nw + 1];
+  left = l; right = r;
+}
+
+// The class of the nearest byte that is not '\r' at q0 or beyond it in direction dir (-1 / +1).  Called by a whole wave,
+// which looks at 64 bytes a step; bytes outside [lo, hi) end the walk as NB_EDGE.
+__device__ inline uint32_t cr_run_end(const uint8_t* __restrict__ b, int64_t lo, int64_t hi, int64_t q0, int dir) {
+  for(int64_t q = q0 + dir * (int64_t)(threadIdx.x & 63); ; q += dir * 64) {
+    const uint32_t c = (q < lo || q >= hi) ? (uint32_t)'\n' : (uint32_t)b[q];
+    const uint64_t stop = __ballot(c != '\r');
+    if(stop) return __shfl(c == '\n' ? (uint32_t)NB_EDGE : (uint32_t)NB_DATA, __builtin_ctzll(stop), 64);
+  }
+}
+
+// What one thread knows about its 16 bytes before any line state: which are valid, which are '\n', which open a FASTA
+// header, which are '\r' that a line end or the chunk's edge takes away.
+struct LaneBytes {
+  uint4 w; int64_t p0; uint32_t valid, nl, hdr, crdrop;
+};
+constexpr int kCrWords = 2 * (kParseBlock / 64) + 2;
+
+// (every thread of the workgroup calls this: it holds a barrier)
 template <uint32_t FMT>
-__device__ inline LaneBytes lane_load(const uint8_t* __restrict__ b, int64_t lo, int64_t hi, int64_t tile) {
+__device__ inline LaneBytes lane_load(const uint8_t* __restrict__ b, int64_t lo, int64_t hi, int64_t tile, uint32_t* s_cr) {
   LaneBytes L;
   L.p0 = tile * kParseTile + (int64_t)threadIdx.x * kParseLane;
-  L.w = make_uint4(0, 0, 0, 0); L.valid = L.nl = L.hdr = 0;
+  L.w = make_uint4(0, 0, 0, 0); L.valid = L.nl = L.hdr = L.crdrop = 0;
+  uint32_t cr = 0, gt = 0;
   if(L.p0 < hi && L.p0 + kParseLane > lo) {
     L.w = *reinterpret_cast<const uint4*>(b + L.p0);
 #pragma unroll
@@ -126,9 +183,26 @@ __device__ inline LaneBytes lane_load(const uint8_t* __restrict__ b, int64_t lo,
       L.valid |= 1u << i;
       const uint32_t c = byte_of(L.w, i);
       if(c == '\n') L.nl |= 1u << i;
-      if(FMT == PARSE_FASTA && c == '>' && after_newline(b, lo, p)) L.hdr |= 1u << i;
+      if(c == '\r') cr |= 1u << i;
+      if(FMT == PARSE_FASTA && c == '>') gt |= 1u << i;
     }
   }
+  const uint32_t edge = (L.nl | ~L.valid) & 0xFFFFu, other = ~cr & 0xFFFFu;
+  const uint32_t last = other ? ((edge >> (31 - __builtin_clz(other)) & 1) ? NB_EDGE : NB_DATA) : NB_CR;
+  const uint32_t first = other ? ((edge >> __builtin_ctz(other) & 1) ? NB_EDGE : NB_DATA) : NB_CR;
+  // the two runs that may leave the tile are followed to their other end by the wave that holds the tile's edge
+  uint32_t edge_l = NB_EDGE, edge_r = NB_EDGE;
+  const uint32_t wave = threadIdx.x >> 6;
+  if(wave == 0 && __ballot(threadIdx.x == 0 && ((cr | gt) & 1u)))
+    edge_l = cr_run_end(b, lo, hi, L.p0 - (int64_t)threadIdx.x * kParseLane - 1, -1);
+  if(wave == (blockDim.x >> 6) - 1 && __ballot(threadIdx.x == blockDim.x - 1 && (cr >> (kParseLane - 1) & 1u)))
+    edge_r = cr_run_end(b, lo, hi, L.p0 + ((int64_t)blockDim.x - threadIdx.x) * kParseLane, +1);
+  uint32_t left, right;
+  cr_neighbours(last, first, edge_l, edge_r, s_cr, left, right);
+  const uint32_t after = after_edge(cr, edge, left == NB_EDGE);
+  const uint32_t before = rev16(after_edge(rev16(cr), rev16(edge), right == NB_EDGE));
+  L.hdr = gt & after;
+  L.crdrop = cr & (after | before);
   return L;
 }
 
@@ -138,12 +212,12 @@ __device__ inline uint32_t lane_last_event(const LaneBytes& L) {
 }
 
 // FASTA: output character for byte i given the state before it (0 = dropped); updates the state.
-__device__ inline uint32_t fasta_step(const LaneBytes& L, int i, uint32_t& st, const uint8_t* __restrict__ b, int64_t lo, int64_t hi) {
+__device__ inline uint32_t fasta_step(const LaneBytes& L, int i, uint32_t& st) {
   const uint32_t c = byte_of(L.w, i);
   if(L.hdr >> i & 1) { st = EV_HEADER; return 'N'; }
   if(L.nl >> i & 1) { st = EV_SEQ; return 0; }
   if(st == EV_HEADER) return 0;
-  if(c == '\r') return cr_dropped(b, lo, hi, L.p0 + i) ? 0u : c;
+  if(L.crdrop >> i & 1) return 0;
   return c;
 }
 
@@ -160,9 +234,10 @@ __global__ __launch_bounds__(kParseBlock) void parse_agg_kernel(const uint8_t* _
                                                                 int64_t tile0, ParseAgg* __restrict__ agg) {
   __shared__ uint32_t s_w[kParseBlock / 64];
   __shared__ uint32_t s_c[4];
+  __shared__ uint32_t s_cr[kCrWords];
   const int64_t tile = tile0 + blockIdx.x;
   if(threadIdx.x < 4) s_c[threadIdx.x] = 0;
-  const LaneBytes L = lane_load<FMT>(b, lo, hi, tile);
+  const LaneBytes L = lane_load<FMT>(b, lo, hi, tile, s_cr);
   uint32_t acc = 0;                                       // four 8-bit counters
   uint32_t tile_ev = 0;
   if(FMT == PARSE_FASTA) {
@@ -172,7 +247,7 @@ __global__ __launch_bounds__(kParseBlock) void parse_agg_kernel(const uint8_t* _
       if(!(L.valid >> i & 1)) continue;
       const bool ev = (L.hdr | L.nl) >> i & 1;
       uint32_t s2 = st == EV_NONE ? (uint32_t)EV_SEQ : st;
-      const uint32_t o = fasta_step(L, i, s2, b, lo, hi);
+      const uint32_t o = fasta_step(L, i, s2);
       if(o) acc += (seen || ev) ? 0x100u : 1u;           // the header's own 'N' counts as "after"
       if(ev) { seen = true; st = s2; }
     }
@@ -183,7 +258,7 @@ __global__ __launch_bounds__(kParseBlock) void parse_agg_kernel(const uint8_t* _
       const uint32_t c = byte_of(L.w, i);
       if(fastq_line_start(L, i, b, lo)) acc += 1u << (((0u - r) & 3) * 8);          // 'N' when this line has phase 0
       if(c == '\n') ++r;
-      else if(c != '\r' || !cr_dropped(b, lo, hi, L.p0 + i)) acc += 1u << (((1u - r) & 3) * 8);   // kept when phase 1
+      else if(!(L.crdrop >> i & 1)) acc += 1u << (((1u - r) & 3) * 8);   // kept when phase 1
     }
   }
 #pragma unroll
@@ -249,9 +324,10 @@ __global__ __launch_bounds__(kParseBlock) void parse_emit_kernel(const uint8_t* 
                                                                  ParseResult* __restrict__ res) {
   __shared__ uint32_t s_w[kParseBlock / 64];
   __shared__ uint8_t s_out[kParseTile];
+  __shared__ uint32_t s_cr[kCrWords];
   const int64_t tile = tile0 + blockIdx.x;
   const ParseStart S = start[blockIdx.x];
-  const LaneBytes L = lane_load<FMT>(b, lo, hi, tile);
+  const LaneBytes L = lane_load<FMT>(b, lo, hi, tile, s_cr);
   uint32_t recs = 0;
   uint32_t st_in = 0; uint64_t line_in = 0;
   if(FMT == PARSE_FASTA) {
@@ -268,7 +344,7 @@ __global__ __launch_bounds__(kParseBlock) void parse_emit_kernel(const uint8_t* 
 #pragma unroll
       for(int i = 0; i < kParseLane; ++i) {
         if(!(L.valid >> i & 1)) continue;
-        const uint32_t c = fasta_step(L, i, st, b, lo, hi);
+        const uint32_t c = fasta_step(L, i, st);
         if(c) put(c);
       }
     } else {
@@ -279,7 +355,7 @@ __global__ __launch_bounds__(kParseBlock) void parse_emit_kernel(const uint8_t* 
         const uint32_t c = byte_of(L.w, i);
         if((line & 3) == 0 && fastq_line_start(L, i, b, lo)) put('N');
         if(c == '\n') ++line;
-        else if((line & 3) == 1 && (c != '\r' || !cr_dropped(b, lo, hi, L.p0 + i))) put(c);
+        else if((line & 3) == 1 && !(L.crdrop >> i & 1)) put(c);
       }
     }
   };

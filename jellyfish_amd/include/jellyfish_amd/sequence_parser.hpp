@@ -7,8 +7,9 @@
 //     "Unsupported format" (:134-148); empty files are skipped (:135)
 //   * header lines dropped, sequence lines of a record concatenated with '\n' and
 //     trailing '\r' removed (:260-274), one 'N' written between records (:173-176)
-//   * FASTQ: sequence lines up to a line starting with '+', then exactly seq_len
-//     quality characters are skipped, the next record must start with '@'
+//   * FASTQ: sequence lines up to a line starting with '+', then seq_len quality
+//     characters are skipped (seq_len + 1 where the last quality line is that
+//     long: istream::ignore's count, :296), the next record must start with '@'
 //     (:187-217, :290-307), else "Invalid fastq sequence"
 //   * consecutive buffers of one file overlap by k-1 characters (the "seam",
 //     :164-167,182-184) so no k-mer is lost or seen twice; nothing is carried
@@ -247,7 +248,9 @@ private:
         p = e < end ? e + 1 : end;
       }
       p = skip_newlines(p, end);
-      if(quals != seq_len || (p < end && *p != '@')) throw std::runtime_error("Invalid fastq sequence");
+      // (the reference skips the quality with istream::ignore(seq_len - quals + 1, line end), :296: it takes one character
+      // more than the sequence has when no line end comes first, so a last quality line one character too long passes)
+      if((quals != seq_len && quals != seq_len + 1) || (p < end && *p != '@')) throw std::runtime_error("Invalid fastq sequence");
       if(p < end) {
         buf_.push_back('N');
         p = line_end(p, end); if(p < end) ++p;

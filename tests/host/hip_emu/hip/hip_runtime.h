@@ -447,6 +447,7 @@ template <typename T> static inline T __shfl_xor(T v, unsigned o, int = 64) { re
 static inline unsigned long long __ballot(int pred) { return ::hip_emu::wave_ballot(pred); }
 template <typename T> static inline T __shfl(T v, int src, int = 64) { return ::hip_emu::lane_read(v, src); }
 static inline int __popc(unsigned v) { return __builtin_popcount(v); }
+static inline unsigned __brev(unsigned v) { unsigned r = 0; for(int i = 0; i < 32; ++i) r |= ((v >> i) & 1u) << (31 - i); return r; }
 static inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
 static inline int __ffs(int v) { return __builtin_ffs(v); }
 static inline int __ffsll(long long v) { return __builtin_ffsll(v); }

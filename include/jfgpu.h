@@ -614,6 +614,49 @@ int  jfgpu_qtext_last_ms(jfgpu_qtext* x, double out4[4]);
 /* The last run's pieces, positions, lines and bytes. */
 int  jfgpu_qtext_counts(jfgpu_qtext* x, uint64_t out4[4]);
 
+/* ---- sorted records: `query -s` answered from a binary/sorted body as the file has it ----
+ * Replaces binary_query (include/jellyfish/binary_dumper.hpp:112-213) under query_from_sequence
+ * (sub_commands/query_main.cc:44-51).  The records of such a file ascend by (pos, key), pos = (M * key) & (size - 1), and the
+ * positions of hashed keys are uniform, so the body is its own index: it is uploaded unchanged, one kernel cuts it into
+ * 2^bucket_bits buckets by the top bits of pos, and a look-up scans the records of its key's bucket for the key.  No table
+ * is built: device memory is the body's bytes and about one byte a record, whatever k is. */
+typedef struct jfgpu_sorted jfgpu_sorted;
+typedef struct {
+  uint32_t k, canonical, counter_len;   /* counter_len 1..8: header.counter_len() */
+  uint32_t matrix_rows;                 /* header.matrix().r */
+  uint64_t size;                        /* header.size(); must be 1 << matrix_rows */
+  const uint64_t* matrix_columns;       /* 2k columns as in jfgpu_params; NULL: identity */
+  int32_t  device;                      /* -1 = current */
+  uint32_t records_per_bucket;          /* 0: the default (8) */
+} jfgpu_sorted_params;
+/* binary_dumper.hpp:112-213 has no counterpart: what jfgpu_sorted_create will use.  bucket_bits: the smallest B with
+ * n_records >> B <= records_per_bucket, at most log2(size).  device_bytes: the body, 32 zeroed bytes behind it,
+ * 8 * (2^B + 1) bytes of index and the matrix's byte tables (2048 bytes a key byte; none are kept for the identity
+ * matrix).  Pure: no device is needed.  JFGPU_E_UNSUPPORTED for k > 128 or counter_len > 8, JFGPU_E_INVALID for k or
+ * counter_len of 0 and a size that is no power of two. */
+int  jfgpu_sorted_plan(uint64_t n_records, uint64_t size, uint32_t k, uint32_t counter_len, uint32_t records_per_bucket,
+                       uint32_t* bucket_bits, uint64_t* device_bytes);
+/* binary_query's constructor (binary_dumper.hpp:112-145) on the device.  body: host memory at any alignment (the mmap of
+ * the file past its header) holding n_records records of ceil(2k / 8) + counter_len bytes; it is read during the call
+ * only.  Fails, with nothing left allocated: JFGPU_E_INVALID "records are not in strictly increasing (pos, key) order";
+ * JFGPU_E_INVALID when size is not 1 << matrix_rows; JFGPU_E_ALLOC when the device cannot take device_bytes;
+ * JFGPU_E_UNSUPPORTED for k > 128 or counter_len > 8.  n_records == 0 is legal: every look-up answers "not found". */
+int  jfgpu_sorted_create(const jfgpu_sorted_params* p, const void* body, uint64_t n_records, jfgpu_sorted** out);
+void jfgpu_sorted_destroy(jfgpu_sorted* s);
+/* n_records, bucket_bits, records of the longest bucket, device bytes held, microseconds of the upload and of the index
+ * kernels in jfgpu_sorted_create. */
+int  jfgpu_sorted_info(const jfgpu_sorted* s, uint64_t out6[6]);
+/* query_from_sequence (query_main.cc:44-51) over one contract buffer, binary_query::check (binary_dumper.hpp:191-213) per
+ * k-mer: the contract of jfgpu_query_ascii_dev / jfgpu_query_ascii, asynchronous on the object's own stream in the _dev
+ * form (any later call of the same object is ordered behind it). */
+int  jfgpu_sorted_query_ascii_dev(jfgpu_sorted* s, const char* d_bases, size_t n, uint64_t* d_vals, uint8_t* d_flags);
+int  jfgpu_sorted_query_ascii(jfgpu_sorted* s, const char* bases, size_t n, uint64_t* vals, uint8_t* flags);
+/* binary_query::check (binary_dumper.hpp:191-213) for n encoded keys, the layout and masking of jfgpu_lookup; found may
+ * be NULL. */
+int  jfgpu_sorted_lookup(jfgpu_sorted* s, const uint64_t* keys, size_t n, uint64_t* vals, uint8_t* found);
+/* query_from_sequence (query_main.cc:44-51) with the lines built on the device: jfgpu_query_text answered by the records. */
+int  jfgpu_sorted_query_text(jfgpu_sorted* s, jfgpu_qtext* x, const char* bases, size_t n, jfgpu_text_sink sink, void* user);
+
 /* ---- measurement helpers (bench.py; not part of the reference surface) -- */
 /* Per-kernel HIP-event timing on the table's stream.  which: 0 count (direct), 1 add_keys,
  * 2 shard partition, 3 lookup, 4 P1 partition, 5 P2 partition, 6 tile insert, 7 items-direct.  Returns accumulated milliseconds and launches since the

@@ -70,6 +70,12 @@ class QTextParams(C.Structure):
     _fields_ = [("k", C.c_uint32), ("device", C.c_int32), ("piece_positions", C.c_uint64)]
 
 
+class SortedParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("canonical", C.c_uint32), ("counter_len", C.c_uint32), ("matrix_rows", C.c_uint32),
+                ("size", C.c_uint64), ("matrix_columns", C.POINTER(C.c_uint64)), ("device", C.c_int32),
+                ("records_per_bucket", C.c_uint32)]
+
+
 TEXT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64)
 TEXT_COLUMN, TEXT_FASTA = 0, 1
 MERGE_SUM, MERGE_MIN, MERGE_MAX, MERGE_JACCARD = range(4)
@@ -185,6 +191,14 @@ SIGNATURES = {
     "jfgpu_bc_query_text": (C.c_int, [_P, _P, _P, C.c_size_t, TEXT_SINK, _P]),
     "jfgpu_qtext_last_ms": (C.c_int, [_P, _P]),
     "jfgpu_qtext_counts": (C.c_int, [_P, _P]),
+    "jfgpu_sorted_plan": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "jfgpu_sorted_create": (C.c_int, [C.POINTER(SortedParams), _P, C.c_uint64, C.POINTER(_P)]),
+    "jfgpu_sorted_destroy": (None, [_P]),
+    "jfgpu_sorted_info": (C.c_int, [_P, _P]),
+    "jfgpu_sorted_query_ascii_dev": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "jfgpu_sorted_query_ascii": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "jfgpu_sorted_lookup": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "jfgpu_sorted_query_text": (C.c_int, [_P, _P, _P, C.c_size_t, TEXT_SINK, _P]),
     "jfgpu_set_growth": (C.c_int, [_P, C.c_int]),
     "jfgpu_reference_matrix": (C.c_int, [C.c_uint32, C.c_uint32, _P]),
     "jfgpu_table_bytes": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -728,6 +742,78 @@ class Bloom:
         return out
 
 
+def sorted_plan(n_records, size, k, counter_len, records_per_bucket=0):
+    """(bucket_bits, device_bytes) jfgpu_sorted_create will use for such a body (jfgpu_sorted_plan; needs no device)."""
+    bits, nbytes = C.c_uint32(), C.c_uint64()
+    _check(load().jfgpu_sorted_plan(int(n_records), int(size), k, counter_len, records_per_bucket, C.byref(bits), C.byref(nbytes)))
+    return bits.value, nbytes.value
+
+
+class Sorted:
+    """The records of a binary/sorted database in HBM as the file has them, with a bucket index over them (jfgpu_sorted*):
+    look-ups without a table.  body: a uint8 array of whole records, ascending by (pos, key); matrix: the header's 2k
+    columns, None for the identity matrix."""
+
+    def __init__(self, k, size, matrix, counter_len, body, canonical=True, device=-1, records_per_bucket=0, matrix_rows=None):
+        self._lib = load()
+        self.k, self.kw, self.kb, self.counter_len = k, (2 * k + 63) // 64, (2 * k + 7) // 8, counter_len
+        body = np.ascontiguousarray(body, dtype=np.uint8).reshape(-1)
+        n = len(body) // (self.kb + counter_len) if counter_len else 0
+        p = SortedParams(k=k, canonical=int(bool(canonical)), counter_len=counter_len,
+                         matrix_rows=int(size).bit_length() - 1 if matrix_rows is None else matrix_rows, size=int(size),
+                         device=device, records_per_bucket=records_per_bucket)
+        self._matrix = None
+        if matrix is not None:
+            self._matrix = np.ascontiguousarray(matrix, dtype=np.uint64)
+            p.matrix_columns = self._matrix.ctypes.data_as(C.POINTER(C.c_uint64))
+        h = _P()
+        _check(self._lib.jfgpu_sorted_create(C.byref(p), body.ctypes.data if len(body) else None, n, C.byref(h)))
+        self._h = h
+        self.n_records = n
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.jfgpu_sorted_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def info(self):
+        """dict: n_records, bucket_bits, longest_bucket, device_bytes, upload_us, index_us."""
+        out = np.zeros(6, dtype=np.uint64)
+        _check(self._lib.jfgpu_sorted_info(self._h, out.ctypes.data))
+        return dict(zip(("n_records", "bucket_bits", "longest_bucket", "device_bytes", "upload_us", "index_us"), (int(x) for x in out)))
+
+    def query_ascii(self, seq: bytes):
+        """The count of every k-mer of a contract buffer, indexed by the position of the k-mer's last base:
+        (vals uint64[n], flags uint8[n] of Q_MER | Q_FOUND | Q_REVCOMP), as Table.query_ascii."""
+        buf = np.frombuffer(seq, dtype=np.uint8)
+        vals = np.zeros(len(seq), dtype=np.uint64)
+        flags = np.zeros(len(seq), dtype=np.uint8)
+        _check(self._lib.jfgpu_sorted_query_ascii(self._h, buf.ctypes.data if len(seq) else None, len(seq),
+                                                  vals.ctypes.data if len(seq) else None, flags.ctypes.data if len(seq) else None))
+        return vals, flags
+
+    def query_ascii_dev(self, d_bases, n, d_vals, d_flags=None):
+        """Asynchronous on the object's stream: any host form of the same object (lookup, query_ascii) ends behind it."""
+        _check(self._lib.jfgpu_sorted_query_ascii_dev(self._h, _ptr(d_bases), n, _ptr(d_vals), _ptr(d_flags)))
+
+    def lookup(self, keys):
+        """keys: uint64[n, kw] (bits above 2k ignored).  Returns (vals uint64[n], found bool[n])."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, self.kw)
+        vals = np.zeros(len(keys), dtype=np.uint64)
+        found = np.zeros(len(keys), dtype=np.uint8)
+        _check(self._lib.jfgpu_sorted_lookup(self._h, keys.ctypes.data if len(keys) else None, len(keys),
+                                             vals.ctypes.data if len(keys) else None, found.ctypes.data if len(keys) else None))
+        return vals, found.astype(bool)
+
+
 def opt_m(fp, n):
     return load().jfgpu_bc_opt_m(fp, n)
 
@@ -978,6 +1064,10 @@ class QueryText:
     def run_bloom(self, bloom, seq: bytes, sink=None):
         """jfgpu_bc_query_text: the same, answered by a Bloom counter."""
         return self._run(self._lib.jfgpu_bc_query_text, bloom._h, seq, sink)
+
+    def run_sorted(self, sorted_records, seq: bytes, sink=None):
+        """jfgpu_sorted_query_text: the same, answered by the records of a binary/sorted body (Sorted)."""
+        return self._run(self._lib.jfgpu_sorted_query_text, sorted_records._h, seq, sink)
 
     def last_ms(self):
         """(upload, kernels, download, sink) milliseconds of the last run."""

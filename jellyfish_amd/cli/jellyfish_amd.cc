@@ -1205,11 +1205,13 @@ int query_main(int argc, char* argv[]) {
   struct { binary_query* b; bloom_query* f; uint64_t check(const mer_dna& m) const { return b ? b->check(m) : f->check(m); } } bq{bin.get(), bloom.get()};
   const bool canonical = header.canonical();
   const unsigned k = mer_dna::k();
-  // query_from_sequence (query_main.cc:44-51) answered by the device.  A binary/sorted file's records go
-  // back into a table under the header's own matrix (jfgpu_add_key_vals); a bloomcounter file's body goes into a counter
-  // under the header's two matrices (jfgpu_bc_load).  The contract buffers of the -s files are handed over as they are:
-  // the k-mers are rolled, made canonical and looked up in one kernel, for every mer length, and the lines are built on
-  // the device from the answer (jfgpu_query_text / jfgpu_bc_query_text), whose sink writes them to the output stream.
+  // query_from_sequence (query_main.cc:44-51) answered by the device.  A binary/sorted file's body goes up
+  // as it is and gets a bucket index (jfgpu_sorted_create): the records are looked up where they lie, no table is built.
+  // JFGPU_QUERY_TABLE=1 puts the records back into a table under the header's own matrix instead (jfgpu_add_key_vals), a
+  // second implementation to compare with.  A bloomcounter file's body goes into a counter under the header's two matrices
+  // (jfgpu_bc_load).  The contract buffers of the -s files are handed over as they are: the k-mers are rolled, made
+  // canonical and looked up in one kernel, for every mer length, and the lines are built on the device from the answer
+  // (jfgpu_sorted_query_text / jfgpu_query_text / jfgpu_bc_query_text), whose sink writes them to the output stream.
   // JFGPU_QUERY_FORMAT_HOST=1 keeps the look-up on the device and builds the lines here, from a count and three flag bits
   // per position.  JFGPU_QUERY_HOST=1, no device or a Bloom counter body of another length than its header's size take the
   // host loop below, and so does a device that fails before anything was written (no room for the table, ...).
@@ -1219,20 +1221,33 @@ int query_main(int argc, char* argv[]) {
   const bool bloom_fits = bloom && map.length() - header.offset() == header.size() / 5 + (header.size() % 5 != 0);
   if(!sequences.empty() && (bin || bloom_fits) && !getenv("JFGPU_QUERY_HOST") && jfgpu_device_count() > 0) {
     jfgpu_table* t = nullptr;
+    jfgpu_sorted* sd = nullptr;
     jfgpu_bloom* bc = nullptr;
     jfgpu_qtext* qx = nullptr;
     auto release = [&]() {
       if(qx) jfgpu_qtext_destroy(qx);
       if(t) jfgpu_destroy(t);
+      if(sd) jfgpu_sorted_destroy(sd);
       if(bc) jfgpu_bc_destroy(bc);
-      qx = nullptr; t = nullptr; bc = nullptr;
+      qx = nullptr; t = nullptr; sd = nullptr; bc = nullptr;
     };
+    auto have = [&]() { return t || sd || bc; };
     auto to_host = [&](const char* what) {                   // nothing has been written yet: the host path answers
       if(!getenv("JFGPU_QUIET")) std::cerr << "jellyfish-amd query: " << what << " (" << jfgpu_last_error() << "): answering on the host\n";
       release();
     };
     const auto load_t0 = std::chrono::steady_clock::now();    // (the trace says what bringing the database to the device took)
-    if(bin) {
+    const bool by_table = bin && getenv("JFGPU_QUERY_TABLE") != nullptr;
+    if(bin && !by_table) {
+      const header_matrix hm = header.matrix();
+      const size_t rec = (2 * k + 7) / 8 + header.counter_len();
+      jfgpu_sorted_params p; memset(&p, 0, sizeof p);
+      p.k = k; p.canonical = canonical; p.counter_len = (uint32_t)header.counter_len(); p.matrix_rows = hm.r; p.size = header.size(); p.device = -1;
+      if(const char* per = getenv("JFGPU_QUERY_PER_BUCKET")) p.records_per_bucket = (uint32_t)strtoul(per, 0, 10);   // (tools/query_sorted_bench.sh)
+      if(!hm.identity) p.matrix_columns = hm.columns.data();
+      if(!hm.identity && hm.columns.size() != 2 * k) to_host("the header's matrix has not 2k columns");
+      else if(jfgpu_sorted_create(&p, map.base() + header.offset(), (map.length() - header.offset()) / rec, &sd) != JFGPU_OK) { sd = nullptr; to_host("database records not taken by the device"); }
+    } else if(bin) {
       jfgpu_params p; memset(&p, 0, sizeof p);
       p.k = k; p.canonical = canonical; p.size = header.size(); p.device = -1; p.out_counter_len = 8;
       const header_matrix hm = header.matrix();
@@ -1262,12 +1277,12 @@ int query_main(int argc, char* argv[]) {
     }
     const double load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - load_t0).count();
     const bool format_host = getenv("JFGPU_QUERY_FORMAT_HOST") != nullptr;
-    if((t || bc) && !format_host) {
+    if(have() && !format_host) {
       jfgpu_qtext_params qp; memset(&qp, 0, sizeof qp);
       qp.k = k; qp.device = -1;
       if(jfgpu_qtext_create(&qp, &qx) != JFGPU_OK) { qx = nullptr; to_host("device formatter not created"); }
     }
-    if(t || bc) {
+    if(have()) {
       std::vector<uint64_t> vals; std::vector<uint8_t> flags;
       std::string text;
       uint64_t positions = 0, n_mers = 0;
@@ -1285,19 +1300,21 @@ int query_main(int argc, char* argv[]) {
         to_host(what);
       };
       for(const auto& path : sequences) {
-        if(!t && !bc) break;
+        if(!have()) break;
         sequence_parser parser(k, (size_t)8 << 20);
         parser.parse_file(path.c_str(), [&](const char* buf, size_t n) {
-          if((!t && !bc) || !n) return;
+          if(!have() || !n) return;
           if(qx) {
-            if((t ? jfgpu_query_text(t, qx, buf, n, sink_write, &sk) : jfgpu_bc_query_text(bc, qx, buf, n, sink_write, &sk)) != JFGPU_OK) { failed("device query failed"); return; }
+            if((sd ? jfgpu_sorted_query_text(sd, qx, buf, n, sink_write, &sk) : t ? jfgpu_query_text(t, qx, buf, n, sink_write, &sk)
+                   : jfgpu_bc_query_text(bc, qx, buf, n, sink_write, &sk)) != JFGPU_OK) { failed("device query failed"); return; }
             double m4[4];
             if(jfgpu_qtext_last_ms(qx, m4) == JFGPU_OK) for(int i = 0; i < 4; ++i) ms[i] += m4[i];
             positions += n;
             return;
           }
           vals.resize(n); flags.resize(n);
-          if((t ? jfgpu_query_ascii(t, buf, n, vals.data(), flags.data()) : jfgpu_bc_query_ascii(bc, buf, n, vals.data(), flags.data())) != JFGPU_OK) { failed("device query failed"); return; }
+          if((sd ? jfgpu_sorted_query_ascii(sd, buf, n, vals.data(), flags.data()) : t ? jfgpu_query_ascii(t, buf, n, vals.data(), flags.data())
+                 : jfgpu_bc_query_ascii(bc, buf, n, vals.data(), flags.data())) != JFGPU_OK) { failed("device query failed"); return; }
           text.clear();
           for(size_t i = 0; i < n; ++i) {
             if(!(flags[i] & JFGPU_Q_MER)) continue;
@@ -1312,8 +1329,9 @@ int query_main(int argc, char* argv[]) {
           positions += n; wrote = true;
         });
       }
-      if(t || bc) {
+      if(have()) {
         const bool device_lines = qx != nullptr;
+        const char* lookup = sd ? " lookup=records" : t ? " lookup=table" : "";
         release();
         sequences.clear();
         on_device = true;
@@ -1321,7 +1339,7 @@ int query_main(int argc, char* argv[]) {
           char times[160];
           snprintf(times, sizeof times, " load_ms=%.3f upload_ms=%.3f kernels_ms=%.3f download_ms=%.3f sink_ms=%.3f", load_ms, ms[0], ms[1], ms[2], ms[3]);
           std::cerr << "query: device k=" << k << " positions=" << positions << " db=" << (bin ? "binary" : "bloomcounter")
-                    << " format=" << (device_lines ? "device" : "host") << times << " mers=" << (device_lines ? sk.lines : n_mers) << "\n";
+                    << " format=" << (device_lines ? "device" : "host") << times << lookup << " mers=" << (device_lines ? sk.lines : n_mers) << "\n";
         }
       }
     }

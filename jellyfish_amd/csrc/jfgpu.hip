@@ -38,6 +38,7 @@
 #include "kernels_bgzf.hip.hpp"
 #include "kernels_stream.hip.hpp"
 #include "kernels_merge.hip.hpp"
+#include "kernels_sorted.hip.hpp"
 #include "kernels_text.hip.hpp"
 #include "kernels_qtext.hip.hpp"
 #include "kernels_comm.hip.hpp"
@@ -1425,3 +1426,4 @@ int jfgpu_memcpy_d2h(jfgpu_table* t, void* dst, const void* d_src, size_t bytes)
 #include "abi_merge.inl"
 #include "abi_text.inl"
 #include "abi_qtext.inl"
+#include "abi_sorted.inl"
